@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- the driver's benchmark contract.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run measures the primary workload only: set-up, warm-up, K timed steps, the result line.  --full adds
+everything else below (secondary and tertiary workloads, CPU baselines and the correctness checks that ride on them).
+--dump-outputs DIR writes what the timed primary path computed in its last step as DIR/<name>.npy (see dump_outputs).
 
 Primary workload (BASELINE.json configs[1], the configuration the metric is quoted on):
 square fp32 matrix_multiply, N = 4096, both operands and the output resident in HBM, one
@@ -22,8 +26,8 @@ Tertiary workload (N = 1): BASELINE configs[4], the U-Net's 128->128 3x3 convolu
 forward + both gradients, with its own roofline and CPU baseline ("tertiary").
 
 Rank 0 prints ONE JSON line carrying, besides the contract keys, `roofline` (dominant kernel vs the
-gfx950 fp32 MFMA peak, timed with HIP events on the launch stream) and `cpu_baseline` (the reference's
-own loop, lib/matrix.c:47-57, timed on this host on a bounded slice of the same product).
+gfx950 fp32 MFMA peak, timed with HIP events on the launch stream) and, with --full, `cpu_baseline` (the
+reference's own loop, lib/matrix.c:47-57, timed on this host on a bounded slice of the same product).
 """
 import argparse
 import ctypes as C
@@ -515,18 +519,36 @@ def cpu_baseline_conv(arrays, target_seconds=6.0):
             "sample": f"{n} images, conv() + conv_ddx() each ({what}), gcc -O2, {dt:.1f} s"}, err
 
 
+DUMP_MAX_ELEMS = 8 << 20     # 32 MiB of float32 per dumped array
+
+
+def dump_outputs(out_dir, c, stream):
+    """What a caller of the timed path receives: C = A @ B of the last timed step (every step computes the same product of the
+    same seeded operands).  A product above DUMP_MAX_ELEMS elements is written as a fixed sample of whole rows: the rows
+    np.random.default_rng(0) draws without replacement, ascending -- the same rows in every run of the same --size."""
+    os.makedirs(out_dir, exist_ok=True)
+    full = c.numpy(stream)
+    n_rows, n_cols = full.shape
+    if full.size > DUMP_MAX_ELEMS:
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, size=DUMP_MAX_ELEMS // n_cols, replace=False))
+        full = full[rows]
+    np.save(os.path.join(out_dir, "gemm_c.npy"), np.ascontiguousarray(full, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=50)   # ~50 ms of launches: with 10 the clocks are still ramping inside the timed region (140 vs 143 TFLOP/s)
     ap.add_argument("--size", type=int, default=4096, help="square GEMM size (BASELINE configs[1]: 1024..8192)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the secondary and tertiary workloads and the CPU baselines (off: the primary workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed primary path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--preroll", type=float, default=0.15, help="seconds of untimed launches of the same product before the warm-up steps (clock ramp; 0 = off)")
-    ap.add_argument("--mnist-steps", type=int, default=300, help="timed steps of the secondary MNIST-NN workload (0 = skip)")
+    ap.add_argument("--mnist-steps", type=int, default=300, help="with --full: timed steps of the secondary MNIST-NN workload (0 = skip)")
     ap.add_argument("--mnist-warmup", type=int, default=30)
-    ap.add_argument("--unet-steps", type=int, default=5, help="timed forward+backward passes of the batch-64 U-Net under the tertiary workload (0 = skip; N = 1 only)")
-    ap.add_argument("--conv-steps", type=int, default=20, help="timed forward+backward passes of the tertiary batched-convolution workload (0 = skip; N = 1 only)")
+    ap.add_argument("--unet-steps", type=int, default=5, help="with --full: timed forward+backward passes of the batch-64 U-Net under the tertiary workload (0 = skip; N = 1 only)")
+    ap.add_argument("--conv-steps", type=int, default=20, help="with --full: timed forward+backward passes of the tertiary batched-convolution workload (0 = skip; N = 1 only)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -636,9 +658,11 @@ def main():
                 break
         except (OSError, KeyError, ValueError):
             continue
-    # the GPU workloads are timed back to back; the CPU baselines (tens of seconds of host work) come after them
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dc, stream)
+    # --full only: the GPU workloads are timed back to back; the CPU baselines (tens of seconds of host work) come after them
     sec, fault, ter, conv_arrays = None, None, None, None
-    if args.mnist_steps > 0:
+    if args.full and args.mnist_steps > 0:
         try:
             sec, fault = run_mnist(bla, dist, world, rank, stream, args.mnist_steps, args.mnist_warmup, barrier)
         except Exception as e:       # the headline measurement above must still be reported
@@ -646,7 +670,7 @@ def main():
             traceback.print_exc()
             fault = {"stage": "secondary workload", "error": repr(e)}
             sec = {"metric": "MNIST-NN training samples/sec", "value": None, "unit": "samples/s", "n_gpus": world, "error": repr(e)} if rank == 0 else None
-    if world == 1 and args.conv_steps > 0:
+    if args.full and world == 1 and args.conv_steps > 0:
         try:
             ter, conv_arrays = run_conv(bla, stream, barrier, steps=args.conv_steps)
         except Exception as e:
@@ -660,7 +684,7 @@ def main():
                 import traceback
                 traceback.print_exc()
                 ter["unet_batch_64"] = {"value": None, "error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base, c_cpu, rows = cpu_baseline_gemm(n)
         out["cpu_baseline"] = base
         # the same slice doubles as a correctness check of what was just timed

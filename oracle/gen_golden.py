@@ -632,6 +632,81 @@ def gen_print():
     np.savez_compressed(os.path.join(GOLD, "print_matrix.npz"), **d)
 
 
+# ---- tests/test_oracle_vs_ref.py: the reference's results on that test's own inputs (the test recomputes them where the reference build exists)
+def gen_oracle_vs_ref():
+    d = {}
+    for seed in range(12):
+        rng = np.random.default_rng(seed)
+        m, k, n = [int(v) for v in rng.integers(1, 90, 3)]
+        a = uniform(seed * 3 + 1, (m, k), -3, 3); b = uniform(seed * 3 + 2, (k, n), -3, 3)
+        d[f"matmul_s{seed}"] = ref.matmul(a, b)
+        d[f"matmul_inplace_s{seed}"] = ref.matmul_inplace(a, b)
+    for r, c in [(1, 1), (5, 9), (9, 5), (31, 64), (64, 64)]:
+        a = uniform(11, (r, c), -2, 2); b = uniform(12, (r, c), -2, 2)
+        t = f"ew_{r}x{c}_"
+        d[t + "scale"] = ref.inplace1("matrix_scale", a, C.c_double(1 / 3))
+        d[t + "add"] = ref.inplace2("matrix_add", a, b)
+        d[t + "hadamard"] = ref.inplace2("matrix_multiply_elementwise", a, b)
+        d[t + "transpose"] = ref.inplace1("matrix_transpose", a)
+        d[t + "row_sum"] = ref.take(L.matrix_row_sum(ref.mat(a)))
+        if r <= c:  # defined behaviour only (Q2)
+            d[t + "col_sum"] = ref.take(L.matrix_col_sum(ref.mat(a)))
+        d[t + "frobenius"] = np.array(L.frobenius_norm(ref.mat(a)))
+        d[t + "max"] = np.array(L.max_value(ref.mat(a)))
+        d[t + "zscore"] = ref.inplace1("matrix_z_score_normalize", a)
+        d[t + "relu"] = ref.data_fn("relu", a, a.size)
+        d[t + "softmax_cols"] = ref.data_fn("softmax", a, r, c)
+        d[t + "softmax_rows"] = ref.data_fn("softmax_row_wise", a, r, c)
+    for h, w, cin, cout, k, s in [(4, 4, 1, 1, 3, 1), (9, 6, 2, 3, 3, 2), (10, 10, 3, 2, 1, 2), (5, 5, 2, 2, 3, 3)]:
+        x = uniform(21, (cin, h, w))
+        ho, wo = int(np.ceil(np.float32(h) / s)), int(np.ceil(np.float32(w) / s))      # lib/conv.c:55-56
+        im = np.zeros((ho * wo, k * k * cin)); imm = ref.mat(im)
+        L._im2col(ref.mats(x), C.byref(imm), k, cin, s)
+        d["im2col_" + "_".join(map(str, (h, w, cin, cout, k, s)))] = im
+    np.savez_compressed(os.path.join(GOLD, "oracle_vs_ref.npz"), **d)
+
+
+# ---- tests/test_host_io.py: its cases (procedures on a library of the I/O units) run on the reference's own csv / mnist_csv2 / cifar10 / bmp
+# / mnist_csv units, compiled by the test's own recipe
+def gen_host_io():
+    import pathlib
+    import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import test_host_io as t
+    d = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        tmp = pathlib.Path(tmp)
+        io = t.reference_io_lib(tmp)
+        legacy = t._legacy_reader(os.path.join(REFROOT, "lib", "mnist_csv.c"), tmp)
+        for name, res in (("csv", t.csv_case(io, tmp)), ("mnist", t.mnist_case(io, tmp)), ("bmp_cifar", t.bmp_cifar_case(io, tmp)),
+                          ("legacy", t.legacy_case(legacy, tmp))):
+            for k, v in res.items():
+                d[f"{name}:{k}"] = v
+    np.savez_compressed(os.path.join(GOLD, "host_io.npz"), **d)
+
+
+# ---- tests/test_c_trainer.py / test_c_unet.py: what the reference's own programs write (`init`, as sha256 per file) and draw, by the tests' recipes
+def gen_c_programs():
+    import pathlib
+    import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import test_c_trainer
+    import test_c_unet
+    d = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        tmp = pathlib.Path(tmp)
+        (tmp / "mnist").mkdir(); (tmp / "unet").mkdir()
+        for f, dig in test_c_trainer.reference_init_digests(tmp / "mnist").items():
+            d["mnist_init:" + f] = dig
+        d["unet_init:paths"], d["unet_init:sha256"] = test_c_unet.reference_init_tree(tmp / "unet")
+        batch = tmp / "data_batch_1.bin"                     # test_c_unet.batch_file
+        np.random.default_rng(11).integers(0, 256, (10000, 3073), dtype=np.uint8).tofile(batch)
+        dr = test_c_unet.reference_draws(str(batch), tmp)
+        d["unet_draws:x"], d["unet_draws:noise"], d["unet_draws:next_rand"] = dr["x"], dr["noise"], dr["next_rand"]
+        d["unet_draws:drop_bits"], d["unet_draws:drop_len"] = np.packbits(dr["drop"]), np.array(dr["drop"].size)
+    np.savez_compressed(os.path.join(GOLD, "c_programs.npz"), **d)
+
+
 def sum_seq(v):
     """left-to-right fp64 sum, the order of the loop at model/cifar_unet.c:1191-1196"""
     s_ = 0.0
@@ -645,7 +720,8 @@ if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     only = sys.argv[1:]          # e.g. `gen_golden.py layer print` regenerates just those files
     gens = {"gemm": gen_gemm, "matrix_ops": gen_matrix_ops, "conv": gen_conv, "norm": gen_norm, "mnist": gen_mnist, "unet_glue": gen_unet_glue,
-            "attention": gen_attention, "resnet": gen_resnet, "layer": gen_layer, "print": gen_print}
+            "attention": gen_attention, "resnet": gen_resnet, "layer": gen_layer, "print": gen_print,
+            "oracle_vs_ref": gen_oracle_vs_ref, "host_io": gen_host_io, "c_programs": gen_c_programs}
     for name, fn in gens.items():
         if not only or name in only:
             fn()

@@ -1,10 +1,11 @@
 """bench.py's one-line JSON contract: the keys the driver reads, BASELINE.json's metric, the `roofline` and `cpu_baseline` objects.
-CPU: the committed line of the last measurement pass (profiles/r03_bench_default_output.json).  GPU: a short live run."""
+CPU: the committed line of the last measurement pass (profiles/r03_bench_default_output.json).  GPU: a short live run with --full, and a plain one with --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -14,7 +15,7 @@ ROOF = ["bound", "achieved", "peak", "unit", "frac", "traffic"]
 CPU = ["value", "unit", "cores", "kind", "sample"]
 
 
-def check_line(d, with_cpu_baseline):
+def check_headline(d):
     for k in TOP:
         assert k in d, k
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
@@ -26,6 +27,10 @@ def check_line(d, with_cpu_baseline):
     r = d["roofline"]
     assert r["bound"] == "mfma" and r["unit"] == "TFLOP/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3 and 0 < r["frac"] < 1
     assert abs(d["value"] - d["n_gpus"] * 2 * 4096 ** 3 / (d["ms_per_step"] * 1e-3) / 1e9) <= 2e-3 * d["value"]     # whole-job GFLOP/s over the timed region
+
+
+def check_line(d, with_cpu_baseline):
+    check_headline(d)
     sec, ter = d["secondary"], d["tertiary"]
     assert sec["unit"] == "samples/s" and sec["value"] > 0 and "roofline" in sec
     assert ter["unit"] == "images/s" and ter["value"] > 0 and 0 < ter["roofline"]["frac"] < 1
@@ -62,7 +67,7 @@ def test_committed_rehearsals_of_the_multi_rank_path():
 
 @pytest.mark.gpu
 def test_live_bench_line_keeps_the_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--mnist-steps", "20", "--mnist-warmup", "5", "--conv-steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "2", "--mnist-steps", "20", "--mnist-warmup", "5", "--conv-steps", "2",
                         "--unet-steps", "1", "--no-cpu-baseline"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -70,3 +75,29 @@ def test_live_bench_line_keeps_the_contract():
     d = json.loads(lines[0])
     assert d["steps"] == 3 and d["warmup"] == 2 and d["n_gpus"] == 1
     check_line(d, False)
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_its_output(tmp_path):
+    """Without --full the run times the headline GEMM only (no secondary / tertiary workload, no CPU baseline); --dump-outputs writes the
+    product of its last timed step as a fixed sample of rows (bench.dump_outputs), which must be C = A @ B of the seeded operands."""
+    from inputs import uniform
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["n_gpus"] == 1
+    check_headline(d)
+    assert "secondary" not in d and "tertiary" not in d and "cpu_baseline" not in d
+    assert sorted(os.listdir(tmp_path)) == ["gemm_c.npy"]
+    c = np.load(tmp_path / "gemm_c.npy")
+    n = 4096
+    assert c.dtype == np.float32 and c.shape == (2048, n) and c.nbytes <= 64 << 20
+    rows = np.sort(np.random.default_rng(0).choice(n, size=2048, replace=False))
+    pick = np.arange(0, 2048, 32)                                   # 64 of the dumped rows against fp64
+    a = uniform(0xB1A5, (n, n))[rows[pick]]; b = uniform(0xB1A6, (n, n))
+    want = a @ b
+    err = np.linalg.norm(c[pick] - want) / np.linalg.norm(want)
+    assert err < 1e-5, err

@@ -4,6 +4,7 @@ same example order as lib/mnist_csv2.c's walk.  GPU part: a training run and a p
 the oracle restatement of the same loop (same sampler order, fp64), including the epoch's loss / accuracy line; and the same run with two
 replicas in one process (BLA_GPUS=2) against the single replica."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 import sys
@@ -64,20 +65,37 @@ def test_usage_messages_match_the_reference_shape(prog, tmp_path):
     assert r.returncode == 1 and r.stdout.startswith("Unrecognized argument, options:")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources only exist in the build container")
-def test_init_writes_the_reference_files(prog, tmp_path):
-    """model/mnist_nn.c:97-142 compiled as is (with the reference's own lib units) against ours: same rand() draws, same float
-    expressions, same CSV bytes in all six files."""
-    ref_exe = str(tmp_path / "ref_mnist_nn")
+def init_digests(d):
+    """sha256 of each of the six files `init` wrote under d/data/mnist_nn/."""
+    return {f: np.frombuffer(hashlib.sha256(open(os.path.join(d, "data", "mnist_nn", f"{f}.csv"), "rb").read()).digest(), np.uint8) for f in FILES}
+
+
+def reference_init_digests(tmp):
+    """model/mnist_nn.c:97-142 compiled as is (with the reference's own lib units), run as `init` in a scratch directory."""
+    ref_exe = str(tmp / "ref_mnist_nn")
     subprocess.check_call(["gcc", "-std=c99", "-O1", "-w", "-o", ref_exe, f"{REF}/model/mnist_nn.c", f"{REF}/lib/matrix.c", f"{REF}/lib/csv.c",
                            f"{REF}/lib/mnist_csv2.c", "-lm"])
-    a, b = tmp_path / "theirs", tmp_path / "ours"
-    for d in (a, b):
-        (d / "data" / "mnist_nn").mkdir(parents=True)
+    a = tmp / "theirs"
+    (a / "data" / "mnist_nn").mkdir(parents=True)
     subprocess.check_call([ref_exe, "init"], cwd=str(a))
+    return init_digests(a)
+
+
+def test_init_writes_the_reference_files(prog, tmp_path):
+    """`init` against the reference's own init(): same rand() draws, same float expressions, same CSV bytes in all six files -- the
+    sha256 of each file the reference wrote is recorded in tests/golden/c_programs.npz (oracle/gen_golden.py); where the reference's
+    sources exist, its program is also compiled and run here and must still write exactly those files."""
+    rec = golden("c_programs")
+    b = tmp_path / "ours"
+    (b / "data" / "mnist_nn").mkdir(parents=True)
     run(prog, ["init"], str(b))
+    ours = init_digests(b)
     for f in FILES:
-        assert open(a / "data" / "mnist_nn" / f"{f}.csv", "rb").read() == open(b / "data" / "mnist_nn" / f"{f}.csv", "rb").read(), f
+        assert np.array_equal(ours[f], rec["mnist_init:" + f]), f
+    if os.path.isdir(REF):
+        theirs = reference_init_digests(tmp_path)
+        for f in FILES:
+            assert np.array_equal(theirs[f], rec["mnist_init:" + f]), f"{f}: tests/golden/c_programs.npz differs from the reference's init"
 
 
 def test_fast_sampler_equals_the_library_walk(prog, tmp_path):

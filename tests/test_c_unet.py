@@ -1,8 +1,9 @@
 """examples/cifar_unet_gpu.c -- the reference's CIFAR U-Net program (model/cifar_unet.c: init / train / run) as a C host program over the
-batched device model.  CPU part (needs the reference built as oracle/_ref/libref_unet.so, so container only): `init` writes byte for byte
-the 122 files the reference's own init() writes; the example, noise and dropout draws of `train` are the ones the reference's own functions
-(init_parameters, load_example, random_gaussian, _dropout) make when called in train()'s / forward()'s order after srand(42).  GPU part: one
+batched device model.  CPU part (against what the reference built as oracle/_ref/libref_unet.so produced, recorded in tests/golden/c_programs.npz):
+`init` writes byte for byte the 122 files the reference's own init() writes; the example, noise and dropout draws of `train` are the ones the
+reference's own functions (init_parameters, load_example, random_gaussian, _dropout) make when called in train()'s / forward()'s order after srand(42).  GPU part: one
 training pass of two images against the oracle composition on exactly the values the program uploaded; `run` from the as-written file set."""
+import hashlib
 import os
 import subprocess
 import sys
@@ -10,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, golden
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from unet_refconst import CFG, tensor_list  # noqa: E402
@@ -19,7 +20,10 @@ EX = os.path.join(ROOT, "examples")
 BIN = os.path.join(EX, "cifar_unet_gpu")
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_unet.so")
 IMAGE = 3 * 32 * 32
-needs_ref = pytest.mark.skipif(not (os.path.isdir("/root/reference") and os.path.exists(REF_SO)), reason="the reference build only exists in the build container")
+
+
+def needs_ref_build():
+    return os.path.isdir("/root/reference") and os.path.exists(REF_SO)
 
 
 @pytest.fixture(scope="module")
@@ -65,21 +69,37 @@ U.cifar_unet_main(2, (C.c_char_p * 3)(b"cifar_unet", b"init", None))
 """
 
 
-@needs_ref
-def test_init_writes_the_reference_files(prog, tmp_path):
-    """model/cifar_unet.c's own main("init") (compiled from the reference's sources, oracle/Makefile) against ours: the same directories, the same
-    122 files, the same bytes -- He / Xavier draws in init_parameters' order (:1804-1844) and save_parameters' as-written channel counts."""
-    a, b = tmp_path / "theirs", tmp_path / "ours"
-    for d in (a, b):
-        (d / "data").mkdir(parents=True)
+def init_tree(d):
+    """Every directory and file `init` made under d (sorted relative paths) and the sha256 of each file (zeros for a directory)."""
+    paths = sorted(os.path.relpath(os.path.join(r, f), d) for r, ds, fs in os.walk(d) for f in fs + ds)
+    digs = [hashlib.sha256(open(os.path.join(d, p), "rb").read()).digest() if os.path.isfile(os.path.join(d, p)) else bytes(32) for p in paths]
+    return np.array(paths), np.frombuffer(b"".join(digs), np.uint8).reshape(len(paths), 32)
+
+
+def reference_init_tree(tmp):
+    """model/cifar_unet.c's own main("init") (oracle/_ref/libref_unet.so, compiled from the reference's sources by oracle/Makefile)."""
+    a = tmp / "theirs"
+    (a / "data").mkdir(parents=True)
     subprocess.check_call([sys.executable, "-c", REF_INIT % REF_SO], cwd=str(a))
+    return init_tree(a)
+
+
+def test_init_writes_the_reference_files(prog, tmp_path):
+    """`init` against the reference's own main("init"): the same directories, the same 122 files, the same bytes -- He / Xavier draws in
+    init_parameters' order (:1804-1844) and save_parameters' as-written channel counts.  What the reference wrote (paths, sha256 of every
+    file) is recorded in tests/golden/c_programs.npz (oracle/gen_golden.py); where the reference build exists it is run here as well and
+    must still write exactly that."""
+    rec = golden("c_programs")
+    b = tmp_path / "ours"
+    (b / "data").mkdir(parents=True)
     run(prog, ["init"], b)
-    theirs = sorted(os.path.relpath(os.path.join(r, f), a) for r, ds, fs in os.walk(a) for f in fs + ds)
-    ours = sorted(os.path.relpath(os.path.join(r, f), b) for r, ds, fs in os.walk(b) for f in fs + ds)
-    assert ours == theirs and sum(1 for p in ours if p.endswith(".csv")) == 122
-    for p in ours:
-        if p.endswith(".csv"):
-            assert open(a / p, "rb").read() == open(b / p, "rb").read(), p
+    paths, digs = init_tree(b)
+    assert list(paths) == list(rec["unet_init:paths"]) and sum(1 for p in paths if p.endswith(".csv")) == 122
+    for p, got, want in zip(paths, digs, rec["unet_init:sha256"]):
+        assert np.array_equal(got, want), p
+    if needs_ref_build():
+        tp, td = reference_init_tree(tmp_path)
+        assert list(tp) == list(rec["unet_init:paths"]) and np.array_equal(td, rec["unet_init:sha256"]), "tests/golden/c_programs.npz differs from the reference's init"
 
 
 REF_DRAWS = """
@@ -107,15 +127,34 @@ np.savez(%(out)r, x=np.stack(xs), noise=np.stack(noises), drop=np.concatenate([n
 """
 
 
-@needs_ref
+DRAW_BLOCKS = [(c, s) for c, s in zip([128, 128] + [256] * 14 + [128, 128], [32, 32, 16, 16, 8, 8, 4, 4, 4, 4, 4, 4, 8, 8, 16, 16, 32, 32])]
+
+
+def reference_draws(batch_file, tmp):
+    """REF_DRAWS on two images of batch_file: x, noise, drop (one uint8 per dropout decision), next_rand."""
+    out = str(tmp / "ref.npz")
+    subprocess.check_call([sys.executable, "-c", REF_DRAWS % dict(oracle=os.path.join(ROOT, "oracle"), so=REF_SO, batch=batch_file, images=2, blocks=DRAW_BLOCKS, out=out)])
+    z = np.load(out)
+    return {k: z[k] for k in z.files}
+
+
+def recorded_draws():
+    rec = golden("c_programs")
+    return {"x": rec["unet_draws:x"], "noise": rec["unet_draws:noise"], "next_rand": rec["unet_draws:next_rand"],
+            "drop": np.unpackbits(rec["unet_draws:drop_bits"])[:int(rec["unet_draws:drop_len"])]}
+
+
 def test_draws_are_the_reference_functions_draws(prog, batch_file, tmp_path):
     """What `train 1 2` hands the device against the reference's own functions called in the reference's order (in a fresh process: random_gaussian
     keeps a static spare value): pixels -> [-1, 1], the Gaussian noise of rand_r(&seed), every dropout decision, and the NEXT rand() value --
-    so the number of draws agrees as well as their order."""
-    blocks = [(c, s) for c, s in zip([128, 128] + [256] * 14 + [128, 128], [32, 32, 16, 16, 8, 8, 4, 4, 4, 4, 4, 4, 8, 8, 16, 16, 32, 32])]
-    out = str(tmp_path / "ref.npz")
-    subprocess.check_call([sys.executable, "-c", REF_DRAWS % dict(oracle=os.path.join(ROOT, "oracle"), so=REF_SO, batch=batch_file, images=2, blocks=blocks, out=out)])
-    want = np.load(out)
+    so the number of draws agrees as well as their order.  The reference's draws on this batch file are recorded in tests/golden/c_programs.npz
+    (oracle/gen_golden.py); where the reference build exists they are drawn again here and must still be those."""
+    blocks = DRAW_BLOCKS
+    want = recorded_draws()
+    if needs_ref_build():
+        live = reference_draws(batch_file, tmp_path)
+        for k in want:
+            assert np.array_equal(live[k], want[k]), f"{k}: tests/golden/c_programs.npz differs from the reference's draws"
     d = tmp_path / "ours"; d.mkdir()
     r = run(prog, ["draws", "2", str(d)], tmp_path, env=dict(BLA_CIFAR_BATCH=batch_file))
     words = r.stdout.split()

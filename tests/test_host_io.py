@@ -1,6 +1,7 @@
 """Host-side I/O units of the drop-in layer (csv, mnist_csv2, cifar10, bmp): same bytes / same values / same rand()
-consumption as the reference's units, compared directly against the reference compiled into a scratch .so (only where
-/root/reference exists), plus fixture-free known answers (data/a.csv values)."""
+consumption as the reference's units, plus fixture-free known answers (data/a.csv values).  Each case is one
+procedure run on a library of these units; what the reference's own units produced in it is recorded in tests/golden/host_io.npz
+(oracle/gen_golden.py), and where the reference's sources exist the case also runs on them, compiled into a scratch .so."""
 import ctypes as C
 import os
 import subprocess
@@ -8,29 +9,41 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, golden
 
 LIB = os.path.join(ROOT, "big-linear-algebra_amd", "lib")
 REF = "/root/reference"
 libc = C.CDLL(None)
 
 
-@pytest.fixture(scope="module")
-def ours(pkg):
-    pkg.build_native()
-    L = C.CDLL(os.path.join(LIB, "libbla_host.so"))
+def reference_io_lib(tmp):
+    """The reference's csv / mnist_csv2 / cifar10 / bmp units compiled as they are into a scratch .so (where its sources exist)."""
+    so = str(tmp / "librefio.so")
+    subprocess.check_call(["gcc", "-std=c99", "-O1", "-w", "-fPIC", "-shared", "-o", so] +
+                          [os.path.join(REF, "lib", f) for f in ("csv.c", "mnist_csv2.c", "cifar10.c", "bmp.c")] + ["-lm"])
+    L = C.CDLL(so)
     L.read_csv_contents.restype = C.POINTER(C.c_float)
     return L
 
 
+def check_case(name, mine, theirs_fn):
+    """`mine` (a dict of arrays from one case on our units) against the reference's recorded result of the same case, and against
+    the reference's units themselves where their sources exist (theirs_fn builds them and runs the case)."""
+    rec = golden("host_io")
+    want = {k[len(name) + 1:]: rec[k] for k in rec.z.files if k.startswith(name + ":")}
+    assert sorted(mine) == sorted(want), (name, sorted(mine), sorted(want))
+    for k in want:
+        assert np.array_equal(mine[k], want[k]), f"{name}:{k} differs from the reference's recorded result"
+    if os.path.isdir(REF):
+        theirs = theirs_fn()
+        for k in want:
+            assert np.array_equal(theirs[k], want[k]), f"{name}:{k}: tests/golden/host_io.npz differs from the reference's units"
+
+
 @pytest.fixture(scope="module")
-def theirs(tmp_path_factory):
-    if not os.path.isdir(REF):
-        pytest.skip("reference sources only exist in the build container")
-    so = str(tmp_path_factory.mktemp("refio") / "librefio.so")
-    subprocess.check_call(["gcc", "-std=c99", "-O1", "-w", "-fPIC", "-shared", "-o", so] +
-                          [os.path.join(REF, "lib", f) for f in ("csv.c", "mnist_csv2.c", "cifar10.c", "bmp.c")] + ["-lm"])
-    L = C.CDLL(so)
+def ours(pkg):
+    pkg.build_native()
+    L = C.CDLL(os.path.join(LIB, "libbla_host.so"))
     L.read_csv_contents.restype = C.POINTER(C.c_float)
     return L
 
@@ -50,16 +63,17 @@ def test_csv_roundtrip_and_known_answer(ours, tmp_path):
     assert ours.count_num_lines(fh) == 2
 
 
-def test_csv_matches_reference(ours, theirs, tmp_path):
+def csv_case(L, tmp):
     rng = np.random.default_rng(0)
     d = (rng.normal(size=37 * 5) * 100).astype(np.float32)
-    a, b = str(tmp_path / "o.csv"), str(tmp_path / "t.csv")
-    ours.write_csv_contents(a.encode(), d.ctypes.data_as(C.POINTER(C.c_float)), 5, 37)
-    theirs.write_csv_contents(b.encode(), d.ctypes.data_as(C.POINTER(C.c_float)), 5, 37)
-    assert open(a, "rb").read() == open(b, "rb").read()
-    va = np.ctypeslib.as_array(ours.read_csv_contents(a.encode()), shape=(185,)).copy()
-    vb = np.ctypeslib.as_array(theirs.read_csv_contents(a.encode()), shape=(185,)).copy()
-    assert np.array_equal(va, vb)
+    a = str(tmp / "csv_case.csv")
+    L.write_csv_contents(a.encode(), d.ctypes.data_as(C.POINTER(C.c_float)), 5, 37)
+    return {"bytes": np.frombuffer(open(a, "rb").read(), np.uint8),
+            "read": np.ctypeslib.as_array(L.read_csv_contents(a.encode()), shape=(185,)).copy()}
+
+
+def test_csv_matches_reference(ours, tmp_path):
+    check_case("csv", csv_case(ours, tmp_path), lambda: csv_case(reference_io_lib(tmp_path), tmp_path))
 
 
 class MnistCSV(C.Structure):
@@ -71,31 +85,32 @@ class MnistExample(C.Structure):
     _fields_ = [("X", C.POINTER(C.c_float)), ("y", C.c_float), ("num_examples", C.c_int)]
 
 
-def test_mnist_store_and_samplers_match_reference(ours, theirs, tmp_path):
+def mnist_case(L, tmp):
     rng = np.random.default_rng(1)
     n = 23
     rows = np.concatenate([rng.integers(0, 10, (n, 1)), rng.integers(0, 256, (n, 784))], 1)
-    p = str(tmp_path / "mnist.csv")
+    p = str(tmp / "mnist.csv")
     open(p, "w").write("".join(",".join(str(v) for v in r) + ",\n" for r in rows))
     fopen = libc.fopen; fopen.restype = C.c_void_p
-    out = []
-    for L in (ours, theirs):
-        L.get_random_data_take.restype = MnistExample; L.get_random_data_take.argtypes = [C.POINTER(MnistCSV)]
-        L.get_random_data_replace.restype = MnistExample; L.get_random_data_replace.argtypes = [C.POINTER(MnistCSV)]
-        m = MnistCSV(fopen(p.encode(), b"r"), None, None, 0, 0, None)
-        L.mnist_csv_init(C.byref(m))
-        X = np.ctypeslib.as_array(m.X, shape=(784, n)).copy(); y = np.ctypeslib.as_array(m.y, shape=(n,)).copy()
-        libc.srand(42)                                     # model/mnist_nn.c:513
-        base = C.cast(m.X, C.c_void_p).value
-        picks = []
-        for _ in range(2 * n + 3):                         # runs past exhaustion: the sampler restarts (lib/mnist_csv2.c:43-46)
-            ex = L.get_random_data_take(C.byref(m)); picks.append(((C.cast(ex.X, C.c_void_p).value - base) // 4, ex.y))
-        for _ in range(5):
-            ex = L.get_random_data_replace(C.byref(m)); picks.append(((C.cast(ex.X, C.c_void_p).value - base) // 4, ex.y))
-        out.append((X, y, picks))
-    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
-    assert np.array_equal(out[0][0], rows[:, 1:].T.astype(np.float32))     # feature-major store
-    assert out[0][2] == out[1][2]
+    L.get_random_data_take.restype = MnistExample; L.get_random_data_take.argtypes = [C.POINTER(MnistCSV)]
+    L.get_random_data_replace.restype = MnistExample; L.get_random_data_replace.argtypes = [C.POINTER(MnistCSV)]
+    m = MnistCSV(fopen(p.encode(), b"r"), None, None, 0, 0, None)
+    L.mnist_csv_init(C.byref(m))
+    X = np.ctypeslib.as_array(m.X, shape=(784, n)).copy(); y = np.ctypeslib.as_array(m.y, shape=(n,)).copy()
+    libc.srand(42)                                     # model/mnist_nn.c:513
+    base = C.cast(m.X, C.c_void_p).value
+    picks = []
+    for _ in range(2 * n + 3):                         # runs past exhaustion: the sampler restarts (lib/mnist_csv2.c:43-46)
+        ex = L.get_random_data_take(C.byref(m)); picks.append(((C.cast(ex.X, C.c_void_p).value - base) // 4, ex.y))
+    for _ in range(5):
+        ex = L.get_random_data_replace(C.byref(m)); picks.append(((C.cast(ex.X, C.c_void_p).value - base) // 4, ex.y))
+    return {"X": X, "y": y, "picks": np.array(picks, np.float64), "rows": rows}
+
+
+def test_mnist_store_and_samplers_match_reference(ours, tmp_path):
+    mine = mnist_case(ours, tmp_path)
+    assert np.array_equal(mine["X"], mine["rows"][:, 1:].T.astype(np.float32))     # feature-major store
+    check_case("mnist", mine, lambda: mnist_case(reference_io_lib(tmp_path), tmp_path))
     # NB the reference's "without replacement" walk stops AT the n-th unsampled slot's successor without checking that
     # slot (lib/mnist_csv2.c:53-58), so repeats are possible; reproduced as is (the picks above are identical).
 
@@ -105,29 +120,34 @@ class BMPData(C.Structure):
                 ("blue", C.POINTER(C.c_uint8))]
 
 
-def test_bmp_and_cifar_match_reference(ours, theirs, tmp_path):
+def bmp_cifar_case(L, tmp):
     rng = np.random.default_rng(2)
-    batch = str(tmp_path / "data_batch_1.bin")
+    batch = str(tmp / "data_batch_1.bin")
     rng.integers(0, 256, 3073 * 10000, dtype=np.uint8).tofile(batch)       # a full-size batch file (30,730,000 bytes)
-    imgs = []
-    for L in (ours, theirs):
-        fd = os.open(batch, os.O_RDONLY)
-        libc.srand(7)
-        arr = np.zeros(3072, np.uint8)
-        for _ in range(3):
-            L.fill_random_data(fd, arr.ctypes.data_as(C.POINTER(C.c_uint8)))
-        os.close(fd)
-        imgs.append(arr.copy())
-    assert np.array_equal(imgs[0], imgs[1])
+    fd = os.open(batch, os.O_RDONLY)
+    libc.srand(7)
+    arr = np.zeros(3072, np.uint8)
+    for _ in range(3):
+        L.fill_random_data(fd, arr.ctypes.data_as(C.POINTER(C.c_uint8)))
+    os.close(fd)
+    out = {"image": arr.copy()}
     for w, h in [(32, 32), (5, 3)]:
         planes = [rng.integers(0, 256, w * h, dtype=np.uint8) for _ in range(3)]
-        files = []
-        for i, L in enumerate((ours, theirs)):
-            d = BMPData(w, h, *[p.ctypes.data_as(C.POINTER(C.c_uint8)) for p in planes])
-            f = str(tmp_path / f"img{i}_{w}.bmp"); L.write_bmp_data(f.encode(), C.byref(d)); files.append(open(f, "rb").read())
+        d = BMPData(w, h, *[p.ctypes.data_as(C.POINTER(C.c_uint8)) for p in planes])
+        f = str(tmp / f"img_{w}.bmp"); L.write_bmp_data(f.encode(), C.byref(d))
+        b = np.frombuffer(open(f, "rb").read(), np.uint8).copy()
         # byte 47 (info header [33]) is never written by the reference (lib/bmp.c:70-72 assigns [32] twice): stack garbage there
-        assert files[0][:47] == files[1][:47] and files[0][48:] == files[1][48:]
-        assert files[0][:2] == b"BM" and len(files[0]) == 54 + ((24 * w + 31) // 32) * 4 * h
+        b[47] = 0
+        out[f"bmp_{w}x{h}"] = b
+    return out
+
+
+def test_bmp_and_cifar_match_reference(ours, tmp_path):
+    mine = bmp_cifar_case(ours, tmp_path)
+    for w, h in [(32, 32), (5, 3)]:
+        f = mine[f"bmp_{w}x{h}"].tobytes()
+        assert f[:2] == b"BM" and len(f) == 54 + ((24 * w + 31) // 32) * 4 * h
+    check_case("bmp_cifar", mine, lambda: bmp_cifar_case(reference_io_lib(tmp_path), tmp_path))
 
 
 def _legacy_reader(path_c, tmp):
@@ -167,18 +187,21 @@ def _legacy_rows(L, path, rows, tmp, tag):
     return np.array(vals), rcs, open(out_path, "rb").read()
 
 
-def test_legacy_streaming_reader_matches_reference(tmp_path):
-    """lib/mnist_csv.c (get_next_data, visualize_digit_data): same values, same return codes, same stdout as the reference's unit
-    on a synthetic MNIST-shaped file (label + 784 pixels per row, comma-terminated values, newline-terminated rows)."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference sources only exist in the build container")
+def legacy_case(L, tmp):
     rng = np.random.default_rng(3)
     rows = 4
-    path = str(tmp_path / "mnist.csv")
+    path = str(tmp / "mnist.csv")
     with open(path, "w") as f:
         for r in range(rows):
             f.write(",".join(str(int(v)) for v in [rng.integers(10)] + list(rng.integers(0, 256, 784))) + ("\n" if r % 2 else ",\n"))
-    mine = _legacy_rows(_legacy_reader(os.path.join(LIB, "mnist_csv.c"), tmp_path), path, rows, tmp_path, "ours")
-    ref = _legacy_rows(_legacy_reader(os.path.join(REF, "lib", "mnist_csv.c"), tmp_path), path, rows, tmp_path, "theirs")
-    assert np.array_equal(mine[0], ref[0]) and mine[1] == ref[1] == [0] * rows + [1]
-    assert mine[2] == ref[2] and b"CSV file is empty" in mine[2] and mine[2].count(b"\n") >= 31
+    vals, rcs, out = _legacy_rows(L, path, rows, tmp, "legacy")
+    return {"values": vals, "rcs": np.array(rcs, np.int64), "stdout": np.frombuffer(out, np.uint8)}
+
+
+def test_legacy_streaming_reader_matches_reference(tmp_path):
+    """lib/mnist_csv.c (get_next_data, visualize_digit_data): same values, same return codes, same stdout as the reference's unit
+    on a synthetic MNIST-shaped file (label + 784 pixels per row, comma-terminated values, newline-terminated rows)."""
+    mine = legacy_case(_legacy_reader(os.path.join(LIB, "mnist_csv.c"), tmp_path), tmp_path)
+    out = mine["stdout"].tobytes()
+    assert list(mine["rcs"]) == [0] * 4 + [1] and b"CSV file is empty" in out and out.count(b"\n") >= 31
+    check_case("legacy", mine, lambda: legacy_case(_legacy_reader(os.path.join(REF, "lib", "mnist_csv.c"), tmp_path), tmp_path))

@@ -9,11 +9,11 @@
 out=${1:-gpurun_out/r03m}; part=${2:-a}; mkdir -p $out
 export TMPDIR=/tmp
 if [ $part = a ]; then
-  python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+  python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
   for n in 2 4; do      # (the one-GPU box lets at most 6 processes use the card, the launcher counts as one or two: 8 ranks of the same command cannot be rehearsed there)
     BLA_BENCH_SHARE_GPU=1 BLA_BENCH_BACKEND=gloo BLA_BENCH_EXCHANGE=direct BLA_BENCH_STRICT=1 BLA_DP_MAX_BLOCKS=48 GPU_MAX_HW_QUEUES=16 HSA_ENABLE_IPC_MODE_LEGACY=0 \
       timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29517 + n)) \
-      bench.py --gpus $n --steps 10 --warmup 5 --mnist-steps 100 > $out/bench_share$n.json 2> $out/bench_share$n.err; echo "bench share$n rc=$?"
+      bench.py --full --gpus $n --steps 10 --warmup 5 --mnist-steps 100 > $out/bench_share$n.json 2> $out/bench_share$n.err; echo "bench share$n rc=$?"
   done
   python tools/dp_step_floor.py > $out/dp_step_floor.txt 2>&1; echo "dp floor rc=$?"
   python tools/conv_bench.py > $out/conv_bench.txt 2>&1; echo "conv bench rc=$?"
@@ -23,7 +23,7 @@ if [ $part = a ]; then
 elif [ $part = b ]; then
   python tools/gemm_sweep.py --sizes 1024,1536,2048,3072,4096,5120,6144,8192 --configs=-1 --layouts nn,nt --rounds 3 --iters 40 > $out/gemm_sweep.txt 2>&1; echo "sweep rc=$?"
   python tools/ew_bench.py 8192 > $out/ew_bench.txt 2>&1; echo "ew rc=$?"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_prof -- python3 bench.py --no-cpu-baseline > $out/bench_prof.json 2> $out/bench_prof.err; echo "bench prof rc=$?"
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_prof -- python3 bench.py --full --no-cpu-baseline > $out/bench_prof.json 2> $out/bench_prof.err; echo "bench prof rc=$?"
   rm -f $out/bench_prof/*/*_kernel_trace.csv
   for c in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/gemm4096_$c -- python3 bench.py --no-cpu-baseline --mnist-steps 0 --conv-steps 0 --steps 10 --warmup 5 > $out/gemm4096_$c.json 2> $out/gemm4096_$c.err; echo "pmc $c rc=$?"
