@@ -1,0 +1,258 @@
+// bla_diffusion.hip -- what turns the U-Net of model/cifar_unet.c into a DDPM (Ho, Jain, Abbeel 2020): the linear beta schedule, the forward noising
+// of a training batch, the sinusoidal time embedding, the ancestral sampler step and the sampling loop around bla_unet_forward_f32.
+//
+// The reference has the network (time embedding input, noise prediction, MSE against the noise) but never writes the embedding (:535), never noises
+// an image at a timestep and leaves run() empty (:1936).  Random draws come from the Philox streams of bla_philox.h (see include/bla.h), so every
+// value written here can be restated from (seed, offset) alone:
+//   noise  (seed, pass):  t_b = u32(seed, pass << 32)[b] % T,  eps = normal(seed, pass << 32)[0 .. B*F),  x_t = sqrt(abar_t) x0 + sqrt(1 - abar_t) eps
+//   step   (seed, t):     z = normal(seed, (t + 1) << 32)[0 .. B*F) (0 at t = 0);  x <- (x - beta_t / sqrt(1 - abar_t) eps_hat) / sqrt(alpha_t) + sqrt(beta_t) z
+// The schedule is formed in double on the host at create time; the kernels read fp32 tables of the per-step coefficients.  The time embedding is
+// the one examples/cifar_unet_gpu.c computes for BLA_UNET_TIMESTEP, evaluated in double: at t ~ 1000 its arguments reach 1000 rad, where an fp32
+// product t * w_i alone is off by ~6e-5.
+#include "bla_internal.h"
+#include "bla_philox.h"
+#include <cmath>
+#include <vector>
+
+using namespace bla;
+
+struct bla_diffusion {
+	int steps = 0;
+	std::vector<double> beta, alpha_bar;
+	float* table = nullptr;        // device, 5 x steps: sqrt(abar), sqrt(1 - abar), beta / sqrt(1 - abar), 1 / sqrt(alpha), sqrt(beta)
+	float* temb = nullptr;         // the sampler's [B][time_dim] embedding workspace (grows on first use)
+	size_t temb_floats = 0;
+};
+
+namespace {
+
+constexpr int kThreads = 256;
+enum { TAB_SQRT_AB = 0, TAB_SQRT_1MAB = 1, TAB_EPS_COEF = 2, TAB_INV_SQRT_A = 3, TAB_SIGMA = 4 };
+constexpr int kMaxNoiseBatch = 4096;   // the per-image timesteps sit in LDS
+
+// element i of the embedding of t (examples/cifar_unet_gpu.c time_embedding): w_k = exp(-ln(1e4) k / half), relu(sin(t w_k)) at k, relu(cos(t w_k)) at
+// half + k; an odd time_dim leaves its last element 0
+__device__ __forceinline__ float temb_value(int t, int i, int dim) {
+	const int half = dim / 2;
+	if (i >= 2 * half) return 0.f;
+	const int k = i < half ? i : i - half;
+	const double w = exp(-log(10000.0) * k / half), arg = (double)t * w;
+	const double s = i < half ? sin(arg) : cos(arg);
+	return (float)(s > 0 ? s : 0);
+}
+
+unsigned grid_for(size_t work, size_t cap_per_cu = 8) {
+	const size_t cap = cap_per_cu * (size_t)(ctx().num_cus > 0 ? ctx().num_cus : 256);
+	size_t b = (work + kThreads - 1) / kThreads;
+	return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// d_t == NULL: every image at t_const
+__global__ void __launch_bounds__(kThreads) time_embedding_kernel(const int* __restrict__ d_t, int t_const, int batch, int dim, float* __restrict__ out) {
+	const size_t n = (size_t)batch * dim;
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+		out[i] = temb_value(d_t ? d_t[i / dim] : t_const, (int)(i % dim), dim);
+}
+
+__global__ void __launch_bounds__(kThreads) noise_kernel(const float* __restrict__ x0, int batch, size_t F, int dim, unsigned long long seed, unsigned long long offset,
+                                                         int steps, const float* __restrict__ table, int* __restrict__ d_t, float* __restrict__ eps,
+                                                         float* __restrict__ xt, float* __restrict__ temb, int vec) {
+	__shared__ int ts[kMaxNoiseBatch];
+	for (int b = threadIdx.x; b < batch; b += blockDim.x) {
+		ts[b] = (int)(u32_at(seed, offset, (size_t)b) % (uint32_t)steps);
+		if (blockIdx.x == 0) d_t[b] = ts[b];
+	}
+	__syncthreads();
+	const float* sab = table + TAB_SQRT_AB * steps;
+	const float* s1m = table + TAB_SQRT_1MAB * steps;
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	const size_t ne = (size_t)batch * dim;
+	for (size_t i = tid; i < ne; i += stride) temb[i] = temb_value(ts[i / dim], (int)(i % dim), dim);
+	const size_t n = (size_t)batch * F;
+	if (vec) {   // F % 4 == 0, all three 16-byte aligned: Philox block q <-> float4 q, one image per float4
+		for (size_t q = tid; q < n / 4; q += stride) {
+			const int t = ts[(4 * q) / F];
+			const float4 z = philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL));
+			const float4 x = reinterpret_cast<const float4*>(x0)[q];
+			const float a = sab[t], c = s1m[t];
+			reinterpret_cast<float4*>(eps)[q] = z;
+			reinterpret_cast<float4*>(xt)[q] = make_float4(a * x.x + c * z.x, a * x.y + c * z.y, a * x.z + c * z.z, a * x.w + c * z.w);
+		}
+	} else {
+		for (size_t e = tid; e < n; e += stride) {
+			const int t = ts[e / F];
+			const float z = normal_at(seed, offset, e);
+			eps[e] = z;
+			xt[e] = sab[t] * x0[e] + s1m[t] * z;
+		}
+	}
+}
+
+__global__ void __launch_bounds__(kThreads) step_kernel(float* __restrict__ x, const float* __restrict__ eps_hat, size_t n, int t, int steps, unsigned long long seed,
+                                                        const float* __restrict__ table, int batch, int dim, float* __restrict__ temb_next, int vec) {
+	const float k = table[TAB_EPS_COEF * steps + t], inv = table[TAB_INV_SQRT_A * steps + t], sig = table[TAB_SIGMA * steps + t];
+	const unsigned long long offset = (unsigned long long)(t + 1) << 32;
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	if (temb_next && t > 0) {
+		const size_t ne = (size_t)batch * dim;
+		for (size_t i = tid; i < ne; i += stride) temb_next[i] = temb_value(t - 1, (int)(i % dim), dim);
+	}
+	const size_t n4 = vec ? n / 4 : 0;
+	for (size_t q = tid; q < n4; q += stride) {
+		const float4 z = t > 0 ? philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL)) : make_float4(0.f, 0.f, 0.f, 0.f);
+		const float4 e = reinterpret_cast<const float4*>(eps_hat)[q];
+		float4 v = reinterpret_cast<float4*>(x)[q];
+		v.x = (v.x - k * e.x) * inv + sig * z.x; v.y = (v.y - k * e.y) * inv + sig * z.y;
+		v.z = (v.z - k * e.z) * inv + sig * z.z; v.w = (v.w - k * e.w) * inv + sig * z.w;
+		reinterpret_cast<float4*>(x)[q] = v;
+	}
+	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
+		const float z = t > 0 ? normal_at(seed, offset, i) : 0.f;
+		x[i] = (x[i] - k * eps_hat[i]) * inv + sig * z;
+	}
+}
+
+// acc[0] += sum_i (a_i - b_i)^2 in double, one workgroup in a fixed order (deterministic)
+__global__ void __launch_bounds__(1024) sq_diff_sum_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n, double* __restrict__ acc) {
+	__shared__ double part[16];
+	double s = 0;
+	for (size_t i = threadIdx.x; i < n; i += blockDim.x) { const double d = (double)a[i] - (double)b[i]; s += d * d; }
+	for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+	if (threadIdx.x % 64 == 0) part[threadIdx.x / 64] = s;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		double t = 0;
+		for (int w = 0; w < (int)(blockDim.x / 64); w++) t += part[w];
+		acc[0] += t;
+	}
+}
+
+bla_status check_images(const bla_diffusion* d, int batch, size_t image_floats, int time_dim) {
+	BLA_REQUIRE(d, BLA_ERR_INVALID, "null diffusion object");
+	BLA_REQUIRE(batch >= 1 && image_floats >= 1 && time_dim >= 1, BLA_ERR_INVALID, "batch %d, image_floats %zu, time_dim %d", batch, image_floats, time_dim);
+	return BLA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+bla_status bla_diffusion_create(bla_diffusion** out, int steps, float beta_start, float beta_end) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(out, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(steps >= 1 && steps <= (1 << 24), BLA_ERR_INVALID, "steps %d", steps);
+	BLA_REQUIRE(beta_start > 0.f && beta_end > 0.f && beta_start < 1.f && beta_end < 1.f, BLA_ERR_INVALID, "betas (%g, %g) outside (0, 1)", beta_start, beta_end);
+	bla_diffusion* d = new bla_diffusion();
+	d->steps = steps;
+	d->beta.resize(steps); d->alpha_bar.resize(steps);
+	std::vector<float> tab((size_t)5 * steps);
+	double ab = 1.0;
+	for (int t = 0; t < steps; t++) {
+		const double b = steps == 1 ? (double)beta_start : (double)beta_start + ((double)beta_end - beta_start) * t / (steps - 1);   // linspace
+		ab *= 1.0 - b;
+		d->beta[t] = b; d->alpha_bar[t] = ab;
+		tab[TAB_SQRT_AB * steps + t] = (float)std::sqrt(ab);
+		tab[TAB_SQRT_1MAB * steps + t] = (float)std::sqrt(1.0 - ab);
+		tab[TAB_EPS_COEF * steps + t] = (float)(b / std::sqrt(1.0 - ab));
+		tab[TAB_INV_SQRT_A * steps + t] = (float)(1.0 / std::sqrt(1.0 - b));
+		tab[TAB_SIGMA * steps + t] = (float)std::sqrt(b);
+	}
+	hipError_t e = hipMalloc((void**)&d->table, tab.size() * sizeof(float));
+	if (e == hipSuccess) e = hipMemcpy(d->table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
+	if (e != hipSuccess) { (void)hipFree(d->table); delete d; return hip_fail(e, "bla_diffusion_create"); }
+	*out = d;
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_destroy(bla_diffusion* d) {
+	if (!d) return BLA_OK;
+	(void)hipDeviceSynchronize();
+	(void)hipFree(d->table); (void)hipFree(d->temb);
+	delete d;
+	return BLA_OK;
+}
+
+int bla_diffusion_steps(const bla_diffusion* d) { return d ? d->steps : 0; }
+
+bla_status bla_diffusion_schedule(const bla_diffusion* d, int t, double* beta, double* alpha_bar) {
+	BLA_REQUIRE(d && t >= 0 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", t, d ? d->steps : 0);
+	if (beta) *beta = d->beta[t];
+	if (alpha_bar) *alpha_bar = d->alpha_bar[t];
+	return BLA_OK;
+}
+
+bla_status bla_time_embedding_f32(void* stream, const int* d_t, int batch, int time_dim, float* d_temb) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(d_t && d_temb, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(batch >= 1 && time_dim >= 1, BLA_ERR_INVALID, "batch %d, time_dim %d", batch, time_dim);
+	hipLaunchKernelGGL(time_embedding_kernel, dim3(grid_for((size_t)batch * time_dim)), dim3(kThreads), 0, pick_stream(stream), d_t, 0, batch, time_dim, d_temb);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_noise_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, int time_dim, unsigned long long seed,
+                                   unsigned long long pass, int* d_t, float* d_eps, float* d_xt, float* d_temb) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(d_x0 && d_t && d_eps && d_xt && d_temb, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(batch <= kMaxNoiseBatch, BLA_ERR_INVALID, "batch %d > %d", batch, kMaxNoiseBatch);
+	BLA_REQUIRE(pass < (1ull << 32), BLA_ERR_INVALID, "pass %llu does not fit the stream offset pass << 32", pass);
+	const int vec = image_floats % 4 == 0 && ((uintptr_t)d_x0 | (uintptr_t)d_eps | (uintptr_t)d_xt) % 16 == 0;
+	const size_t n = (size_t)batch * image_floats;
+	hipLaunchKernelGGL(noise_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x0, batch, image_floats, time_dim, seed, pass << 32,
+	                   d->steps, d->table, d_t, d_eps, d_xt, d_temb, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, int batch, size_t image_floats, int t,
+                                  unsigned long long seed, int time_dim, float* d_temb_next) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(d_x && d_eps_hat, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(t >= 0 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", t, d->steps);
+	const size_t n = (size_t)batch * image_floats;
+	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_hat) % 16 == 0;
+	hipLaunchKernelGGL(step_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_eps_hat, n, t, d->steps, seed, d->table, batch,
+	                   time_dim, d_temb_next, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_unet_sample_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, unsigned long long seed) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d && d_x, BLA_ERR_INVALID, "null argument");
+	const bla_unet_config& c = *unet_config(m);
+	const int B = bla_unet_batch(m), T = d->steps;
+	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);   // the embedding workspace is scratch, not part of the schedule
+	if (dm->temb_floats < ne) {
+		BLA_HIP(hipStreamSynchronize(pick_stream(stream)));
+		(void)hipFree(dm->temb); dm->temb = nullptr; dm->temb_floats = 0;
+		BLA_HIP(hipMalloc((void**)&dm->temb, ne * sizeof(float)));
+		dm->temb_floats = ne;
+	}
+	hipLaunchKernelGGL(time_embedding_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, pick_stream(stream), (const int*)nullptr, T - 1, B, c.time_dim, dm->temb);
+	BLA_HIP(hipGetLastError());
+	for (int t = T - 1; t >= 0; t--) {
+		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
+		if ((st = bla_diffusion_step_f32(d, stream, d_x, bla_unet_output(m), B, F, t, seed, c.time_dim, dm->temb))) return st;
+	}
+	return BLA_OK;
+}
+
+bla_status bla_mse_accumulate_f32(void* stream, const float* d_a, const float* d_b, size_t n, double* d_acc) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(d_a && d_b && d_acc, BLA_ERR_INVALID, "null argument");
+	hipLaunchKernelGGL(sq_diff_sum_kernel, dim3(1), dim3(1024), 0, pick_stream(stream), d_a, d_b, n, d_acc);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+}  // extern "C"

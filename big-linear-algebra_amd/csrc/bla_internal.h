@@ -135,6 +135,9 @@ bla_status resnet_backward_batched(void* stream, int batch, const float* d_del_o
                                    const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc, float* d_dtb, float* d_del_x, int h, int w,
                                    int cin, int cout, int k, int tdim, int group_size, int flags, const ResnetPads* pads);
 
+// bla_unet_model.hip: the configuration a U-Net was created with (bla_diffusion.hip's sampler sizes its embeddings from it)
+const bla_unet_config* unet_config(const bla_unet* m);
+
 // "My gradients are ready", posted by the LAST gradient kernel of a data-parallel step instead of by the exchange launch behind it (every
 // step paid a launch boundary before any peer could start reading).  The block lives in device memory (built by bla_dp_connect); a launch that is
 // handed it counts its workgroups in, and the last one to finish stores epoch + 1 into every peer's flag word for this rank -- each workgroup after

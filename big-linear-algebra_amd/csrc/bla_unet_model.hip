@@ -264,6 +264,8 @@ __global__ void __launch_bounds__(256) unet_split_kernel(const float* __restrict
 unsigned grid_of(size_t n) { size_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
 }  // namespace
 
+const bla_unet_config* bla::unet_config(const bla_unet* m) { return &m->cfg; }
+
 extern "C" {
 
 bla_status bla_unet_create(bla_unet** out, const bla_unet_config* cfg) { return bla_unet_create_batched(out, cfg, 1); }

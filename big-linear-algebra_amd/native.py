@@ -47,7 +47,7 @@ ResnetGrads = _ptr_struct("bla_resnet_grads", ("conv1", "conv2", "time_w", "time
 ResnetWs = _ptr_struct("bla_resnet_ws", ("mu1", "sd1", "relu1", "c1", "tdense", "mu2", "sd2", "relu2", "dp", "c2", "res"))
 ResnetScratch = _ptr_struct("bla_resnet_scratch", ("g_out_a", "g_out_b", "g_in", "flip"))
 
-_VP, _I, _F, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_VP, _I, _F, _SZ, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_ulonglong
 # name -> (restype, argtypes); every symbol include/bla.h declares must appear here (tests check both ways)
 SIGNATURES = {
     "bla_init": (_I, [_I]), "bla_shutdown": (_I, []), "bla_is_initialized": (_I, []), "bla_device_count": (_I, []),
@@ -134,6 +134,15 @@ SIGNATURES = {
     "bla_dp_rccl_available": (_I, []), "bla_dp_rccl_init_all": (_I, [C.POINTER(_VP), C.POINTER(_I), _I]), "bla_dp_rccl_group_begin": (_I, []),
     "bla_dp_rccl_group_end": (_I, []), "bla_rand_guard_enter": (None, []), "bla_rand_guard_leave": (None, []),
     "bla_mnist_nn_dp_step": (_I, [_VP, _VP, _VP, _F, _I]), "bla_mnist_nn_dp_step_direct": (_I, [_VP, _VP, _VP, _F, _I]),
+    "bla_rand_u32": (_I, [_VP, _VP, _SZ, _U64, _U64]), "bla_rand_normal_f32": (_I, [_VP, _VP, _SZ, _F, _F, _U64, _U64]),
+    "bla_rand_bernoulli_u8": (_I, [_VP, _VP, _SZ, _F, _U64, _U64]),
+    "bla_adam_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _F, _F, _F, _I]),
+    "bla_diffusion_create": (_I, [C.POINTER(_VP), _I, _F, _F]), "bla_diffusion_destroy": (_I, [_VP]), "bla_diffusion_steps": (_I, [_VP]),
+    "bla_diffusion_schedule": (_I, [_VP, _I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bla_time_embedding_f32": (_I, [_VP, _VP, _I, _I, _VP]),
+    "bla_diffusion_noise_f32": (_I, [_VP, _VP, _VP, _I, _SZ, _I, _U64, _U64, _VP, _VP, _VP, _VP]),
+    "bla_diffusion_step_f32": (_I, [_VP, _VP, _VP, _VP, _I, _SZ, _I, _U64, _I, _VP]),
+    "bla_unet_sample_f32": (_I, [_VP, _VP, _VP, _VP, _U64]), "bla_mse_accumulate_f32": (_I, [_VP, _VP, _VP, _SZ, _VP]),
 }
 
 

@@ -28,6 +28,23 @@
  *                                                      oracle, tests/test_c_unet.py).  BLA_UNET_INIT=unit draws the same rand() values onto
  *                                                      +-sqrt(3 / (values one output sums over)) instead: variance preserving, trainable.
  *   draws <images> <dir>                               host only (tests): everything `train 1 <images>` would hand the device, as raw files
+ *   (not in the reference; what its train() / run()    `fit <epochs> [<batch>]` (default batch 64): DDPM training with Adam.  Parameters from
+ *    were building towards: the Adam moments :1887,    draw_parameters() with the variance-preserving draw (BLA_UNET_INIT=reference: the
+ *    the time embedding, an empty run() :1936)         reference's, which blows up, see above; BLA_UNET_RESUME=1: the file set).  Data: every
+ *                                                      $BLA_CIFAR_DIR/data_batch_{1..5}.bin that exists (default data/cifar, at least one),
+ *                                                      records in order, the last partial batch dropped, uploaded once as load_example maps
+ *                                                      them.  Each pass: bla_diffusion_noise_f32 (t, eps, x_t, time embedding), dropout
+ *                                                      decisions by bla_rand_bernoulli_u8 (p = DROPOUT_RATE), forward on x_t, backward
+ *                                                      against eps, bla_adam_f32 with grad_scale 1 / batch.  The mean loss of the last
+ *                                                      BLA_UNET_LOG_EVERY passes (default 50) is the only host round trip; the trained
+ *                                                      parameters go to the file set at the end.  BLA_ADAM_LR (2e-4), BLA_DIFFUSION_STEPS
+ *                                                      (1000, linear betas 1e-4 .. 0.02), BLA_SEED (42).  Draws nothing from rand() after
+ *                                                      draw_parameters(): every random number is a Philox stream of BLA_SEED.
+ *                                                      `sample <n> [<dir>]`: the file set, batches of min(n, BLA_UNET_BATCH) (default 16),
+ *                                                      x_T = bla_rand_normal_f32(seed, offset 0), bla_unet_sample_f32, x_0 mapped back to
+ *                                                      bytes (clamp(round((x + 1) 127.5)), the inverse of load_example) and written as
+ *                                                      <dir>/sample_%04d.bmp (default data/cifar_unet_samples).  Batch k draws with seed
+ *                                                      BLA_SEED + k.
  *
  * BLA_UNET_DUMP=<dir> makes train write what it uploaded (params, x, time embedding, noise, dropout decisions) and what came back (prediction,
  * gradient bucket) as raw little-endian files; tests/test_c_unet.py compares those with the oracle.
@@ -39,6 +56,7 @@
  *       -L big-linear-algebra_amd/lib -l:libbla_host.so -L big-linear-algebra_amd/csrc -l:libbla_hip.so -lm */
 #define _XOPEN_SOURCE 600      /* initstate / setstate, rand_r */
 #include "bla.h"
+#include "bmp.h"
 #include "cifar10.h"
 #include "csv.h"
 #include "util.h"
@@ -185,8 +203,8 @@ static void plan_model(void) {
 }
 
 /* init_parameters :1804-1844: _init_params_he / _init_params_xavier (:1439-1452) in double, stored as the float save_parameters would write */
-static void draw_parameters(void) {
-	const int unit_gain = strcmp(env_or("BLA_UNET_INIT", "reference"), "unit") == 0;
+static void draw_parameters(const char* default_init) {
+	const int unit_gain = strcmp(env_or("BLA_UNET_INIT", default_init), "unit") == 0;
 	rng_begin();
 	for (int t = 0; t < g_tensor_count; t++) {
 		Tensor* x = &g_tensors[t];
@@ -339,6 +357,17 @@ static void device_upload(Device* dv, const Inputs* in) {
 	CHECK(bla_memcpy_h2d(dv->temb, in->temb, (size_t)in->batch * TIME_EMBED_DIM * sizeof(float), NULL));
 	CHECK(bla_memcpy_h2d(dv->drop, in->drop, in->drop_per_image * in->batch, NULL));
 }
+/* device bucket -> host tensors (the inverse of device_set_params) */
+static void device_get_params(Device* dv) {
+	CHECK(bla_memcpy_d2h(dv->bucket, bla_unet_params(dv->net), bla_unet_param_count(dv->net) * sizeof(float), NULL));
+	CHECK(bla_stream_sync(NULL));
+	const int n = bla_unet_tensor_count(dv->net);
+	for (int i = 0; i < n; i++) {
+		size_t off, count; char name[64];
+		CHECK(bla_unet_tensor_info(dv->net, i, &off, &count, name, sizeof name));
+		for (int t = 0; t < g_tensor_count; t++) if (strcmp(g_tensors[t].name, name) == 0) memcpy(g_tensors[t].host, dv->bucket + off, count * sizeof(float));
+	}
+}
 static void device_close(Device* dv) {
 	CHECK(bla_free(dv->x)); CHECK(bla_free(dv->noise)); CHECK(bla_free(dv->temb)); CHECK(bla_free(dv->drop));
 	CHECK(bla_unet_destroy(dv->net)); free(dv->bucket);
@@ -356,7 +385,7 @@ static float batch_loss(const float* prediction, const float* noise, int batch) 
 }
 
 static void init(void) {
-	draw_parameters();
+	draw_parameters("reference");
 	save_parameters();
 }
 
@@ -364,7 +393,7 @@ static void train(int passes, int batch) {
 	const int fd = open_batch_file();
 	const char* dump_dir = getenv("BLA_UNET_DUMP");
 	const double learn_rate = atof(env_or("BLA_UNET_LEARN_RATE", "0"));
-	draw_parameters();                                                                          /* :1900 (load_parameters is commented out there) */
+	draw_parameters("reference");                                                               /* :1900 (load_parameters is commented out there) */
 	Inputs in = inputs_alloc(batch);
 	Device dv = device_open(batch, in.drop_per_image);
 	device_set_params(&dv);
@@ -397,14 +426,7 @@ static void train(int passes, int batch) {
 		}
 	}
 	if (learn_rate != 0) {                                                                      /* trained parameters back into the file set */
-		CHECK(bla_memcpy_d2h(dv.bucket, bla_unet_params(dv.net), params * sizeof(float), NULL));
-		CHECK(bla_stream_sync(NULL));
-		const int n = bla_unet_tensor_count(dv.net);
-		for (int i = 0; i < n; i++) {
-			size_t off, count; char name[64];
-			CHECK(bla_unet_tensor_info(dv.net, i, &off, &count, name, sizeof name));
-			for (int t = 0; t < g_tensor_count; t++) if (strcmp(g_tensors[t].name, name) == 0) memcpy(g_tensors[t].host, dv.bucket + off, count * sizeof(float));
-		}
+		device_get_params(&dv);
 		save_parameters();
 	}
 	free(prediction); inputs_free(&in); device_close(&dv); close(fd);
@@ -439,7 +461,7 @@ static void run(int num_predictions) {
 /* host only: what `train 1 <images>` would upload, and the rand() value that would come next */
 static void draws(int images, const char* dir) {
 	const int fd = open_batch_file();
-	draw_parameters();
+	draw_parameters("reference");
 	Inputs in = inputs_alloc(images);
 	unsigned int seed = 0;
 	draw_inputs(&in, fd, &seed, 1);
@@ -454,6 +476,133 @@ static void draws(int images, const char* dir) {
 	rng_begin(); const int next = rand(); rng_end();
 	printf("blocks %d drop_per_image %zu next_rand %d\n", g_block_count, in.drop_per_image, next);
 	inputs_free(&in); close(fd);
+}
+
+/* ---- fit / sample: DDPM training with Adam and the reverse-diffusion sampler (not in the reference; see the head of this file) ------------ */
+static unsigned long long env_seed(void) { return strtoull(env_or("BLA_SEED", "42"), NULL, 10); }
+static int env_steps(void) { const int T = atoi(env_or("BLA_DIFFUSION_STEPS", "1000")); if (T < 1) { fprintf(stderr, "BLA_DIFFUSION_STEPS must be >= 1\n"); exit(1); } return T; }
+
+/* every data_batch_{1..5}.bin below BLA_CIFAR_DIR, records in order, mapped as load_example maps them (:221-233: planes with their rows flipped,
+ * (p - 127.5) / 127.5); *count = records read */
+static float* read_training_set(size_t* count) {
+	const char* dir = env_or("BLA_CIFAR_DIR", "data/cifar");
+	float* all = NULL; size_t n = 0;
+	int files = 0;
+	for (int k = 1; k <= 5; k++) {
+		char path[512];
+		snprintf(path, sizeof path, "%s/data_batch_%d.bin", dir, k);
+		FILE* f = fopen(path, "rb");
+		if (!f) {
+			if (k == 1 && errno != ENOENT) { fprintf(stderr, "cannot open %s: %s\n", path, strerror(errno)); exit(1); }
+			continue;
+		}
+		files++;
+		uint8_t rec[3073];
+		while (fread(rec, 1, sizeof rec, f) == sizeof rec) {
+			if (n % 1024 == 0) all = realloc(all, (n + 1024) * IMAGE_FLOATS * sizeof(float));
+			float* x = all + n * IMAGE_FLOATS;
+			for (int c = 0; c < IMAGE_CHANNELS; c++)
+				for (int y = 0; y < IMAGE_SIDE; y++)
+					for (int i = 0; i < IMAGE_SIDE; i++)
+						x[(c * IMAGE_SIDE + y) * IMAGE_SIDE + i] = (float)(((double)rec[1 + (c * IMAGE_SIDE + IMAGE_SIDE - 1 - y) * IMAGE_SIDE + i] - 127.5) / 127.5);
+			n++;
+		}
+		fclose(f);
+	}
+	if (!files) { fprintf(stderr, "cannot open %s/data_batch_1.bin: %s (nor any data_batch_{2..5}.bin)\n", dir, strerror(ENOENT)); exit(1); }
+	*count = n;
+	return all;
+}
+
+static void fit(int epochs, int batch) {
+	if (batch < 1 || epochs < 1) { fprintf(stderr, "fit: epochs and batch must be >= 1\n"); exit(1); }
+	size_t records = 0;
+	float* data = read_training_set(&records);
+	const size_t per_epoch = records / batch;                                                   /* the last partial batch is dropped */
+	if (per_epoch == 0) { fprintf(stderr, "fit: %zu records, fewer than one batch of %d\n", records, batch); exit(1); }
+	if (env_flag("BLA_UNET_RESUME")) load_parameters(); else draw_parameters("unit");
+	const unsigned long long seed = env_seed();
+	const double lr = atof(env_or("BLA_ADAM_LR", "2e-4"));
+	int log_every = atoi(env_or("BLA_UNET_LOG_EVERY", "50"));
+	if (log_every < 1) log_every = 1;
+	Inputs in = inputs_alloc(1);                                                                /* only for the dropout layout */
+	Device dv = device_open(batch, in.drop_per_image);
+	device_set_params(&dv);
+	bla_diffusion* diff;
+	CHECK(bla_diffusion_create(&diff, env_steps(), 1e-4f, 0.02f));
+	const size_t params = bla_unet_param_count(dv.net), drops = bla_unet_dropout_count(dv.net), used = per_epoch * batch;
+	float *d_data, *d_m, *d_v; int* d_t; double* d_loss;
+	CHECK(bla_malloc((void**)&d_data, used * IMAGE_FLOATS * sizeof(float)));
+	CHECK(bla_memcpy_h2d(d_data, data, used * IMAGE_FLOATS * sizeof(float), NULL));
+	CHECK(bla_malloc((void**)&d_m, params * sizeof(float))); CHECK(bla_memset(d_m, 0, params * sizeof(float), NULL));
+	CHECK(bla_malloc((void**)&d_v, params * sizeof(float))); CHECK(bla_memset(d_v, 0, params * sizeof(float), NULL));
+	CHECK(bla_malloc((void**)&d_t, batch * sizeof(int)));
+	CHECK(bla_malloc((void**)&d_loss, sizeof(double))); CHECK(bla_memset(d_loss, 0, sizeof(double), NULL));
+	CHECK(bla_stream_sync(NULL));
+	free(data);
+	printf("fit: %zu records, %zu passes of %d per epoch, %d epochs\n", records, per_epoch, batch, epochs);
+	const size_t passes = per_epoch * epochs;
+	size_t logged = 0;
+	for (size_t pass = 0; pass < passes; pass++) {
+		const float* x0 = d_data + (pass % per_epoch) * batch * IMAGE_FLOATS;
+		CHECK(bla_diffusion_noise_f32(diff, NULL, x0, batch, IMAGE_FLOATS, TIME_EMBED_DIM, seed, pass, d_t, dv.noise, dv.x, dv.temb));
+		CHECK(bla_rand_bernoulli_u8(NULL, dv.drop, drops, DROPOUT_RATE, seed, (unsigned long long)pass << 32));
+		CHECK(bla_unet_forward_f32(dv.net, NULL, dv.x, dv.temb, dv.drop));
+		CHECK(bla_unet_backward_f32(dv.net, NULL, dv.noise));
+		CHECK(bla_mse_accumulate_f32(NULL, bla_unet_output(dv.net), dv.noise, (size_t)batch * IMAGE_FLOATS, d_loss));
+		CHECK(bla_adam_f32(NULL, bla_unet_params(dv.net), bla_unet_grads(dv.net), d_m, d_v, params, (float)lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
+		if ((pass + 1) % log_every == 0 || pass + 1 == passes) {
+			double sum = 0;
+			CHECK(bla_memcpy_d2h(&sum, d_loss, sizeof sum, NULL));
+			CHECK(bla_memset(d_loss, 0, sizeof(double), NULL));
+			CHECK(bla_stream_sync(NULL));
+			printf("Pass %zu:\tAvg loss: %f\n", pass, sum / ((double)(pass + 1 - logged) * batch * IMAGE_FLOATS));
+			fflush(stdout);
+			logged = pass + 1;
+		}
+	}
+	device_get_params(&dv);
+	save_parameters();
+	CHECK(bla_free(d_data)); CHECK(bla_free(d_m)); CHECK(bla_free(d_v)); CHECK(bla_free(d_t)); CHECK(bla_free(d_loss));
+	CHECK(bla_diffusion_destroy(diff));
+	inputs_free(&in); device_close(&dv);
+}
+
+static void sample(int count, const char* dir) {
+	int batch = atoi(env_or("BLA_UNET_BATCH", "16"));
+	if (batch > count) batch = count;
+	if (batch < 1) return;
+	load_parameters();
+	if (mkdir(dir, 0777) != 0 && errno != EEXIST) { fprintf(stderr, "cannot make %s: %s\n", dir, strerror(errno)); exit(1); }
+	const unsigned long long seed = env_seed();
+	Inputs in = inputs_alloc(1);
+	Device dv = device_open(batch, in.drop_per_image);
+	device_set_params(&dv);
+	bla_diffusion* diff;
+	CHECK(bla_diffusion_create(&diff, env_steps(), 1e-4f, 0.02f));
+	float* x = malloc((size_t)batch * IMAGE_FLOATS * sizeof(float));
+	uint8_t planes[IMAGE_FLOATS];
+	int done = 0;
+	for (unsigned long long k = 0; done < count; k++) {
+		CHECK(bla_rand_normal_f32(NULL, dv.x, (size_t)batch * IMAGE_FLOATS, 0.f, 1.f, seed + k, 0));   /* x_T */
+		CHECK(bla_unet_sample_f32(dv.net, diff, NULL, dv.x, seed + k));
+		CHECK(bla_memcpy_d2h(x, dv.x, (size_t)batch * IMAGE_FLOATS * sizeof(float), NULL));
+		CHECK(bla_stream_sync(NULL));
+		for (int b = 0; b < batch && done < count; b++, done++) {
+			for (int i = 0; i < IMAGE_FLOATS; i++) {                                            /* the inverse of load_example's (p - 127.5) / 127.5 */
+				const double v = round(((double)x[(size_t)b * IMAGE_FLOATS + i] + 1.0) * 127.5);
+				planes[i] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+			}
+			BMPData img = {IMAGE_SIDE, IMAGE_SIDE, planes, planes + IMAGE_SIDE * IMAGE_SIDE, planes + 2 * IMAGE_SIDE * IMAGE_SIDE};
+			char path[512];
+			snprintf(path, sizeof path, "%s/sample_%04d.bmp", dir, done);
+			write_bmp_data(path, &img);
+		}
+	}
+	printf("Wrote %d samples to %s\n", count, dir);
+	free(x);
+	CHECK(bla_diffusion_destroy(diff));
+	inputs_free(&in); device_close(&dv);
 }
 
 int main(int argc, char** argv) {
@@ -475,6 +624,14 @@ int main(int argc, char** argv) {
 		init();
 	} else if (strcmp(argv[1], "draws") == 0 && argc >= 4) {
 		draws(atoi(argv[2]), argv[3]);
+	} else if (strcmp(argv[1], "fit") == 0) {
+		if (argc < 3) {
+			printf("Please supply a number of epochs, usage:\n\tfit <num_epochs> [<batch> (default 64)]\n");
+			exit(1);
+		}
+		fit(atoi(argv[2]), argc < 4 ? 64 : atoi(argv[3]));
+	} else if (strcmp(argv[1], "sample") == 0) {
+		sample(argc < 3 ? 1 : atoi(argv[2]), argc < 4 ? "data/cifar_unet_samples" : argv[3]);
 	} else {
 		printf("Unrecognized argument, options:\n\trun [<num samples> (default 1)]\n\ttrain <num epochs>\n\tinit\n");
 		exit(1);

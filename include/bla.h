@@ -415,6 +415,53 @@ BLA_API bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* 
 /* del_Y = 2 (prediction - noise) (:1353-1364), then every block backwards; uses the activations of the last forward pass */
 BLA_API bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float* d_noise /* [C][H][W] */);
 
+/* ---- training the U-Net as a diffusion model (DDPM, Ho et al. 2020) and drawing images from it ----------------------------------------------
+ * Not in the reference: its train() allocates Adam's two moment sets and never uses them (:1887-1888), never noises an image at a timestep, never
+ * writes the time embedding (:535), and run() is empty (:1936).  examples/cifar_unet_gpu.c `fit` / `sample` drive these.
+ *
+ * Counter-based random numbers, Philox4x32-10 (Salmon et al., SC'11): key = (lo32(seed), hi32(seed)); element i of the stream (seed, offset) is word
+ * i % 4 of block j = offset + i / 4 (64-bit), counter {lo32(j), hi32(j), tag, 0}, tag 0 = u32, 1 = normal, 2 = Bernoulli (the three streams never
+ * share a block).  A round maps (c0, c1, c2, c3) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), M0 = 0xD2511F53,
+ * M1 = 0xCD9E8D57; the key adds (0x9E3779B9, 0xBB67AE85) between rounds; 10 rounds.  Normal: Box-Muller on the word pairs (w0, w1) and (w2, w3),
+ * u = ((w >> 8) + 0.5) * 2^-24 evaluated in fp32 (in (0, 1]), r = sqrt(-2 ln u_first), element 4j + 0 / 1 = r cos / r sin (2 pi u_second), the same
+ * for 4j + 2 / 3; out = mean + stddev * z.  Bernoulli: 1 = w < floor(p * 2^32), one byte per decision (the d_drop layout of bla_unet_forward_f32).
+ * Any alignment and any n; 16-byte stores in the body. */
+BLA_API bla_status bla_rand_u32(void* stream, unsigned int* d_out, size_t n, unsigned long long seed, unsigned long long offset);
+BLA_API bla_status bla_rand_normal_f32(void* stream, float* d_out, size_t n, float mean, float stddev, unsigned long long seed, unsigned long long offset);
+BLA_API bla_status bla_rand_bernoulli_u8(void* stream, unsigned char* d_out, size_t n, float p, unsigned long long seed, unsigned long long offset);
+/* Adam / AdamW over n floats in one pass (torch.optim.AdamW(foreach=False), step for step): g = grad_scale * grad; p *= 1 - lr * weight_decay;
+ * m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2; p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).  The bias
+ * corrections are formed in double on the host.  step >= 1 counts the updates so far, this one included; grad_scale = 1 / B for the U-Net's
+ * gradients (summed over the images).  m and v start zeroed. */
+BLA_API bla_status bla_adam_f32(void* stream, float* d_params, const float* d_grads, float* d_m, float* d_v, size_t n, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, float grad_scale, int step);
+/* Linear beta schedule over `steps` timesteps (DDPM: 1e-4 .. 0.02, steps = 1000): beta_t = beta_start + (beta_end - beta_start) t / (steps - 1),
+ * alpha_bar_t = prod_{s <= t} (1 - beta_s), in double at create time; the kernels read fp32 tables of the per-step coefficients. */
+typedef struct bla_diffusion bla_diffusion;
+BLA_API bla_status bla_diffusion_create(bla_diffusion** out, int steps, float beta_start, float beta_end);
+BLA_API bla_status bla_diffusion_destroy(bla_diffusion* d);
+BLA_API int bla_diffusion_steps(const bla_diffusion* d);
+BLA_API bla_status bla_diffusion_schedule(const bla_diffusion* d, int t, double* beta, double* alpha_bar);   /* host values of step t */
+/* d_temb [batch][time_dim] for the timesteps d_t [batch]: w_i = exp(-ln(1e4) i / half), element i = relu(sin(t w_i)), half + i = relu(cos(t w_i)),
+ * half = time_dim / 2 (an odd time_dim leaves the last element 0) -- the ReLU'd embedding of :168, evaluated in double. */
+BLA_API bla_status bla_time_embedding_f32(void* stream, const int* d_t, int batch, int time_dim, float* d_temb);
+/* One launch noises a training batch d_x0 [batch][image_floats] for pass `pass` (< 2^32): t_b = bla_rand_u32(seed, pass << 32)[b] % steps,
+ * d_eps = bla_rand_normal_f32(batch * image_floats, 0, 1, seed, pass << 32), d_xt = sqrt(alpha_bar_t) x0 + sqrt(1 - alpha_bar_t) eps,
+ * d_temb [batch][time_dim] = the embedding of t_b; all four written.  batch <= 4096. */
+BLA_API bla_status bla_diffusion_noise_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, int time_dim,
+                                           unsigned long long seed, unsigned long long pass, int* d_t, float* d_eps, float* d_xt, float* d_temb);
+/* The DDPM ancestral step at t (sigma_t^2 = beta_t), in place: x <- (x - beta_t / sqrt(1 - alpha_bar_t) eps_hat) / sqrt(1 - beta_t) + sigma_t z,
+ * z = bla_rand_normal_f32(batch * image_floats, 0, 1, seed, (t + 1) << 32) (offset 0 stays free for x_T), z = 0 at t = 0.  d_temb_next (may be
+ * NULL): the same launch writes the embedding of t - 1 for every image ([batch][time_dim]; nothing at t = 0). */
+BLA_API bla_status bla_diffusion_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, int batch, size_t image_floats, int t,
+                                          unsigned long long seed, int time_dim, float* d_temb_next);
+/* The whole reverse process on the model's batch: for t = steps - 1 .. 0, bla_unet_forward_f32 (no dropout) then bla_diffusion_step_f32 with the model's
+ * output.  d_x: in x_T, out x_0, [B][C][H][W].  The [B][time_dim] embedding workspace belongs to the diffusion object and is allocated on first use:
+ * like the model's own workspaces, run the sampler once eagerly before capturing it into a graph. */
+BLA_API bla_status bla_unet_sample_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, unsigned long long seed);
+/* *d_acc += sum_i (a_i - b_i)^2, accumulated in double in a fixed order (one workgroup): the training loss without a host round trip per pass */
+BLA_API bla_status bla_mse_accumulate_f32(void* stream, const float* d_a, const float* d_b, size_t n, double* d_acc);
+
 /* ---- device-resident MNIST-NN trainer: the hot loop of model/mnist_nn.c:218-315 with everything in HBM -------
  * sizes = {n0, n1, n2, n3} (784, 256, 128, 10 in the reference, model/mnist_nn.c:25-28); samples are columns.
  * Parameters sit in one flat bucket ordered W1,b1,W2,b2,W3,b3 (each row-major), gradients in a second bucket of
