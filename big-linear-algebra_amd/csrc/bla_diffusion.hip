@@ -22,6 +22,10 @@ struct bla_diffusion {
 	float* table = nullptr;        // device, 5 x steps: sqrt(abar), sqrt(1 - abar), beta / sqrt(1 - abar), 1 / sqrt(alpha), sqrt(beta)
 	float* temb = nullptr;         // the sampler's [B][time_dim] embedding workspace (grows on first use)
 	size_t temb_floats = 0;
+	float* xg = nullptr;           // the guided sampler's model input [2n][C][H][W] and class rows [2n] (grow on first use)
+	size_t xg_floats = 0;
+	int* rows = nullptr;
+	int rows_count = 0;
 };
 
 namespace {
@@ -112,6 +116,63 @@ __global__ void __launch_bounds__(kThreads) step_kernel(float* __restrict__ x, c
 	}
 }
 
+// the classifier-free guided step (Ho & Salimans 2022): eps~ = eps_u + s (eps_c - eps_u), then step_kernel's update word for word (the same z stream; at s = 0
+// eps~ is eps_u bit for bit, and so is the result).  x_copy (may be NULL) receives the new x too: the second, null-class half of the model's input.
+// temb_next [2 batch][dim] (may be NULL): the embedding of t - 1 plus table[rows[b]] (nothing added where table is NULL or a row is outside [0, classes])
+__global__ void __launch_bounds__(kThreads) guided_step_kernel(float* __restrict__ x, float* __restrict__ x_copy, const float* __restrict__ eps_c,
+                                                               const float* __restrict__ eps_u, float s, size_t n, int t, int steps, unsigned long long seed,
+                                                               const float* __restrict__ table, int batch, int dim, float* __restrict__ temb_next,
+                                                               const float* __restrict__ ctable, int classes, const int* __restrict__ rows, int vec) {
+	const float k = table[TAB_EPS_COEF * steps + t], inv = table[TAB_INV_SQRT_A * steps + t], sig = table[TAB_SIGMA * steps + t];
+	const unsigned long long offset = (unsigned long long)(t + 1) << 32;
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	if (temb_next && t > 0) {
+		const size_t ne = (size_t)2 * batch * dim;
+		for (size_t i = tid; i < ne; i += stride) {
+			const float e = temb_value(t - 1, (int)(i % dim), dim);
+			const int r = ctable ? rows[i / dim] : -1;
+			temb_next[i] = r >= 0 && r <= classes ? e + ctable[(size_t)r * dim + i % dim] : e;
+		}
+	}
+	const size_t n4 = vec ? n / 4 : 0;
+	for (size_t q = tid; q < n4; q += stride) {
+		const float4 z = t > 0 ? philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL)) : make_float4(0.f, 0.f, 0.f, 0.f);
+		const float4 c = reinterpret_cast<const float4*>(eps_c)[q], u = reinterpret_cast<const float4*>(eps_u)[q];
+		const float4 e = make_float4(fmaf(s, c.x - u.x, u.x), fmaf(s, c.y - u.y, u.y), fmaf(s, c.z - u.z, u.z), fmaf(s, c.w - u.w, u.w));
+		float4 v = reinterpret_cast<float4*>(x)[q];
+		v.x = (v.x - k * e.x) * inv + sig * z.x; v.y = (v.y - k * e.y) * inv + sig * z.y;
+		v.z = (v.z - k * e.z) * inv + sig * z.z; v.w = (v.w - k * e.w) * inv + sig * z.w;
+		reinterpret_cast<float4*>(x)[q] = v;
+		if (x_copy) reinterpret_cast<float4*>(x_copy)[q] = v;
+	}
+	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
+		const float z = t > 0 ? normal_at(seed, offset, i) : 0.f;
+		const float e = fmaf(s, eps_c[i] - eps_u[i], eps_u[i]);
+		x[i] = (x[i] - k * e) * inv + sig * z;
+		if (x_copy) x_copy[i] = x[i];
+	}
+}
+
+// the guided sampler's start: rows[b] = labels[b] (b < n; -1 outside [0, classes]) / classes (b >= n) unless labels is NULL (rows already hold them), and
+// temb [2n][dim] = the embedding of t plus table[rows[b]]
+__global__ void __launch_bounds__(kThreads) guided_start_kernel(const int* __restrict__ labels, int n, int classes, int* __restrict__ rows, const float* __restrict__ ctable,
+                                                                int t, int dim, float* __restrict__ temb) {
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	const size_t ne = (size_t)2 * n * dim;
+	for (size_t i = tid; i < ne; i += stride) {
+		const int b = (int)(i / dim);
+		int r;
+		if (labels) {
+			r = b >= n ? classes : (labels[b] >= 0 && labels[b] <= classes ? labels[b] : -1);
+			if (i % dim == 0) rows[b] = r;
+		} else {
+			r = rows[b];
+		}
+		const float e = temb_value(t, (int)(i % dim), dim);
+		temb[i] = r >= 0 && r <= classes ? e + ctable[(size_t)r * dim + i % dim] : e;
+	}
+}
+
 // acc[0] += sum_i (a_i - b_i)^2 in double, one workgroup in a fixed order (deterministic)
 __global__ void __launch_bounds__(1024) sq_diff_sum_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n, double* __restrict__ acc) {
 	__shared__ double part[16];
@@ -168,7 +229,7 @@ bla_status bla_diffusion_create(bla_diffusion** out, int steps, float beta_start
 bla_status bla_diffusion_destroy(bla_diffusion* d) {
 	if (!d) return BLA_OK;
 	(void)hipDeviceSynchronize();
-	(void)hipFree(d->table); (void)hipFree(d->temb);
+	(void)hipFree(d->table); (void)hipFree(d->temb); (void)hipFree(d->xg); (void)hipFree(d->rows);
 	delete d;
 	return BLA_OK;
 }
@@ -243,6 +304,82 @@ bla_status bla_unet_sample_f32(bla_unet* m, const bla_diffusion* d, void* stream
 		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
 		if ((st = bla_diffusion_step_f32(d, stream, d_x, bla_unet_output(m), B, F, t, seed, c.time_dim, dm->temb))) return st;
 	}
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_guided_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond, const float* d_eps_uncond,
+                                         float guidance, int batch, size_t image_floats, int t, unsigned long long seed, int time_dim, float* d_temb_next,
+                                         const float* d_table, int classes, const int* d_rows) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(d_x && d_eps_cond && d_eps_uncond, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(t >= 0 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", t, d->steps);
+	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
+	BLA_REQUIRE(!d_table || (d_rows && classes >= 1), BLA_ERR_INVALID, "a class table needs the rows [2 batch] and classes >= 1");
+	const size_t n = (size_t)batch * image_floats;
+	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_cond | (uintptr_t)d_eps_uncond | (uintptr_t)d_x_copy) % 16 == 0;
+	hipLaunchKernelGGL(guided_step_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_x_copy, d_eps_cond, d_eps_uncond, guidance, n, t,
+	                   d->steps, seed, d->table, batch, time_dim, d_temb_next, d_table, classes, d_rows, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_unet_sample_guided_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes, const int* labels, float guidance,
+                                      unsigned long long seed) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d && d_x && d_table && labels, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(classes >= 1, BLA_ERR_INVALID, "classes %d", classes);
+	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
+	const bla_unet_config& c = *unet_config(m);
+	const int B = bla_unet_batch(m), n = B / 2, T = d->steps;
+	BLA_REQUIRE(B % 2 == 0, BLA_ERR_INVALID, "the guided sampler needs an even model batch (n conditioned images + their n null-class copies), not %d", B);
+	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim, nx = (size_t)B * F;
+	hipStream_t s = pick_stream(stream);
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);   // workspaces, not part of the schedule
+	if (dm->temb_floats < ne || dm->xg_floats < nx || dm->rows_count < B) {
+		BLA_HIP(hipStreamSynchronize(s));
+		if (dm->temb_floats < ne) {
+			(void)hipFree(dm->temb); dm->temb = nullptr; dm->temb_floats = 0;
+			BLA_HIP(hipMalloc((void**)&dm->temb, ne * sizeof(float)));
+			dm->temb_floats = ne;
+		}
+		if (dm->xg_floats < nx) {
+			(void)hipFree(dm->xg); dm->xg = nullptr; dm->xg_floats = 0;
+			BLA_HIP(hipMalloc((void**)&dm->xg, nx * sizeof(float)));
+			dm->xg_floats = nx;
+		}
+		if (dm->rows_count < B) {
+			(void)hipFree(dm->rows); dm->rows = nullptr; dm->rows_count = 0;
+			BLA_HIP(hipMalloc((void**)&dm->rows, (size_t)B * sizeof(int)));
+			dm->rows_count = B;
+		}
+	}
+	const int* dev_labels = labels;
+	if (host_pointer(labels)) {   // host labels: checked here, the rows uploaded (not capturable: the copy waits for the host)
+		std::vector<int> rows(B);
+		for (int b = 0; b < n; b++) {
+			BLA_REQUIRE(labels[b] >= 0 && labels[b] <= classes, BLA_ERR_INVALID, "label %d of image %d outside [0, %d]", labels[b], b, classes);
+			rows[b] = labels[b]; rows[n + b] = classes;
+		}
+		BLA_HIP(hipMemcpyAsync(dm->rows, rows.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+		BLA_HIP(hipStreamSynchronize(s));
+		dev_labels = nullptr;
+	}
+	float* xg = dm->xg;
+	BLA_HIP(hipMemcpyAsync(xg, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	BLA_HIP(hipMemcpyAsync(xg + (size_t)n * F, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	hipLaunchKernelGGL(guided_start_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, s, dev_labels, n, classes, dm->rows, d_table, T - 1, c.time_dim, dm->temb);
+	BLA_HIP(hipGetLastError());
+	const float* out = bla_unet_output(m);
+	for (int t = T - 1; t >= 0; t--) {
+		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
+		if ((st = bla_diffusion_guided_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, n, F, t, seed, c.time_dim, dm->temb, d_table,
+		                                        classes, dm->rows)))
+			return st;
+	}
+	BLA_HIP(hipMemcpyAsync(d_x, xg, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
 	return BLA_OK;
 }
 

@@ -137,6 +137,10 @@ bla_status resnet_backward_batched(void* stream, int batch, const float* d_del_o
 
 // bla_unet_model.hip: the configuration a U-Net was created with (bla_diffusion.hip's sampler sizes its embeddings from it)
 const bla_unet_config* unet_config(const bla_unet* m);
+// bla_guidance.hip: true when the runtime does not know p as device memory (class labels handed in from the host are checked there); the Bernoulli
+// threshold of bla_rand_bernoulli_u8 (1 = word < floor(p * 2^32), clamped to [0, 2^32])
+bool host_pointer(const void* p);
+unsigned long long bernoulli_threshold(float p);
 
 // "My gradients are ready", posted by the LAST gradient kernel of a data-parallel step instead of by the exchange launch behind it (every
 // step paid a launch boundary before any peer could start reading).  The block lives in device memory (built by bla_dp_connect); a launch that is

@@ -72,6 +72,9 @@ struct bla_unet {
 	// backward
 	float *t1 = nullptr, *t2 = nullptr, *t3 = nullptr, *gskip[4] = {nullptr, nullptr, nullptr, nullptr};
 	TimeJob* time_jobs = nullptr;                // device, one per ResNet block (batch > 1)
+	TimeJob* emb_jobs = nullptr;                 // device, one per ResNet block, every configuration: dtb = where the backward pass leaves the block's per-image
+	                                             // channel sums (r.dtb; at B = 1 the block's time-bias gradient itself) -- read by bla_unet_embedding_grad_f32
+	bool have_grads = false;                     // a backward pass has run since the last forward pass
 	float* g_res = nullptr;                                      // batched: the residual 1x1 convolutions' data gradient (largest block input)
 	// batched, weight gradients on the context's side lane (BLA_UNET_SIDE=0: off): every gradient buffer of a backward pass is written ONCE (a pool instead of
 	// three rotating buffers), every block has its own g_out_b -- what the lane reads stays intact until the pass's one join
@@ -226,6 +229,51 @@ __global__ void __launch_bounds__(256) time_grads_all_kernel(const TimeJob* __re
 		}
 		for (int i = 0; i < nt; i++) j.g_tw[(size_t)(t0 + i) * j.cout + c] = acc[i];
 		if (blockIdx.y == 0) j.g_tb[c] = sb;
+	}
+}
+// dtemb[b][t] = sum_k sum_c W_k[t][c] dtb_k[b][c] -- the gradient of the time-embedding input, which feeds nothing but the 18 projections: grid (tdim / 8,
+// batch / 8), a workgroup = 8 embedding rows x 8 images.  Wave w takes the blocks [kEmbSplit[w], kEmbSplit[w + 1]) in order, lane l the channels c = l mod 64
+// of each, so every W_k row segment is read coalesced and once per tile of images; the 64 x 64 lane partials of each wave go through LDS and are summed in
+// lane order, then the four waves' sums in wave order.  The order is fixed: bit-reproducible.
+constexpr int kEmbSplit[5] = {0, 5, 9, 14, 18};
+__global__ void __launch_bounds__(256) temb_grad_all_kernel(const TimeJob* __restrict__ jobs, int batch, int tdim, float* __restrict__ dtemb) {
+	__shared__ float part[4][64][65];       // [wave][output = image * 8 + row][lane]
+	__shared__ float wsum[4][64];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int t0 = blockIdx.x * 8, nt = min(8, tdim - t0), b0 = blockIdx.y * 8, nb = min(8, batch - b0);
+	float acc[8][8];                        // [image][row]
+#pragma unroll
+	for (int i = 0; i < 8; i++)
+#pragma unroll
+		for (int j = 0; j < 8; j++) acc[i][j] = 0.f;
+	const int k1 = wave == 0 ? kEmbSplit[1] : wave == 1 ? kEmbSplit[2] : wave == 2 ? kEmbSplit[3] : kEmbSplit[4];
+	for (int k = wave == 0 ? 0 : wave == 1 ? kEmbSplit[1] : wave == 2 ? kEmbSplit[2] : kEmbSplit[3]; k < k1; k++) {
+		const TimeJob j = jobs[k];
+#pragma unroll 2
+		for (int c = lane; c < j.cout; c += 64) {
+			float d[8], w[8];
+#pragma unroll
+			for (int i = 0; i < 8; i++) d[i] = i < nb ? j.dtb[(size_t)(b0 + i) * j.cout + c] : 0.f;
+#pragma unroll
+			for (int r = 0; r < 8; r++) w[r] = r < nt ? j.w[(size_t)(t0 + r) * j.cout + c] : 0.f;
+#pragma unroll
+			for (int i = 0; i < 8; i++)
+#pragma unroll
+				for (int r = 0; r < 8; r++) acc[i][r] = fmaf(w[r], d[i], acc[i][r]);
+		}
+	}
+#pragma unroll
+	for (int i = 0; i < 8; i++)
+#pragma unroll
+		for (int r = 0; r < 8; r++) part[wave][i * 8 + r][lane] = acc[i][r];
+	__syncthreads();
+	float s = 0.f;                          // thread (wave, lane): output `lane` of wave `wave`, its 64 lanes in order
+	for (int l = 0; l < 64; l++) s += part[wave][lane][l];
+	wsum[wave][lane] = s;
+	__syncthreads();
+	if (wave == 0) {
+		const int i = lane >> 3, r = lane & 7;
+		if (i < nb && r < nt) dtemb[(size_t)(b0 + i) * tdim + t0 + r] = ((wsum[0][lane] + wsum[1][lane]) + wsum[2][lane]) + wsum[3][lane];
 	}
 }
 // del_Y = 2 (prediction - noise), model/cifar_unet.c:1353-1364
@@ -388,6 +436,18 @@ bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, i
 		m->time_jobs = (TimeJob*)tj;
 		BLA_HIP(hipMemcpy(tj, jobs, sizeof jobs, hipMemcpyHostToDevice));
 	}
+	{   // the embedding gradient's table: every configuration (the backward pass leaves the per-image channel sums in r.dtb, or at B = 1 in the time-bias gradient)
+		TimeJob jobs[18];
+		for (int i = 0; i < 18; i++) {
+			const Res& r = m->res[i];
+			jobs[i] = TimeJob{m->params + r.tw, m->params + r.tb, r.ws.tdense, batch > 1 ? r.dtb : m->grads + r.tb, m->grads + r.tw, m->grads + r.tb, r.cout};
+		}
+		void* ej = nullptr;
+		BLA_HIP(hipMalloc(&ej, sizeof jobs));
+		m->owned.push_back(ej);
+		m->emb_jobs = (TimeJob*)ej;
+		BLA_HIP(hipMemcpy(ej, jobs, sizeof jobs, hipMemcpyHostToDevice));
+	}
 	static const bool prep_on = [] { const char* e = getenv("BLA_UNET_PREP"); return !(e && e[0] == '0'); }();
 	if (batch > 1 && prep_on) {
 		// One launch at the head of forward() and one at the head of backward() put every convolution's kernels into the form its product reads (window order,
@@ -469,6 +529,7 @@ bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* d_x, con
 	const int B = m->batch;
 	hipStream_t s = pick_stream(stream);
 	m->last_x = d_x; m->last_temb = d_time_embedding; m->last_drop = d_drop;
+	m->have_grads = false;
 	auto res = [&](int i, const float* in) -> bla_status {
 		Res& r = m->res[i];
 		bla_resnet_params p = {P + r.conv1, P + r.conv2, P + r.tw, P + r.tb, r.res != kNone ? P + r.res : nullptr};
@@ -642,8 +703,23 @@ bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float* d_noise
 		BLA_HIP(hipGetLastError());
 	}
 	if (m->side) TRY(side_lane_join(s));      // the weight gradients are in when this stream moves on
+	m->have_grads = true;
 	return BLA_OK;
 }
 #undef TRY
+
+/* d_dtemb [B][time_dim] = dL/dtemb for the loss of the last backward pass: every block's time projection W_k [time_dim][cout] applied to the per-image
+ * channel sums it left behind, summed over the 18 blocks -- one launch, nothing of the backward pass re-run or changed */
+bla_status bla_unet_embedding_grad_f32(bla_unet* m, void* stream, float* d_dtemb) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d_dtemb, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(m->have_grads, BLA_ERR_INVALID, "no bla_unet_backward_f32 since the last forward pass");
+	const int tdim = m->cfg.time_dim;
+	hipLaunchKernelGGL(temb_grad_all_kernel, dim3((unsigned)((tdim + 7) / 8), (unsigned)((m->batch + 7) / 8)), dim3(256), 0, pick_stream(stream), m->emb_jobs, m->batch,
+	                   tdim, d_dtemb);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
 
 }  // extern "C"

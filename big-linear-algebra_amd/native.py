@@ -143,6 +143,11 @@ SIGNATURES = {
     "bla_diffusion_noise_f32": (_I, [_VP, _VP, _VP, _I, _SZ, _I, _U64, _U64, _VP, _VP, _VP, _VP]),
     "bla_diffusion_step_f32": (_I, [_VP, _VP, _VP, _VP, _I, _SZ, _I, _U64, _I, _VP]),
     "bla_unet_sample_f32": (_I, [_VP, _VP, _VP, _VP, _U64]), "bla_mse_accumulate_f32": (_I, [_VP, _VP, _VP, _SZ, _VP]),
+    "bla_unet_embedding_grad_f32": (_I, [_VP, _VP, _VP]),
+    "bla_class_embedding_f32": (_I, [_VP, _VP, _I, _VP, _I, _I, _F, _U64, _U64, _VP, _VP]),
+    "bla_class_embedding_grad_f32": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
+    "bla_diffusion_guided_step_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _I, _SZ, _I, _U64, _I, _VP, _VP, _I, _VP]),
+    "bla_unet_sample_guided_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _F, _U64]),
 }
 
 

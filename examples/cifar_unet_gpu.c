@@ -45,6 +45,20 @@
  *                                                      bytes (clamp(round((x + 1) 127.5)), the inverse of load_example) and written as
  *                                                      <dir>/sample_%04d.bmp (default data/cifar_unet_samples).  Batch k draws with seed
  *                                                      BLA_SEED + k.
+ *   (not in the reference: its data_batch records'      Class-conditional diffusion with classifier-free guidance (Ho & Salimans 2022).
+ *    label byte, read and dropped by load_example)     `fit` with BLA_UNET_CLASSES=1: the label bytes are read too (a label > 9 stops the
+ *                                                      program before the device is opened); a [11][512] class table (row 10 = the null
+ *                                                      class) starts at zero -- the conditional model starts exactly as the unconditional
+ *                                                      one -- or, with BLA_UNET_RESUME=1, from class_embedding.csv if it exists.  Each pass:
+ *                                                      noise, bla_class_embedding_f32 (label dropped with p = BLA_UNET_UNCOND, default 0.1,
+ *                                                      Philox offset (pass << 32) + 2^31), dropout draw, forward, backward,
+ *                                                      bla_unet_embedding_grad_f32, bla_class_embedding_grad_f32, Adam on the parameters and
+ *                                                      on the table (moments of its own).  The table goes to <weights>/class_embedding.csv
+ *                                                      (save_parameters' matrix format).  Without BLA_UNET_CLASSES `fit` is unchanged.
+ *                                                      `sample` with BLA_UNET_CLASS=k (0..9): the table file (checked, like k, before the
+ *                                                      device is opened) and bla_unet_sample_guided_f32 at model batch 2 x min(n,
+ *                                                      BLA_UNET_BATCH), guidance BLA_UNET_GUIDANCE (default 3); file names, BMP format and
+ *                                                      per-batch seeds as without.  Without BLA_UNET_CLASS `sample` is unchanged.
  *
  * BLA_UNET_DUMP=<dir> makes train write what it uploaded (params, x, time embedding, noise, dropout decisions) and what came back (prediction,
  * gradient bucket) as raw little-endian files; tests/test_c_unet.py compares those with the oracle.
@@ -74,6 +88,7 @@ enum { IMAGE_SIDE = 32, IMAGE_CHANNELS = 3, TIME_EMBED_DIM = 512, KERNEL_SIZE = 
 static const int kDims[4] = {128, 256, 256, 256};
 static const float DROPOUT_RATE = 0.1;
 enum { IMAGE_FLOATS = IMAGE_CHANNELS * IMAGE_SIDE * IMAGE_SIDE, MAX_TENSORS = 160, MAX_BLOCKS = 18 };
+enum { CLASSES = 10 };   /* CIFAR-10; the class table has CLASSES + 1 rows, the last the null class */
 
 #define CHECK(call)                                                                              \
 	do {                                                                                         \
@@ -483,10 +498,11 @@ static unsigned long long env_seed(void) { return strtoull(env_or("BLA_SEED", "4
 static int env_steps(void) { const int T = atoi(env_or("BLA_DIFFUSION_STEPS", "1000")); if (T < 1) { fprintf(stderr, "BLA_DIFFUSION_STEPS must be >= 1\n"); exit(1); } return T; }
 
 /* every data_batch_{1..5}.bin below BLA_CIFAR_DIR, records in order, mapped as load_example maps them (:221-233: planes with their rows flipped,
- * (p - 127.5) / 127.5); *count = records read */
-static float* read_training_set(size_t* count) {
+ * (p - 127.5) / 127.5); *count = records read; *labels (if not NULL): the records' label bytes */
+static float* read_training_set(size_t* count, uint8_t** labels) {
 	const char* dir = env_or("BLA_CIFAR_DIR", "data/cifar");
 	float* all = NULL; size_t n = 0;
+	uint8_t* lab = NULL;
 	int files = 0;
 	for (int k = 1; k <= 5; k++) {
 		char path[512];
@@ -499,7 +515,8 @@ static float* read_training_set(size_t* count) {
 		files++;
 		uint8_t rec[3073];
 		while (fread(rec, 1, sizeof rec, f) == sizeof rec) {
-			if (n % 1024 == 0) all = realloc(all, (n + 1024) * IMAGE_FLOATS * sizeof(float));
+			if (n % 1024 == 0) { all = realloc(all, (n + 1024) * IMAGE_FLOATS * sizeof(float)); if (labels) lab = realloc(lab, n + 1024); }
+			if (labels) lab[n] = rec[0];
 			float* x = all + n * IMAGE_FLOATS;
 			for (int c = 0; c < IMAGE_CHANNELS; c++)
 				for (int y = 0; y < IMAGE_SIDE; y++)
@@ -511,15 +528,46 @@ static float* read_training_set(size_t* count) {
 	}
 	if (!files) { fprintf(stderr, "cannot open %s/data_batch_1.bin: %s (nor any data_batch_{2..5}.bin)\n", dir, strerror(ENOENT)); exit(1); }
 	*count = n;
+	if (labels) *labels = lab;
 	return all;
+}
+
+/* the class table, <weights>/class_embedding.csv, [CLASSES + 1][TIME_EMBED_DIM] in save_parameters' matrix format; 0 = no such file */
+static int load_class_table(float* table) {
+	char path[512];
+	data_path(path, sizeof path, "class_embedding.csv");
+	FILE* f = fopen(path, "r");
+	if (!f) return 0;
+	int count = 0;
+	float* v = read_csv_contents_file(f, &count);
+	if (count != (CLASSES + 1) * TIME_EMBED_DIM) { fprintf(stderr, "%s holds %d values, expected %d\n", path, count, (CLASSES + 1) * TIME_EMBED_DIM); exit(1); }
+	memcpy(table, v, (size_t)count * sizeof(float));
+	free(v);
+	return 1;
+}
+static void save_class_table(float* table) {
+	char path[512];
+	data_path(path, sizeof path, "class_embedding.csv");
+	write_csv_contents(path, table, TIME_EMBED_DIM, CLASSES + 1);
 }
 
 static void fit(int epochs, int batch) {
 	if (batch < 1 || epochs < 1) { fprintf(stderr, "fit: epochs and batch must be >= 1\n"); exit(1); }
+	const int classes = env_flag("BLA_UNET_CLASSES");
 	size_t records = 0;
-	float* data = read_training_set(&records);
+	uint8_t* labels = NULL;
+	float* data = read_training_set(&records, classes ? &labels : NULL);
 	const size_t per_epoch = records / batch;                                                   /* the last partial batch is dropped */
 	if (per_epoch == 0) { fprintf(stderr, "fit: %zu records, fewer than one batch of %d\n", records, batch); exit(1); }
+	float* table = NULL;
+	const double p_uncond = atof(env_or("BLA_UNET_UNCOND", "0.1"));
+	if (classes) {
+		for (size_t r = 0; r < records; r++)
+			if (labels[r] >= CLASSES) { fprintf(stderr, "fit: record %zu has label %d; CIFAR-10 labels are 0..%d\n", r, labels[r], CLASSES - 1); exit(1); }
+		if (!(p_uncond >= 0 && p_uncond <= 1)) { fprintf(stderr, "fit: BLA_UNET_UNCOND must lie in [0, 1]\n"); exit(1); }
+		table = calloc((size_t)(CLASSES + 1) * TIME_EMBED_DIM, sizeof(float));
+		if (env_flag("BLA_UNET_RESUME")) (void)load_class_table(table);
+	}
 	if (env_flag("BLA_UNET_RESUME")) load_parameters(); else draw_parameters("unit");
 	const unsigned long long seed = env_seed();
 	const double lr = atof(env_or("BLA_ADAM_LR", "2e-4"));
@@ -538,19 +586,45 @@ static void fit(int epochs, int batch) {
 	CHECK(bla_malloc((void**)&d_v, params * sizeof(float))); CHECK(bla_memset(d_v, 0, params * sizeof(float), NULL));
 	CHECK(bla_malloc((void**)&d_t, batch * sizeof(int)));
 	CHECK(bla_malloc((void**)&d_loss, sizeof(double))); CHECK(bla_memset(d_loss, 0, sizeof(double), NULL));
+	const size_t table_floats = (size_t)(CLASSES + 1) * TIME_EMBED_DIM;
+	float *d_table = NULL, *d_gtable = NULL, *d_tm = NULL, *d_tv = NULL, *d_dtemb = NULL; int *d_labels = NULL, *d_rows = NULL;
+	if (classes) {
+		int* lab = malloc(used * sizeof(int));
+		for (size_t r = 0; r < used; r++) lab[r] = labels[r];
+		CHECK(bla_malloc((void**)&d_labels, used * sizeof(int)));
+		CHECK(bla_memcpy_h2d(d_labels, lab, used * sizeof(int), NULL));
+		CHECK(bla_malloc((void**)&d_table, table_floats * sizeof(float)));
+		CHECK(bla_memcpy_h2d(d_table, table, table_floats * sizeof(float), NULL));
+		CHECK(bla_malloc((void**)&d_gtable, table_floats * sizeof(float)));
+		CHECK(bla_malloc((void**)&d_tm, table_floats * sizeof(float))); CHECK(bla_memset(d_tm, 0, table_floats * sizeof(float), NULL));
+		CHECK(bla_malloc((void**)&d_tv, table_floats * sizeof(float))); CHECK(bla_memset(d_tv, 0, table_floats * sizeof(float), NULL));
+		CHECK(bla_malloc((void**)&d_dtemb, (size_t)batch * TIME_EMBED_DIM * sizeof(float)));
+		CHECK(bla_malloc((void**)&d_rows, batch * sizeof(int)));
+		CHECK(bla_stream_sync(NULL));
+		free(lab);
+	}
 	CHECK(bla_stream_sync(NULL));
-	free(data);
+	free(data); free(labels);
 	printf("fit: %zu records, %zu passes of %d per epoch, %d epochs\n", records, per_epoch, batch, epochs);
 	const size_t passes = per_epoch * epochs;
 	size_t logged = 0;
 	for (size_t pass = 0; pass < passes; pass++) {
 		const float* x0 = d_data + (pass % per_epoch) * batch * IMAGE_FLOATS;
 		CHECK(bla_diffusion_noise_f32(diff, NULL, x0, batch, IMAGE_FLOATS, TIME_EMBED_DIM, seed, pass, d_t, dv.noise, dv.x, dv.temb));
+		if (classes)   /* the label dropout's Philox blocks start at (pass << 32) + 2^31, behind the dropout decisions' (bla.h) */
+			CHECK(bla_class_embedding_f32(NULL, d_table, CLASSES, d_labels + (pass % per_epoch) * batch, batch, TIME_EMBED_DIM, (float)p_uncond, seed,
+			                              ((unsigned long long)pass << 32) + (1ull << 31), d_rows, dv.temb));
 		CHECK(bla_rand_bernoulli_u8(NULL, dv.drop, drops, DROPOUT_RATE, seed, (unsigned long long)pass << 32));
 		CHECK(bla_unet_forward_f32(dv.net, NULL, dv.x, dv.temb, dv.drop));
 		CHECK(bla_unet_backward_f32(dv.net, NULL, dv.noise));
+		if (classes) {
+			CHECK(bla_unet_embedding_grad_f32(dv.net, NULL, d_dtemb));
+			CHECK(bla_class_embedding_grad_f32(NULL, d_dtemb, d_rows, batch, CLASSES, TIME_EMBED_DIM, d_gtable));
+		}
 		CHECK(bla_mse_accumulate_f32(NULL, bla_unet_output(dv.net), dv.noise, (size_t)batch * IMAGE_FLOATS, d_loss));
 		CHECK(bla_adam_f32(NULL, bla_unet_params(dv.net), bla_unet_grads(dv.net), d_m, d_v, params, (float)lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
+		if (classes)
+			CHECK(bla_adam_f32(NULL, d_table, d_gtable, d_tm, d_tv, table_floats, (float)lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
 		if ((pass + 1) % log_every == 0 || pass + 1 == passes) {
 			double sum = 0;
 			CHECK(bla_memcpy_d2h(&sum, d_loss, sizeof sum, NULL));
@@ -563,6 +637,14 @@ static void fit(int epochs, int batch) {
 	}
 	device_get_params(&dv);
 	save_parameters();
+	if (classes) {
+		CHECK(bla_memcpy_d2h(table, d_table, table_floats * sizeof(float), NULL));
+		CHECK(bla_stream_sync(NULL));
+		save_class_table(table);
+		CHECK(bla_free(d_labels)); CHECK(bla_free(d_table)); CHECK(bla_free(d_gtable)); CHECK(bla_free(d_tm)); CHECK(bla_free(d_tv));
+		CHECK(bla_free(d_dtemb)); CHECK(bla_free(d_rows));
+		free(table);
+	}
 	CHECK(bla_free(d_data)); CHECK(bla_free(d_m)); CHECK(bla_free(d_v)); CHECK(bla_free(d_t)); CHECK(bla_free(d_loss));
 	CHECK(bla_diffusion_destroy(diff));
 	inputs_free(&in); device_close(&dv);
@@ -572,20 +654,51 @@ static void sample(int count, const char* dir) {
 	int batch = atoi(env_or("BLA_UNET_BATCH", "16"));
 	if (batch > count) batch = count;
 	if (batch < 1) return;
+	/* BLA_UNET_CLASS=k: guided sampling of class k with the table fit wrote; both checked before the device is opened */
+	const char* class_env = getenv("BLA_UNET_CLASS");
+	const int guided = class_env && *class_env;
+	int klass = 0;
+	float guidance = 0.f, *table = NULL;
+	if (guided) {
+		char* end = NULL;
+		const long k = strtol(class_env, &end, 10);
+		if (*end || k < 0 || k >= CLASSES) { fprintf(stderr, "sample: BLA_UNET_CLASS=%s; the classes are 0..%d\n", class_env, CLASSES - 1); exit(1); }
+		klass = (int)k;
+		guidance = (float)atof(env_or("BLA_UNET_GUIDANCE", "3"));
+		table = malloc((size_t)(CLASSES + 1) * TIME_EMBED_DIM * sizeof(float));
+		if (!load_class_table(table)) {
+			char path[512];
+			data_path(path, sizeof path, "class_embedding.csv");
+			fprintf(stderr, "sample: cannot open %s (run `fit` with BLA_UNET_CLASSES=1 first)\n", path);
+			exit(1);
+		}
+	}
 	load_parameters();
 	if (mkdir(dir, 0777) != 0 && errno != EEXIST) { fprintf(stderr, "cannot make %s: %s\n", dir, strerror(errno)); exit(1); }
 	const unsigned long long seed = env_seed();
 	Inputs in = inputs_alloc(1);
-	Device dv = device_open(batch, in.drop_per_image);
+	Device dv = device_open(guided ? 2 * batch : batch, in.drop_per_image);   /* guided: n conditioned images + their n null-class copies */
 	device_set_params(&dv);
 	bla_diffusion* diff;
 	CHECK(bla_diffusion_create(&diff, env_steps(), 1e-4f, 0.02f));
+	float* d_table = NULL; int* d_labels = NULL;
+	if (guided) {
+		int* lab = malloc(batch * sizeof(int));
+		for (int b = 0; b < batch; b++) lab[b] = klass;
+		CHECK(bla_malloc((void**)&d_table, (size_t)(CLASSES + 1) * TIME_EMBED_DIM * sizeof(float)));
+		CHECK(bla_memcpy_h2d(d_table, table, (size_t)(CLASSES + 1) * TIME_EMBED_DIM * sizeof(float), NULL));
+		CHECK(bla_malloc((void**)&d_labels, batch * sizeof(int)));
+		CHECK(bla_memcpy_h2d(d_labels, lab, batch * sizeof(int), NULL));
+		CHECK(bla_stream_sync(NULL));
+		free(lab);
+	}
 	float* x = malloc((size_t)batch * IMAGE_FLOATS * sizeof(float));
 	uint8_t planes[IMAGE_FLOATS];
 	int done = 0;
 	for (unsigned long long k = 0; done < count; k++) {
 		CHECK(bla_rand_normal_f32(NULL, dv.x, (size_t)batch * IMAGE_FLOATS, 0.f, 1.f, seed + k, 0));   /* x_T */
-		CHECK(bla_unet_sample_f32(dv.net, diff, NULL, dv.x, seed + k));
+		if (guided) CHECK(bla_unet_sample_guided_f32(dv.net, diff, NULL, dv.x, d_table, CLASSES, d_labels, guidance, seed + k));
+		else CHECK(bla_unet_sample_f32(dv.net, diff, NULL, dv.x, seed + k));
 		CHECK(bla_memcpy_d2h(x, dv.x, (size_t)batch * IMAGE_FLOATS * sizeof(float), NULL));
 		CHECK(bla_stream_sync(NULL));
 		for (int b = 0; b < batch && done < count; b++, done++) {
@@ -601,6 +714,7 @@ static void sample(int count, const char* dir) {
 	}
 	printf("Wrote %d samples to %s\n", count, dir);
 	free(x);
+	if (guided) { CHECK(bla_free(d_table)); CHECK(bla_free(d_labels)); free(table); }
 	CHECK(bla_diffusion_destroy(diff));
 	inputs_free(&in); device_close(&dv);
 }

@@ -462,6 +462,46 @@ BLA_API bla_status bla_unet_sample_f32(bla_unet* m, const bla_diffusion* d, void
 /* *d_acc += sum_i (a_i - b_i)^2, accumulated in double in a fixed order (one workgroup): the training loss without a host round trip per pass */
 BLA_API bla_status bla_mse_accumulate_f32(void* stream, const float* d_a, const float* d_b, size_t n, double* d_acc);
 
+/* ---- class-conditional diffusion with classifier-free guidance (Ho & Salimans 2022) ----------------------------------------------------------
+ * Not in the reference.  A learned class embedding, a table [classes + 1][time_dim] whose row `classes` is the null class, is added to the time
+ * embedding; during training the label is dropped at random (the image then uses the null row), so the one network learns the conditional and the
+ * unconditional noise prediction.  At sampling time the two are mixed: eps~ = eps_u + s (eps_c - eps_u).  examples/cifar_unet_gpu.c drives these
+ * (BLA_UNET_CLASSES / BLA_UNET_CLASS).
+ *
+ * Philox offsets of a conditional training pass `pass` (bla_diffusion_noise_f32's layout above): noise and timesteps at pass << 32 (tags 0 and 1),
+ * the dropout decisions at pass << 32 (tag 2, bla_unet_dropout_count() / 4 blocks), the label dropout at (pass << 32) + (1 << 31) (tag 2, batch / 4
+ * blocks).  The two tag-2 ranges are disjoint as long as bla_unet_dropout_count() < 2^33, and both stay below the next pass's (pass + 1) << 32. */
+
+/* Gradient of the time-embedding input: d_dtemb [B][time_dim] = dL/dtemb for the loss of the last bla_unet_backward_f32 (del_Y = 2 (pred - noise)).
+ * The embedding feeds nothing but the 18 ResNet blocks' projections temb . W_k + bias_k, so dtemb[b] = sum_k W_k . dtb_k[b] with dtb_k[b] the per-image
+ * channel sums of the gradient each block's backward pass already forms.  One launch, deterministic (a fixed summation order), changes nothing the
+ * backward pass computed.  Every configuration bla_unet_create[_batched] accepts.  BLA_ERR_INVALID when no backward pass has run since the last forward. */
+BLA_API bla_status bla_unet_embedding_grad_f32(bla_unet* m, void* stream, float* d_dtemb);
+/* Class embedding with label dropout, in place: row_b = classes if bla_rand_bernoulli_u8(p_uncond, seed, offset)[b] is 1, else labels[b];
+ * d_temb[b] += d_table[row_b] ([batch][time_dim], table [classes + 1][time_dim]); d_rows [batch] receives the rows.  labels[b] == classes is allowed
+ * (that image is forced unconditional).  Labels in host memory are checked on the host: one outside [0, classes] is BLA_ERR_INVALID before anything
+ * runs (the call then waits for the stream: not capturable).  Labels in device memory cannot be checked without a round trip: an image whose label
+ * lies outside [0, classes] gets row -1 and its embedding is left as it was (bla_class_embedding_grad_f32 skips it).  batch <= 4096. */
+BLA_API bla_status bla_class_embedding_f32(void* stream, const float* d_table, int classes, const int* labels, int batch, int time_dim, float p_uncond,
+                                           unsigned long long seed, unsigned long long offset, int* d_rows, float* d_temb);
+/* Gradient of the table: d_gtable[k] = sum over the images b with d_rows[b] == k, in image order, of d_dtemb[b] ([classes + 1][time_dim]; no atomics,
+ * bit-reproducible); rows no image used are written as 0.  Adam on the table is bla_adam_f32 with grad_scale = 1 / batch. */
+BLA_API bla_status bla_class_embedding_grad_f32(void* stream, const float* d_dtemb, const int* d_rows, int batch, int classes, int time_dim, float* d_gtable);
+/* The guided ancestral step: eps~ = eps_u + guidance (eps_c - eps_u), then exactly bla_diffusion_step_f32's update of d_x [batch][image_floats] with the
+ * same z stream (seed, (t + 1) << 32).  guidance 0 = the unguided step on eps_u (bit for bit), 1 = the conditional model alone, > 1 = guidance (Ho &
+ * Salimans' w is guidance - 1).  d_x_copy (may be NULL) receives the new x as well: the null-class half of a batch-2n model input.  d_temb_next (may be
+ * NULL) [2 batch][time_dim]: the embedding of t - 1 (nothing at t = 0) plus, where d_table is given, d_table[d_rows[b]] for its 2 batch rows (a row
+ * outside [0, classes] adds nothing).  One launch. */
+BLA_API bla_status bla_diffusion_guided_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond,
+                                                 const float* d_eps_uncond, float guidance, int batch, size_t image_floats, int t, unsigned long long seed,
+                                                 int time_dim, float* d_temb_next, const float* d_table, int classes, const int* d_rows);
+/* Guided sampling on a model of batch 2n: images 0 .. n-1 carry their class rows, images n .. 2n-1 the null class on copies of the same x, so every step is
+ * ONE batch-2n forward pass followed by bla_diffusion_guided_step_f32.  d_x [n][C][H][W]: in x_T, out x_0.  labels [n] as for bla_class_embedding_f32
+ * (host labels checked, BLA_ERR_INVALID; a device label outside [0, classes] adds no class row).  An odd model batch is BLA_ERR_INVALID.  The model input,
+ * embedding and row workspaces belong to the diffusion object and are allocated on first use: run once eagerly before capturing it into a graph. */
+BLA_API bla_status bla_unet_sample_guided_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes,
+                                              const int* labels, float guidance, unsigned long long seed);
+
 /* ---- device-resident MNIST-NN trainer: the hot loop of model/mnist_nn.c:218-315 with everything in HBM -------
  * sizes = {n0, n1, n2, n3} (784, 256, 128, 10 in the reference, model/mnist_nn.c:25-28); samples are columns.
  * Parameters sit in one flat bucket ordered W1,b1,W2,b2,W3,b3 (each row-major), gradients in a second bucket of
