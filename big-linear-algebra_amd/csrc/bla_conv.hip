@@ -14,6 +14,7 @@
 //     transposes; both run on the LDS-tiled transpose kernel, and the matrix_transpose copies conv_ddx makes
 //     around its two products (lib/conv.c:221-227) disappear into the GEMM's transa/transb.
 #include "bla_internal.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
@@ -733,27 +734,40 @@ static bla_status table_build_allowed(hipStream_t s) {
 	return BLA_OK;
 }
 
-struct TableEntry { int device; ConvGeom g; int2* tab; };
-static std::vector<TableEntry> g_tables;
-
-static bla_status get_table(hipStream_t s, const ConvGeom& g, const int2** out) {
+// One cache entry: the device, the geometry fields its tables depend on, up to five tables.  A caller gets a copy (the vector may grow under another caller).
+struct CachedTables { int device, key[7]; int2* tab[5]; };
+// build(tab): allocate the tables and launch their fills on ctx().stream
+template <class Build>
+static bla_status cached_tables(std::vector<CachedTables>& cache, hipStream_t s, const CachedTables& want, Build build, CachedTables* out) {
 	std::lock_guard<std::mutex> lk(g_table_mu);
 	const int dev = ctx().device;
-	for (const TableEntry& e : g_tables) {
-		const ConvGeom& t = e.g;
-		if (e.device == dev && t.h == g.h && t.w == g.w && t.k == g.k && t.c == g.c && t.s == g.s && t.pt == g.pt && t.pl == g.pl) { *out = e.tab; return BLA_OK; }
-	}
+	for (const CachedTables& e : cache)
+		if (e.device == dev && std::equal(e.key, e.key + 7, want.key)) { *out = e; return BLA_OK; }
 	bla_status st = table_build_allowed(s);
 	if (st) return st;
-	int n = g.c * g.k * g.k;
-	int2* tab;
-	BLA_HIP(hipMalloc((void**)&tab, (size_t)n * sizeof(int2)));
-	hipLaunchKernelGGL(conv_table_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx().stream, tab, g);
+	CachedTables n = want;
+	n.device = dev;
+	st = build(n.tab);
+	if (st) return st;
 	BLA_HIP(hipGetLastError());
 	BLA_HIP(hipStreamSynchronize(ctx().stream));
-	g_tables.push_back(TableEntry{dev, g, tab});
-	*out = tab;
+	cache.push_back(n);
+	*out = n;
 	return BLA_OK;
+}
+
+static std::vector<CachedTables> g_tables, g_ptables, g_padded, g_parity;
+
+static bla_status get_table(hipStream_t s, const ConvGeom& g, const int2** out) {
+	CachedTables t;
+	const bla_status st = cached_tables(g_tables, s, CachedTables{0, {g.h, g.w, g.k, g.c, g.s, g.pt, g.pl}, {}}, [&](int2** tab) -> bla_status {
+		const int n = g.c * g.k * g.k;
+		BLA_HIP(hipMalloc((void**)&tab[0], (size_t)n * sizeof(int2)));
+		hipLaunchKernelGGL(conv_table_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx().stream, tab[0], g);
+		return BLA_OK;
+	}, &t);
+	if (!st) *out = t.tab[0];
+	return st;
 }
 
 // per-geometry table of the output pixels: r = i*Wo + j -> {(i*s)*W + j*s, (i*s) | (j*s) << 16}
@@ -764,25 +778,16 @@ __global__ void __launch_bounds__(256) conv_pixel_table_kernel(int2* tab, ConvGe
 	tab[r] = make_int2(i * g.s * g.w + j * g.s, ((i * g.s) & 0xffff) | ((j * g.s) << 16));
 }
 
-struct PixelTableEntry { int device, w, s, ho, wo; int2* tab; };
-static std::vector<PixelTableEntry> g_ptables;
-
 static bla_status get_pixel_table(hipStream_t s, const ConvGeom& g, const int2** out) {
-	std::lock_guard<std::mutex> lk(g_table_mu);
-	const int dev = ctx().device;
-	for (const PixelTableEntry& t : g_ptables)
-		if (t.device == dev && t.w == g.w && t.s == g.s && t.ho == g.ho && t.wo == g.wo) { *out = t.tab; return BLA_OK; }
-	bla_status st = table_build_allowed(s);
-	if (st) return st;
-	int n = g.ho * g.wo;
-	int2* tab;
-	BLA_HIP(hipMalloc((void**)&tab, (size_t)n * sizeof(int2)));
-	hipLaunchKernelGGL(conv_pixel_table_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx().stream, tab, g);
-	BLA_HIP(hipGetLastError());
-	BLA_HIP(hipStreamSynchronize(ctx().stream));
-	g_ptables.push_back(PixelTableEntry{dev, g.w, g.s, g.ho, g.wo, tab});
-	*out = tab;
-	return BLA_OK;
+	CachedTables t;
+	const bla_status st = cached_tables(g_ptables, s, CachedTables{0, {g.w, g.s, g.ho, g.wo}, {}}, [&](int2** tab) -> bla_status {
+		const int n = g.ho * g.wo;
+		BLA_HIP(hipMalloc((void**)&tab[0], (size_t)n * sizeof(int2)));
+		hipLaunchKernelGGL(conv_pixel_table_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx().stream, tab[0], g);
+		return BLA_OK;
+	}, &t);
+	if (!st) *out = t.tab[0];
+	return st;
 }
 
 // ---- tiled gather on a zero-padded, stride-split copy -------------------------------------------------------------------------
@@ -837,30 +842,18 @@ static PaddedGeom padded_geom(const ConvGeom& g) {
 	pg.plane_floats = (size_t)g.s * g.s * pg.hh * pg.wh;
 	return pg;
 }
-struct PaddedTables { int device; ConvGeom g; int2* taps; int2* pix; };
-static std::vector<PaddedTables> g_padded;
-
 static bla_status get_padded_tables(hipStream_t s, const ConvGeom& g, const int2** taps, const int2** pix) {
-	std::lock_guard<std::mutex> lk(g_table_mu);
-	const int dev = ctx().device;
-	for (const PaddedTables& e : g_padded) {
-		const ConvGeom& t = e.g;
-		if (e.device == dev && t.k == g.k && t.c == g.c && t.s == g.s && t.ho == g.ho && t.wo == g.wo) { *taps = e.taps; *pix = e.pix; return BLA_OK; }
-	}
-	bla_status st = table_build_allowed(s);
-	if (st) return st;
-	const PaddedGeom pg = padded_geom(g);
-	int nt = g.c * g.k * g.k, np = g.ho * g.wo;
-	int2 *t, *q;
-	BLA_HIP(hipMalloc((void**)&t, (size_t)nt * sizeof(int2)));
-	BLA_HIP(hipMalloc((void**)&q, (size_t)np * sizeof(int2)));
-	int n = nt > np ? nt : np;
-	hipLaunchKernelGGL(padded_tables_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx().stream, t, q, g.c, g.k, g.s, pg.hh, pg.wh, g.ho, g.wo);
-	BLA_HIP(hipGetLastError());
-	BLA_HIP(hipStreamSynchronize(ctx().stream));
-	g_padded.push_back(PaddedTables{dev, g, t, q});
-	*taps = t; *pix = q;
-	return BLA_OK;
+	CachedTables t;
+	const bla_status st = cached_tables(g_padded, s, CachedTables{0, {g.k, g.c, g.s, g.ho, g.wo}, {}}, [&](int2** tab) -> bla_status {
+		const PaddedGeom pg = padded_geom(g);
+		const int nt = g.c * g.k * g.k, np = g.ho * g.wo, n = nt > np ? nt : np;
+		BLA_HIP(hipMalloc((void**)&tab[0], (size_t)nt * sizeof(int2)));
+		BLA_HIP(hipMalloc((void**)&tab[1], (size_t)np * sizeof(int2)));
+		hipLaunchKernelGGL(padded_tables_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx().stream, tab[0], tab[1], g.c, g.k, g.s, pg.hh, pg.wh, g.ho, g.wo);
+		return BLA_OK;
+	}, &t);
+	if (!st) { *taps = t.tab[0]; *pix = t.tab[1]; }
+	return st;
 }
 
 // A batch large enough to fill the chip with 128x128 tiles goes to the LDS-tiled gather kernel (bla_gemm.hip: same pipeline as the
@@ -942,9 +935,44 @@ static bla_status plan_wsk_gather(ConvArgs& a, int batch, size_t* slab_bytes, di
 	return BLA_OK;
 }
 
+// The gathered product of a tiled pass: the forward (mode 1 checked, 3 on the padded copy, 7 the image window) or the weight gradient (mode 2 checked, 4 the
+// transposed product on the padded copy); taps / pix: a.tab and the pixel table (modes 1, 2) or the padded copy's tables (3, 4); A as a holds it
+static GatherProduct gather_product(const ConvArgs& a, int mode, const float* img, const int2* taps, const int2* pix) {
+	const bool padded = mode == 3 || mode == 4;
+	const PaddedGeom pg = padded_geom(a.g);
+	GatherProduct p = {};
+	p.mode = mode; p.A = a.A; p.lda = a.lda; p.C = a.out; p.ldc = a.ldo; p.img = img;
+	if (mode == 2 || mode == 4) {   // contraction over (image, output pixel); A = del_y [image][M][HWo]; mode 4: taps are the rows
+		p.M = mode == 4 ? a.N : a.M; p.N = mode == 4 ? a.M : a.N; p.K = a.K * a.batch; p.HWo = a.K; p.ktab = pix; p.ntab = taps;
+		if (mode == 4) p.wo = a.g.wo;
+	} else {                        // columns = (image, output pixel), contraction over the taps
+		p.M = a.M; p.N = a.N * a.batch; p.K = a.K; p.HWo = a.N; p.ktab = taps; p.ntab = pix;
+	}
+	p.H = padded ? pg.hh : a.g.h; p.W = padded ? pg.wh : a.g.w;
+	p.img_stride = padded ? (int)(a.g.c * pg.plane_floats) : (int)a.img_stride;
+	if (a.ep_fused_tiled) p.ep = GatherEpilogue{a.ep_bias, a.ep_bias_stride, a.ep_add, a.ep_out2};
+	return p;
+}
+
+// The zero-padded copy a padded-copy product (modes 3, 4) gathers from, one of three: the caller's (a.padded_src, written by the producer of the image), the
+// image itself where it is its own padded copy (a 1x1 kernel at stride 1 on rows of whole float4: no halo, no row padding), or a copy laid out and filled
+// here in `room`: padded_room(a) floats of the caller's workspace
+static const float* ready_padded(const ConvArgs& a) {
+	if (a.padded_src) return a.padded_src;
+	return a.g.k == 1 && a.g.s == 1 && a.g.w % 4 == 0 && (uintptr_t)a.img % 16 == 0 ? a.img : nullptr;
+}
+static size_t padded_room(const ConvArgs& a) { return ready_padded(a) ? 0 : (size_t)a.batch * a.g.c * padded_geom(a.g).plane_floats; }
+static const float* padded_operand(hipStream_t s, const ConvArgs& a, float* room) {
+	if (const float* ready = ready_padded(a)) return ready;
+	const PaddedGeom pg = padded_geom(a.g);
+	launch_pad_split(s, a.img, room, (unsigned)(a.batch * a.g.c), a.g.h, a.g.w, a.g.pt, a.g.pl, a.g.s, (unsigned)pg.hh, (unsigned)pg.wh);
+	return room;
+}
+
+// one product of a convolution as the *_product constructors below made it (batch, strides and padded copy set)
 template <int MODE>
-static bla_status launch_implicit(hipStream_t s, ConvArgs& a, int batch = 1, size_t img_stride = 0, size_t out_stride = 0, size_t a_stride = 0) {
-	a.batch = batch; a.img_stride = img_stride; a.out_stride = out_stride; a.a_stride = a_stride;
+static bla_status launch_implicit(hipStream_t s, ConvArgs& a) {
+	const int batch = a.batch;
 	const FwdPlan plan = MODE == CONV_FWD ? plan_forward(a, batch) : FwdPlan{FWD_WSK, false};
 	// ep_fused_tiled is conv2d_forward's word that the tile store applies the adds: it took that from the same plan (no second copy of the predicate)
 	BLA_REQUIRE(!a.ep_fused_tiled || (plan.fuses_epilogue && plan.path != FWD_WSK), BLA_ERR_INVALID, "internal: a fused epilogue was planned for a path that has none");
@@ -960,65 +988,33 @@ static bla_status launch_implicit(hipStream_t s, ConvArgs& a, int batch = 1, siz
 			BLA_HIP(hipGetLastError());
 			ordered = (const float*)ws;
 		}
-		const GatherEpilogue gep = {a.ep_bias, a.ep_bias_stride, a.ep_add, a.ep_out2};
-		return gather_gemm(s, 7, batch, a.M, a.N * batch, a.K, ordered, a.K, a.out, a.ldo, a.img, nullptr, nullptr, a.g.h, a.g.w, a.N, (int)img_stride,
-		                   a.ep_fused_tiled ? &gep : nullptr);
+		GatherProduct g = gather_product(a, 7, a.img, nullptr, nullptr);
+		g.A = ordered;
+		return gather_gemm(s, g, batch);
 	}
 	if (MODE == CONV_FWD ? plan.path != FWD_WSK : use_tiled_gather(a, batch, 2)) {
 		const int2* ptab;
 		bla_status st = get_pixel_table(s, a.g, &ptab);
 		if (st) return st;
 		// (the padded-copy kernels address the copy with 32-bit byte offsets: at most 2 GiB of it, and of del_y)
-		const PaddedGeom pg = padded_geom(a.g);
-		const size_t copy_floats = (size_t)batch * a.g.c * pg.plane_floats;
-		const bool fits32 = copy_floats < ((size_t)1 << 29) && (long)batch * a.M * a.g.ho * a.g.wo < (1L << 29);
-		if (MODE == CONV_FWD && plan.path == FWD_TILED_PADDED) {
-			// pad (and split by stride parity) once, then the B slab is fetched with the same 16-byte DMA as a dense operand
-			const int splits3 = gather3_splits(a.M, a.N * batch, a.K);
-			const size_t slab_bytes = splits3 > 1 ? ((size_t)splits3 * a.M * a.N * batch * sizeof(float) + 255) / 256 * 256 : 0;
-			void* ws;
-			// (a 1x1 kernel on rows of whole float4 has no halo and no row padding: the image IS its padded copy)
-			const float* ready = a.padded_src ? a.padded_src : (a.g.k == 1 && a.g.s == 1 && a.g.w % 4 == 0 && (uintptr_t)a.img % 16 == 0 ? a.img : nullptr);
-			st = ensure_workspace(slab_bytes + (ready ? 0 : copy_floats * sizeof(float)) + 64, &ws);   // [slabs][padded copy]
-			if (st) return st;
-			const float* padded = ready;
-			const int2 *taps, *pix;
-			st = get_padded_tables(s, a.g, &taps, &pix);
-			if (st) return st;
-			if (!padded) {
-				float* mine = (float*)((char*)ws + slab_bytes);
-				launch_pad_split(s, a.img, mine, (unsigned)(batch * a.g.c), a.g.h, a.g.w, a.g.pt, a.g.pl, a.g.s, (unsigned)pg.hh, (unsigned)pg.wh);
-				BLA_HIP(hipGetLastError());
-				padded = mine;
-			}
-			const GatherEpilogue gep = {a.ep_bias, a.ep_bias_stride, a.ep_add, a.ep_out2};
-			return gather_gemm(s, 3, batch, a.M, a.N * batch, a.K, a.A, a.lda, a.out, a.ldo, padded, taps, pix, pg.hh, pg.wh, a.N, (int)(a.g.c * pg.plane_floats),
-			                   a.ep_fused_tiled ? &gep : nullptr);
-		}
-		if (MODE == CONV_FWD)   // columns = (image, output pixel), contraction over the taps
-			return gather_gemm(s, 1, batch, a.M, a.N * batch, a.K, a.A, a.lda, a.out, a.ldo, a.img, a.tab, ptab, a.g.h, a.g.w, a.N, (int)img_stride);
-		if (MODE == CONV_WGRAD && fits32 && a.g.wo % 4 == 0 && a.N % 4 == 0) {
-			// transposed product on the padded copy -- taps are the rows, both operands stream in 16-byte chunks
-			const size_t slab_bytes = ((size_t)gather_gemm_splits(4, batch, a.N, a.M, a.K) * a.M * a.N * sizeof(float) + 255) / 256 * 256;
-			void* ws;
-			// (a 1x1 kernel on rows of whole float4 has no halo and no row padding: the image IS its padded copy)
-			const float* ready = a.padded_src ? a.padded_src : (a.g.k == 1 && a.g.s == 1 && a.g.w % 4 == 0 && (uintptr_t)a.img % 16 == 0 ? a.img : nullptr);
-			st = ensure_workspace(slab_bytes + (ready ? 0 : copy_floats * sizeof(float)) + 64, &ws);   // [slabs][padded copy]
-			if (st) return st;
-			const float* padded = ready;
-			const int2 *taps, *pix;
-			st = get_padded_tables(s, a.g, &taps, &pix);
-			if (st) return st;
-			if (!padded) {
-				float* mine = (float*)((char*)ws + slab_bytes);
-				launch_pad_split(s, a.img, mine, (unsigned)(batch * a.g.c), a.g.h, a.g.w, a.g.pt, a.g.pl, a.g.s, (unsigned)pg.hh, (unsigned)pg.wh);
-				BLA_HIP(hipGetLastError());
-				padded = mine;
-			}
-			return gather_gemm(s, 4, batch, a.N, a.M, a.K * batch, a.A, a.lda, a.out, a.ldo, padded, pix, taps, pg.hh, pg.wh, a.K, (int)(a.g.c * pg.plane_floats), nullptr, a.g.wo);
-		}
-		// weight gradient: columns = taps, contraction over (image, output pixel); A = del_y [image][M][HWo]
-		return gather_gemm(s, 2, batch, a.M, a.N, a.K * batch, a.A, a.lda, a.out, a.ldo, a.img, ptab, a.tab, a.g.h, a.g.w, a.K, (int)img_stride);
+		const bool fits32 = (size_t)batch * a.g.c * padded_geom(a.g).plane_floats < ((size_t)1 << 29) && (long)batch * a.M * a.g.ho * a.g.wo < (1L << 29);
+		// forward: pad (and split by stride parity) once, then the B slab is fetched with the same 16-byte DMA as a dense operand; weight gradient: the
+		// transposed product on the padded copy -- taps are the rows, both operands stream in 16-byte chunks.  Else the bounds-checked gather.
+		const int mode = MODE == CONV_FWD ? (plan.path == FWD_TILED_PADDED ? 3 : 1) : (fits32 && a.g.wo % 4 == 0 && a.N % 4 == 0 ? 4 : 2);
+		if (mode == 1 || mode == 2) return gather_gemm(s, gather_product(a, mode, a.img, a.tab, ptab), batch);
+		const int2 *taps, *pix;
+		st = get_padded_tables(s, a.g, &taps, &pix);
+		if (st) return st;
+		GatherProduct g = gather_product(a, mode, nullptr, taps, pix);
+		// one request for [slabs][padded copy]; the weight gradient keeps room for one slab even where its contraction is not cut
+		const size_t slab_floats = std::max(gather_product_slab_floats(g, batch), mode == 4 ? (size_t)g.M * g.N : 0);
+		const size_t slab_bytes = (slab_floats * sizeof(float) + 255) / 256 * 256;
+		void* ws;
+		st = ensure_workspace(slab_bytes + padded_room(a) * sizeof(float) + 64, &ws);
+		if (st) return st;
+		g.img = padded_operand(s, a, (float*)((char*)ws + slab_bytes));
+		BLA_HIP(hipGetLastError());
+		return gather_gemm(s, g, batch);
 	}
 	size_t slab_bytes;
 	dim3 grid;
@@ -1040,14 +1036,21 @@ static bla_status launch_implicit(hipStream_t s, ConvArgs& a, int batch = 1, siz
 	return BLA_OK;
 }
 
-// Weight gradient (w: WGRAD on the forward input) and data gradient (d: FWD on del_y with the flipped kernels) of one convolution
-// as one gather launch + one fold launch; only for shapes that stay on the 32x32 kernel (a single image, a small batch).
-static bla_status launch_backward_pair(hipStream_t s, ConvArgs& w, ConvArgs& d, int batch) {
+// Weight gradient (w: WGRAD on the forward input) and data gradient (d: FWD on del_y with the flipped kernels, made here in d.A = scratch) of one
+// convolution as one gather launch + one fold launch; only for shapes that stay on the 32x32 kernel (a single image, a small batch).
+static bla_status launch_backward_pair(hipStream_t s, ConvArgs& w, ConvArgs& d, const float* kern, float* scratch) {
+	const int batch = w.batch;
+	bla_status st = get_table(s, w.g, &w.tab);
+	if (st) return st;
+	st = get_table(s, d.g, &d.tab);
+	if (st) return st;
+	hipLaunchKernelGGL(flip_kernels_kernel, dim3(grid_for((size_t)d.M * d.K)), dim3(kThreads), 0, s, kern, scratch, d.g.c, d.M, d.g.k);
+	BLA_HIP(hipGetLastError());
 	size_t bytes_w, bytes_d;
 	dim3 gw, gd;
 	bool vw, vd;
 	const int target = 384;   // workgroups per product: the two share the chip (768 for a product launched alone); measured 128 ... 768
-	bla_status st = plan_wsk_gather<CONV_WGRAD>(w, batch, &bytes_w, &gw, &vw, target);
+	st = plan_wsk_gather<CONV_WGRAD>(w, batch, &bytes_w, &gw, &vw, target);
 	if (st) return st;
 	st = plan_wsk_gather<CONV_FWD>(d, batch, &bytes_d, &gd, &vd, target);
 	if (st) return st;
@@ -1073,6 +1076,94 @@ static bla_status launch_backward_pair(hipStream_t s, ConvArgs& w, ConvArgs& d, 
 	}
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
+}
+
+// The three products of one convolution over a batch -- x [B][C][H][W], kernels [F][C][k][k], del_y [B][F][Ho][Wo] -- as launch_implicit, the pair launches
+// and conv_kernel_prep_mode take them (the tap table a.tab is fetched by the caller, where a launch needs it)
+static ConvArgs fwd_product(const float* x, const float* kern, float* out, const float* x_padded, int batch, int h, int w, int k, int c_in, int f_n, int stride) {
+	const Geometry gm = same_geometry(h, w, k, stride);
+	ConvArgs a = {};
+	a.g = ConvGeom{h, w, k, c_in, stride, gm.ho, gm.wo, gm.pt, gm.pl};
+	a.A = kern; a.lda = k * k * c_in; a.img = x; a.out = out; a.ldo = gm.ho * gm.wo;
+	a.M = f_n; a.N = gm.ho * gm.wo; a.K = k * k * c_in;
+	a.batch = batch; a.img_stride = (size_t)c_in * h * w; a.out_stride = (size_t)f_n * gm.ho * gm.wo;
+	a.padded_src = x_padded;
+	return a;
+}
+// dkern [F][C*k*k] = del_y [F][HWo] . patches^T, summed over the images
+static ConvArgs wgrad_product(const float* del_y, const float* x, float* del_kern, const float* x_padded, int batch, int h, int w, int k, int c_in, int f_n, int stride) {
+	const Geometry gm = same_geometry(h, w, k, stride);
+	ConvArgs a = {};
+	a.g = ConvGeom{h, w, k, c_in, stride, gm.ho, gm.wo, gm.pt, gm.pl};
+	a.A = del_y; a.lda = gm.ho * gm.wo; a.img = x; a.out = del_kern; a.ldo = k * k * c_in;
+	a.M = f_n; a.N = k * k * c_in; a.K = gm.ho * gm.wo;
+	a.batch = batch; a.img_stride = (size_t)c_in * h * w; a.a_stride = (size_t)f_n * gm.ho * gm.wo;
+	a.padded_src = x_padded;
+	return a;
+}
+// del_x = the stride-1 forward over dy with the kernels flipped and transposed (kt [C][F][k][k]) and the pads mirrored (k-1-pt, k-1-pl): image = del_y,
+// "input channels" = F.  At stride s > 1 dy is del_y with s-1 zeros put between its pixels, [F][(Ho-1)s+1][(Wo-1)s+1] (the caller dilates into it).
+// dy_padded: del_y's padded copy, taken for odd k at stride 1 (the mirrored pads are the forward's: the copy has conv_padded_layout(h, w, k, 1))
+static ConvArgs dgrad_product(const float* dy, const float* kt, float* del_x, const float* dy_padded, int batch, int h, int w, int k, int c_in, int f_n, int stride) {
+	const Geometry gm = same_geometry(h, w, k, stride);
+	const int hd = (gm.ho - 1) * stride + 1, wd = (gm.wo - 1) * stride + 1;
+	ConvArgs a = {};
+	a.g = ConvGeom{hd, wd, k, f_n, 1, h, w, k - 1 - gm.pt, k - 1 - gm.pl};
+	a.A = kt; a.lda = k * k * f_n; a.img = dy; a.out = del_x; a.ldo = h * w;
+	a.M = c_in; a.N = h * w; a.K = k * k * f_n;
+	a.batch = batch; a.img_stride = (size_t)f_n * hd * wd; a.out_stride = (size_t)c_in * h * w;
+	if (stride == 1 && k % 2 == 1) a.padded_src = dy_padded;
+	return a;
+}
+
+// How conv2d_backward runs both gradients of a stride-1 convolution (aw, ad: wgrad_product / dgrad_product), decided in ONE place: conv2d_backward follows
+// it, conv_kernel_prep_mode asks it which kernel-matrix form the data gradient will read.
+enum BwdPath { BWD_EACH = 0, BWD_WSK_PAIR = 1, BWD_TILED_PAIR = 2 };
+static BwdPath plan_backward(const ConvArgs& aw, const ConvArgs& ad, int batch) {
+	// both on the latency-bound kernel: one gather launch and one fold launch for the two (launch_backward_pair)
+	if (!use_tiled_gather(aw, batch, 2) && !use_tiled_gather(ad, batch, 1)) return BWD_WSK_PAIR;
+	// both on the tiled gather kernels (a batch that fills the chip): ONE launch for the two products -- the data gradient's workgroups move in as the weight
+	// gradient's finish, each product's prologue / drain / tail under the other's body (gather_pair_kernel).  BLA_CONV_PAIR=0: one launch each.
+	static const bool pair_on = [] { const char* e = getenv("BLA_CONV_PAIR"); return !(e && e[0] == '0'); }();
+	static const long pair_max_cols = [] { const char* e = getenv("BLA_CONV_PAIR_COLS"); return e && *e ? atol(e) : 2048L; }();
+	const bool fits_w = (size_t)batch * aw.g.c * padded_geom(aw.g).plane_floats < ((size_t)1 << 29) && (long)batch * aw.M * aw.g.ho * aw.g.wo < (1L << 29);
+	const FwdPath dpath = plan_forward(ad, batch).path;
+	if (pair_on && (long)ad.N * batch <= pair_max_cols && use_tiled_gather(aw, batch, 2) && fits_w && (aw.g.wo == 4 || aw.g.wo == 8 || aw.g.wo % 16 == 0) && aw.N % 4 == 0 &&
+	    gather_pair_fits(4, aw.N, aw.M) && (dpath == FWD_TILED_WINDOW || (dpath == FWD_TILED_PADDED && gather_pair_fits(3, ad.M, ad.N * batch))))
+		return BWD_TILED_PAIR;
+	return BWD_EACH;
+}
+
+// BWD_TILED_PAIR: the two products as launch_implicit builds them (mode 4; mode 7 or 3) in one gather_pair_kernel launch.  One workspace:
+// [weight-gradient slabs][data-gradient slabs][padded x][padded del_y][kernel matrix in the data gradient's form], each only where needed.
+static bla_status launch_tiled_pair(hipStream_t s, const ConvArgs& aw, const ConvArgs& ad, const float* d_kern, float* d_scratch, const float* prepared) {
+	const int batch = aw.batch;
+	const bool window = plan_forward(ad, batch).path == FWD_TILED_WINDOW;
+	const int2 *taps_w, *pix_w, *taps_d = nullptr, *pix_d = nullptr;
+	bla_status st = get_padded_tables(s, aw.g, &taps_w, &pix_w);
+	if (st) return st;
+	if (!window) { st = get_padded_tables(s, ad.g, &taps_d, &pix_d); if (st) return st; }
+	GatherProduct gw = gather_product(aw, 4, nullptr, taps_w, pix_w);
+	GatherProduct gd = gather_product(ad, window ? 7 : 3, window ? ad.img : nullptr, taps_d, pix_d);
+	auto up = [](size_t floats) { return (floats + 63) / 64 * 64; };
+	const size_t slab_w = up(gather_product_slab_floats(gw, batch)), slab_d = up(gather_product_slab_floats(gd, batch));
+	const size_t pad_w = up(padded_room(aw)), pad_d = window ? 0 : up(padded_room(ad)), kern_f = !prepared && window ? up((size_t)ad.M * ad.K) : 0;
+	void* ws;
+	st = ensure_workspace((slab_w + slab_d + pad_w + pad_d + kern_f) * sizeof(float) + 64, &ws);
+	if (st) return st;
+	float *w_slab = (float*)ws, *d_slab = w_slab + slab_w, *w_pad = d_slab + slab_d, *d_pad = w_pad + pad_w, *kbuf = d_pad + pad_d;
+	gw.img = padded_operand(s, aw, w_pad);
+	if (!window) gd.img = padded_operand(s, ad, d_pad);
+	if (prepared) gd.A = prepared;      // (conv_kernel_prep_mode 2 / 3: flipped, and window-ordered where the window kernel runs)
+	else if (window) {
+		hipLaunchKernelGGL(window_order_flipped_kernel, dim3(grid_for((size_t)ad.M * ad.K)), dim3(kThreads), 0, s, d_kern, kbuf, ad.M, ad.g.c);
+		gd.A = kbuf;
+	} else {
+		hipLaunchKernelGGL(flip_kernels_kernel, dim3(grid_for((size_t)ad.M * ad.K)), dim3(kThreads), 0, s, d_kern, d_scratch, ad.g.c, ad.M, ad.g.k);
+		gd.A = d_scratch;
+	}
+	BLA_HIP(hipGetLastError());
+	return gather_pair_products(s, batch, gw, w_slab, gd, d_slab);
 }
 
 template <bool RELU>
@@ -1303,20 +1394,16 @@ static bla_status conv2d_forward(void* stream, const float* d_x, const float* d_
 	Geometry gm = same_geometry(h, w, k, stride);
 	BLA_REQUIRE((ep_add == nullptr) == (ep_out2 == nullptr), BLA_ERR_INVALID, "ep_add and ep_out2 go together");
 	if (thin_conv_applies(k, c_in, f_n, stride)) return thin_conv_forward(s, d_x, d_kern, d_out, batch, h, w, k, c_in, f_n, gm.pt, gm.pl, ep_bias, ep_bias_stride, ep_add, ep_out2);
-	ConvArgs a;
-	a.g = ConvGeom{h, w, k, c_in, stride, gm.ho, gm.wo, gm.pt, gm.pl};
+	ConvArgs a = fwd_product(d_x, d_kern, d_out, x_padded, batch, h, w, k, c_in, f_n, stride);
 	st = get_table(s, a.g, &a.tab);
 	if (st) return st;
-	a.A = d_kern; a.lda = k * k * c_in; a.img = d_x; a.out = d_out; a.ldo = gm.ho * gm.wo;
-	a.M = f_n; a.N = gm.ho * gm.wo; a.K = k * k * c_in;
-	a.padded_src = x_padded;
 	const bool ep = ep_bias || ep_out2;
-	if (prepared && plan_forward(a, batch).path == FWD_TILED_WINDOW) a.prepared_A = prepared;   // (mode 1 of conv_kernel_prep_mode: the only prepared form a forward pass takes)
 	const FwdPlan plan = plan_forward(a, batch);
+	if (prepared && plan.path == FWD_TILED_WINDOW) a.prepared_A = prepared;   // (mode 1 of conv_kernel_prep_mode: the only prepared form a forward pass takes)
 	if (ep && !plan.fuses_epilogue) {
 		// the half-slab forward kernels apply the adds where they store their tiles (one pass over K, whole tiles) and the 32x32 kernel does for a single
 		// image; the other kernels carry no epilogue (the 32x32 kernel's knows one bias set): one pass behind them
-		st = launch_implicit<CONV_FWD>(s, a, batch, (size_t)c_in * h * w, (size_t)f_n * gm.ho * gm.wo, 0);
+		st = launch_implicit<CONV_FWD>(s, a);
 		if (st) return st;
 		const size_t total = (size_t)batch * f_n * a.N;
 		hipLaunchKernelGGL(conv_epilogue_kernel, dim3(grid_for(total)), dim3(kThreads), 0, s, d_out, ep_bias, ep_bias_stride, ep_add, ep_out2, f_n, a.N, total);
@@ -1325,7 +1412,7 @@ static bla_status conv2d_forward(void* stream, const float* d_x, const float* d_
 	}
 	a.ep_bias = ep_bias; a.ep_bias_stride = ep_bias_stride; a.ep_add = ep_add; a.ep_out2 = ep_out2;
 	a.ep_fused_tiled = ep && plan.path != FWD_WSK;
-	return launch_implicit<CONV_FWD>(s, a, batch, (size_t)c_in * h * w, (size_t)f_n * gm.ho * gm.wo, 0);
+	return launch_implicit<CONV_FWD>(s, a);
 }
 
 
@@ -1378,9 +1465,6 @@ __global__ void __launch_bounds__(kThreads) parity_interleave_kernel(const float
 		*reinterpret_cast<float2*>(out + (pc * h + y) * w + 2 * v) = o;
 	}
 }
-struct ParityTables { int device, f_n, k, pt, pl, ho, wo; int2* taps[4]; int2* pix; };
-static std::vector<ParityTables> g_parity;
-
 static bool parity_dgrad_applies(int batch, int h, int w, int k, int c_in, int f_n, int stride, const Geometry& gm) {
 	static const bool off = [] { const char* e = getenv("BLA_CONV_PARITY"); return e && e[0] == '0'; }();
 	if (off || stride != 2 || h % 2 || w % 8 || k > 4 || f_n % 16 || c_in % 128 || ((long)batch * (h / 2) * (w / 2)) % 128) return false;
@@ -1402,34 +1486,20 @@ static bla_status conv2d_backward_parity(hipStream_t s, const float* d_del_y, co
 	for (int r = 0; r < 2; r++)
 		for (int i = 0; i < 4; i++) { if (i < P[r].n && P[r].d[i] > dpmax) dpmax = P[r].d[i]; if (i < Q[r].n && Q[r].d[i] > dqmax) dqmax = Q[r].d[i]; }
 	const int hh = gm.ho + dpmax, wh = (gm.wo + dqmax + 3) / 4 * 4;
-	// tables, once per geometry and device
-	ParityTables t;   // (a copy: the cache vector may grow under another caller once the lock is released)
-	{
-		const ParityTables* tb = nullptr;
-		std::lock_guard<std::mutex> lk(g_table_mu);
-		const int dev = ctx().device;
-		for (const ParityTables& e : g_parity)
-			if (e.device == dev && e.f_n == f_n && e.k == k && e.pt == gm.pt && e.pl == gm.pl && e.ho == gm.ho && e.wo == gm.wo) { tb = &e; break; }
-		if (!tb) {
-			bla_status st = table_build_allowed(s);
-			if (st) return st;
-			ParityTables n = {dev, f_n, k, gm.pt, gm.pl, gm.ho, gm.wo, {nullptr, nullptr, nullptr, nullptr}, nullptr};
-			BLA_HIP(hipMalloc((void**)&n.pix, (size_t)hc * wc * sizeof(int2)));
-			for (int cls = 0; cls < 4; cls++) {
-				const ParityTaps& p = P[cls >> 1]; const ParityTaps& q = Q[cls & 1];
-				const int nt = f_n * p.n * q.n;
-				BLA_HIP(hipMalloc((void**)&n.taps[cls], (size_t)nt * sizeof(int2)));
-				const int cnt = nt > hc * wc ? nt : hc * wc;
-				hipLaunchKernelGGL(parity_tables_kernel, dim3((cnt + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx().stream, n.taps[cls], n.pix, f_n, p, q, dpmax, dqmax, hh,
-				                   wh, hc, wc);
-				BLA_HIP(hipGetLastError());
-			}
-			BLA_HIP(hipStreamSynchronize(ctx().stream));
-			g_parity.push_back(n);
-			tb = &g_parity.back();
+	// tables, once per geometry and device: tab[0..3] the classes' taps, tab[4] the pixels
+	CachedTables t;
+	bla_status st = cached_tables(g_parity, s, CachedTables{0, {f_n, k, gm.pt, gm.pl, gm.ho, gm.wo}, {}}, [&](int2** tab) -> bla_status {
+		BLA_HIP(hipMalloc((void**)&tab[4], (size_t)hc * wc * sizeof(int2)));
+		for (int cls = 0; cls < 4; cls++) {
+			const ParityTaps& p = P[cls >> 1]; const ParityTaps& q = Q[cls & 1];
+			const int nt = f_n * p.n * q.n, cnt = nt > hc * wc ? nt : hc * wc;
+			BLA_HIP(hipMalloc((void**)&tab[cls], (size_t)nt * sizeof(int2)));
+			hipLaunchKernelGGL(parity_tables_kernel, dim3((cnt + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx().stream, tab[cls], tab[4], f_n, p, q, dpmax, dqmax, hh, wh, hc, wc);
+			BLA_HIP(hipGetLastError());
 		}
-		t = *tb;
-	}
+		return BLA_OK;
+	}, &t);
+	if (st) return st;
 	const int N = batch * hc * wc;
 	size_t slab_bytes = 0;
 	for (int cls = 0; cls < 4; cls++) {
@@ -1439,7 +1509,7 @@ static bla_status conv2d_backward_parity(hipStream_t s, const float* d_del_y, co
 	const size_t copy_floats = (size_t)batch * f_n * hh * wh, cls_floats = (size_t)batch * c_in * hc * wc;
 	BLA_REQUIRE(copy_floats < ((size_t)1 << 29) && cls_floats < ((size_t)1 << 29), BLA_ERR_INVALID, "batch too large for 32-bit gather offsets");
 	void* ws;
-	bla_status st = ensure_workspace(slab_bytes + (copy_floats + 4 * cls_floats) * sizeof(float) + 64 + 256, &ws);   // [slabs][padded del_y][four class planes][class table]
+	st = ensure_workspace(slab_bytes + (copy_floats + 4 * cls_floats) * sizeof(float) + 64 + 256, &ws);   // [slabs][padded del_y][four class planes][class table]
 	if (st) return st;
 	float* padded = (float*)((char*)ws + slab_bytes);
 	float* planes = padded + (copy_floats + 3) / 4 * 4;
@@ -1449,7 +1519,7 @@ static bla_status conv2d_backward_parity(hipStream_t s, const float* d_del_y, co
 	GatherClass gc[4];
 	for (int cls = 0; cls < 4; cls++) {
 		const int kc = f_n * P[cls >> 1].n * Q[cls & 1].n;
-		gc[cls] = GatherClass{d_scratch + a_off, kc, t.taps[cls], planes + (size_t)cls * cls_floats};
+		gc[cls] = GatherClass{d_scratch + a_off, kc, t.tab[cls], planes + (size_t)cls * cls_floats};
 		a_off += (size_t)c_in * kc;
 	}
 	// one launch for the four classes where they fill the chip: longest contraction beside shortest on a CU (the workgroups are dealt in launch order:
@@ -1464,12 +1534,15 @@ static bla_status conv2d_backward_parity(hipStream_t s, const float* d_del_y, co
 	hipLaunchKernelGGL(parity_kernels_kernel, dim3(grid_for((size_t)f_n * c_in * k * k)), dim3(kThreads), 0, s, d_kern, d_scratch, f_n, c_in, k, P[0], P[1], Q[0], Q[1], sorted,
 	                   one_launch ? d_tab : nullptr);
 	BLA_HIP(hipGetLastError());
+	GatherProduct g = {};   // what the classes share: c_in x (image, class pixel) outputs gathered from the padded del_y
+	g.mode = 3; g.M = c_in; g.N = N; g.ldc = hc * wc; g.img = padded; g.ntab = t.tab[4]; g.H = hh; g.W = wh; g.HWo = hc * wc; g.img_stride = f_n * hh * wh;
 	if (one_launch) {
-		st = gather_gemm_classes(s, batch, c_in, N, sorted.c, d_tab, 4, hc * wc, padded, t.pix, hh, wh, hc * wc, f_n * hh * wh);
+		st = gather_gemm_classes(s, g, batch, sorted.c, d_tab, 4);
 		if (st) return st;
 	} else {
 		for (int cls = 0; cls < 4; cls++) {
-			st = gather_gemm(s, 3, batch, c_in, N, gc[cls].K, gc[cls].A, gc[cls].K, gc[cls].C, hc * wc, padded, gc[cls].ktab, t.pix, hh, wh, hc * wc, f_n * hh * wh);
+			g.A = gc[cls].A; g.K = g.lda = gc[cls].K; g.ktab = gc[cls].ktab; g.C = gc[cls].C;
+			st = gather_gemm(s, g, batch);
 			if (st) return st;
 		}
 	}
@@ -1487,7 +1560,6 @@ static bla_status conv2d_backward(void* stream, const float* d_del_y, const floa
 	BLA_REQUIRE(d_del_y, BLA_ERR_INVALID, "null operand");
 	hipStream_t s = pick_stream(stream);
 	Geometry gm = same_geometry(h, w, k, stride);
-	const size_t x_sz = (size_t)c_in * h * w, y_sz = (size_t)f_n * gm.ho * gm.wo;
 	if (thin_conv_applies(k, c_in, f_n, stride)) {
 		// a side of at most four channels: direct kernels (bla_conv_thin.hip); the data gradient is the forward form on del_y with the flipped kernels
 		if (d_del_kern) {
@@ -1503,86 +1575,19 @@ static bla_status conv2d_backward(void* stream, const float* d_del_y, const floa
 		}
 		return BLA_OK;
 	}
+	ConvArgs aw = wgrad_product(d_del_y, d_x, d_del_kern, x_padded, batch, h, w, k, c_in, f_n, stride);
+	ConvArgs ad = dgrad_product(d_del_y, d_scratch, d_del_x, dy_padded, batch, h, w, k, c_in, f_n, stride);
 	if (d_del_kern && d_del_x && stride == 1) {
-		// both gradients, both on the latency-bound kernel: one gather launch and one fold launch for the two
 		BLA_REQUIRE(d_x && d_kern && d_scratch, BLA_ERR_INVALID, "the gradients need the forward input, the kernels and a scratch buffer of F*C*k*k floats");
-		ConvArgs aw, ad;
-		aw.g = ConvGeom{h, w, k, c_in, stride, gm.ho, gm.wo, gm.pt, gm.pl};
-		aw.A = d_del_y; aw.lda = gm.ho * gm.wo; aw.img = d_x; aw.out = d_del_kern; aw.ldo = k * k * c_in;
-		aw.M = f_n; aw.N = k * k * c_in; aw.K = gm.ho * gm.wo;
-		aw.batch = batch; aw.img_stride = x_sz; aw.out_stride = 0; aw.a_stride = y_sz;
-		ad.g = ConvGeom{h, w, k, f_n, 1, h, w, k - 1 - gm.pt, k - 1 - gm.pl};
-		ad.A = d_scratch; ad.lda = k * k * f_n; ad.img = d_del_y; ad.out = d_del_x; ad.ldo = h * w;
-		ad.M = c_in; ad.N = h * w; ad.K = k * k * f_n;
-		ad.batch = batch; ad.img_stride = y_sz; ad.out_stride = x_sz; ad.a_stride = 0;
-		if (!use_tiled_gather(aw, batch, 2) && !use_tiled_gather(ad, batch, 1)) {
-			st = get_table(s, aw.g, &aw.tab);
-			if (st) return st;
-			st = get_table(s, ad.g, &ad.tab);
-			if (st) return st;
-			hipLaunchKernelGGL(flip_kernels_kernel, dim3(grid_for((size_t)f_n * c_in * k * k)), dim3(kThreads), 0, s, d_kern, d_scratch, f_n, c_in, k);
-			BLA_HIP(hipGetLastError());
-			return launch_backward_pair(s, aw, ad, batch);
-		}
-		// both on the tiled gather kernels (a batch that fills the chip): ONE launch for the two products -- the data gradient's workgroups move in as the weight
-		// gradient's finish, each product's prologue / drain / tail under the other's body (gather_pair_kernel).  BLA_CONV_PAIR=0: one launch each.
-		static const bool pair_on = [] { const char* e = getenv("BLA_CONV_PAIR"); return !(e && e[0] == '0'); }();
-		const PaddedGeom pgw = padded_geom(aw.g), pgd = padded_geom(ad.g);
-		const size_t copy_w = (size_t)batch * aw.g.c * pgw.plane_floats, copy_d = (size_t)batch * ad.g.c * pgd.plane_floats;
-		const bool fits_w = copy_w < ((size_t)1 << 29) && (long)batch * aw.M * aw.g.ho * aw.g.wo < (1L << 29);
-		ad.padded_src = k % 2 == 1 ? dy_padded : nullptr;
-		const FwdPath dpath = plan_forward(ad, batch).path;
-		static const long pair_max_cols = [] { const char* e = getenv("BLA_CONV_PAIR_COLS"); return e && *e ? atol(e) : 2048L; }();
-		if (pair_on && (long)ad.N * batch <= pair_max_cols && use_tiled_gather(aw, batch, 2) && fits_w && (aw.g.wo == 4 || aw.g.wo == 8 || aw.g.wo % 16 == 0) && aw.N % 4 == 0 && gather_pair_fits(4, aw.N, aw.M) &&
-		    (dpath == FWD_TILED_WINDOW || (dpath == FWD_TILED_PADDED && gather_pair_fits(3, ad.M, ad.N * batch)))) {
-			const int2 *taps_w, *pix_w, *taps_d = nullptr, *pix_d = nullptr;
-			st = get_padded_tables(s, aw.g, &taps_w, &pix_w);
-			if (st) return st;
-			if (dpath == FWD_TILED_PADDED) { st = get_padded_tables(s, ad.g, &taps_d, &pix_d); if (st) return st; }
-			// the two products as gather_gemm would take them (launch_implicit's weight-gradient and forward branches)
-			GatherProduct gw = {4, aw.N, aw.M, aw.K * batch, aw.A, aw.lda, aw.out, aw.ldo, nullptr, pix_w, taps_w, pgw.hh, pgw.wh, aw.K, (int)(aw.g.c * pgw.plane_floats), GatherEpilogue{}, aw.g.wo};
-			GatherProduct gd = dpath == FWD_TILED_WINDOW
-				? GatherProduct{7, ad.M, ad.N * batch, ad.K, nullptr, ad.K, ad.out, ad.ldo, ad.img, nullptr, nullptr, ad.g.h, ad.g.w, ad.N, (int)y_sz, GatherEpilogue{}}
-				: GatherProduct{3, ad.M, ad.N * batch, ad.K, nullptr, ad.lda, ad.out, ad.ldo, nullptr, taps_d, pix_d, pgd.hh, pgd.wh, ad.N, (int)(ad.g.c * pgd.plane_floats), GatherEpilogue{}};
-			// one workspace: [weight-gradient slabs][data-gradient slabs][padded x][padded del_y][kernel matrix in the data gradient's form], each only where needed
-			const float* xp = x_padded ? x_padded : (aw.g.k == 1 && aw.g.w % 4 == 0 && (uintptr_t)d_x % 16 == 0 ? d_x : nullptr);
-			const float* yp = dpath == FWD_TILED_PADDED ? (ad.padded_src ? ad.padded_src : (ad.g.k == 1 && ad.g.w % 4 == 0 && (uintptr_t)d_del_y % 16 == 0 ? d_del_y : nullptr)) : d_del_y;
-			const bool need_kern = !prepared;
-			auto up = [](size_t floats) { return (floats + 63) / 64 * 64; };
-			const size_t slab_w = up(gather_product_slab_floats(gw, batch)), slab_d = up(gather_product_slab_floats(gd, batch));
-			const size_t pad_w = xp ? 0 : up(copy_w), pad_d = yp ? 0 : up(copy_d), kern_f = need_kern && dpath == FWD_TILED_WINDOW ? up((size_t)ad.M * ad.K) : 0;
-			void* ws;
-			st = ensure_workspace((slab_w + slab_d + pad_w + pad_d + kern_f) * sizeof(float) + 64, &ws);
-			if (st) return st;
-			float* base = (float*)ws;
-			float *w_slab = base, *d_slab = base + slab_w, *w_pad = d_slab + slab_d, *d_pad = w_pad + pad_w, *kbuf = d_pad + pad_d;
-			if (!xp) { launch_pad_split(s, d_x, w_pad, (unsigned)(batch * aw.g.c), aw.g.h, aw.g.w, aw.g.pt, aw.g.pl, 1, (unsigned)pgw.hh, (unsigned)pgw.wh); xp = w_pad; }
-			if (!yp) { launch_pad_split(s, d_del_y, d_pad, (unsigned)(batch * ad.g.c), ad.g.h, ad.g.w, ad.g.pt, ad.g.pl, 1, (unsigned)pgd.hh, (unsigned)pgd.wh); yp = d_pad; }
-			if (prepared) gd.A = prepared;      // (conv_kernel_prep_mode 2 / 3: flipped, and window-ordered where the window kernel runs)
-			else if (dpath == FWD_TILED_WINDOW) {
-				hipLaunchKernelGGL(window_order_flipped_kernel, dim3(grid_for((size_t)ad.M * ad.K)), dim3(kThreads), 0, s, d_kern, kbuf, ad.M, ad.g.c);
-				gd.A = kbuf;
-			} else {
-				hipLaunchKernelGGL(flip_kernels_kernel, dim3(grid_for((size_t)f_n * c_in * k * k)), dim3(kThreads), 0, s, d_kern, d_scratch, f_n, c_in, k);
-				gd.A = d_scratch;
-			}
-			BLA_HIP(hipGetLastError());
-			gw.img = xp;
-			if (dpath == FWD_TILED_PADDED) gd.img = yp;
-			return gather_pair_products(s, batch, gw, w_slab, gd, d_slab);
-		}
-		ad.padded_src = nullptr;
+		const BwdPath path = plan_backward(aw, ad, batch);
+		if (path == BWD_WSK_PAIR) return launch_backward_pair(s, aw, ad, d_kern, d_scratch);
+		if (path == BWD_TILED_PAIR) return launch_tiled_pair(s, aw, ad, d_kern, d_scratch, prepared);
 	}
 	if (d_del_kern) {
 		BLA_REQUIRE(d_x, BLA_ERR_INVALID, "weight gradient needs the forward input");
-		ConvArgs a;
-		a.g = ConvGeom{h, w, k, c_in, stride, gm.ho, gm.wo, gm.pt, gm.pl};
-		st = get_table(s, a.g, &a.tab);
+		st = get_table(s, aw.g, &aw.tab);
 		if (st) return st;
-		a.A = d_del_y; a.lda = gm.ho * gm.wo; a.img = d_x; a.out = d_del_kern; a.ldo = k * k * c_in;
-		a.M = f_n; a.N = k * k * c_in; a.K = gm.ho * gm.wo;
-		a.padded_src = x_padded;
-		st = launch_implicit<CONV_WGRAD>(s, a, batch, x_sz, 0, y_sz);
+		st = launch_implicit<CONV_WGRAD>(s, aw);
 		if (st) return st;
 	}
 	if (d_del_x) {
@@ -1593,35 +1598,25 @@ static bla_status conv2d_backward(void* stream, const float* d_del_y, const floa
 		BLA_REQUIRE(d_kern && d_scratch, BLA_ERR_INVALID, "data gradient needs the kernels and a scratch buffer of F*C*k*k floats");
 		if (parity_dgrad_applies(batch, h, w, k, c_in, f_n, stride, gm)) return conv2d_backward_parity(s, d_del_y, d_kern, d_del_x, d_scratch, batch, h, w, k, c_in, f_n, gm);
 		// Stride s > 1 (the intended adjoint; the reference is undefined there): the same stride-1 convolution over del_y with s-1 zeros
-		// put between its pixels, [F][(Ho-1)s+1][(Wo-1)s+1] -- the U-Net's three down-convolutions (model/cifar_unet.c:1105,1111,1115).
-		const float* src = d_del_y;
-		int hd = h, wd = w;
-		size_t src_sz = y_sz;
+		// put between its pixels (dgrad_product) -- the U-Net's three down-convolutions (model/cifar_unet.c:1105,1111,1115).
 		if (stride != 1) {
-			hd = (gm.ho - 1) * stride + 1; wd = (gm.wo - 1) * stride + 1;
-			src_sz = (size_t)f_n * hd * wd;
 			void* ws;
-			st = ensure_workspace2(src_sz * batch * sizeof(float), &ws);
+			st = ensure_workspace2(ad.img_stride * batch * sizeof(float), &ws);
 			if (st) return st;
-			hipLaunchKernelGGL(dilate_kernel, dim3(grid_for(src_sz * batch)), dim3(kThreads), 0, s, d_del_y, (float*)ws, batch * f_n, gm.ho, gm.wo, stride, hd, wd);
+			hipLaunchKernelGGL(dilate_kernel, dim3(grid_for(ad.img_stride * batch)), dim3(kThreads), 0, s, d_del_y, (float*)ws, batch * f_n, gm.ho, gm.wo, stride, ad.g.h, ad.g.w);
 			BLA_HIP(hipGetLastError());
-			src = (const float*)ws;
+			ad.img = (const float*)ws;
 		}
-		ConvArgs a;   // image = del_y [F][H][W] (or its dilated form), "input channels" = F, pads mirrored: k-1-pt, k-1-pl
-		a.g = ConvGeom{hd, wd, k, f_n, 1, h, w, k - 1 - gm.pt, k - 1 - gm.pl};
-		st = get_table(s, a.g, &a.tab);
+		st = get_table(s, ad.g, &ad.tab);
 		if (st) return st;
-		a.A = d_scratch; a.lda = k * k * f_n; a.img = src; a.out = d_del_x; a.ldo = h * w;
-		a.M = c_in; a.N = h * w; a.K = k * k * f_n;
-		if (stride == 1 && k % 2 == 1) a.padded_src = dy_padded;   // (odd k: the mirrored pads are the forward's, so the copy has conv_padded_layout(h, w, k, 1))
-		const bool window = plan_forward(a, batch).path == FWD_TILED_WINDOW;
-		if (prepared && stride == 1) { if (window) a.prepared_A = prepared; else a.A = prepared; }   // conv_kernel_prep_mode 2 / 3: already flipped (and window-ordered)
-		else if (window) a.flip_src = d_kern;      // flipped and window-ordered in one pass, inside launch_implicit
+		const bool window = plan_forward(ad, batch).path == FWD_TILED_WINDOW;
+		if (prepared && stride == 1) { if (window) ad.prepared_A = prepared; else ad.A = prepared; }   // conv_kernel_prep_mode 2 / 3: already flipped (and window-ordered)
+		else if (window) ad.flip_src = d_kern;      // flipped and window-ordered in one pass, inside launch_implicit
 		else {
 			hipLaunchKernelGGL(flip_kernels_kernel, dim3(grid_for((size_t)f_n * c_in * k * k)), dim3(kThreads), 0, s, d_kern, d_scratch, f_n, c_in, k);
 			BLA_HIP(hipGetLastError());
 		}
-		st = launch_implicit<CONV_FWD>(s, a, batch, src_sz, x_sz, 0);
+		st = launch_implicit<CONV_FWD>(s, ad);
 		if (st) return st;
 	}
 	return BLA_OK;
@@ -1693,26 +1688,15 @@ bla_status conv2d_backward_batched(void* stream, const float* d_del_y, const flo
 	return conv2d_backward(stream, d_del_y, d_x, d_kern, d_del_kern, d_del_x, d_scratch, batch, h, w, k, c_in, f_n, stride, x_padded, prepared, dy_padded);
 }
 // Which prepared form (KernelPrepJob::mode) this convolution's forward / stride-1 data-gradient product reads; the same planning as conv2d_forward /
-// conv2d_backward (a 16-byte aligned kernel matrix is assumed: the U-Net's parameter bucket aligns every tensor)
+// conv2d_backward, on products without operands (null addresses pass the alignment checks: the U-Net's parameter bucket aligns every tensor)
 int conv_kernel_prep_mode(int batch, int h, int w, int k, int c_in, int f_n, int stride, bool data_gradient) {
 	if (batch < 2 || thin_conv_applies(k, c_in, f_n, stride) || !ctx().ready) return 0;
-	const Geometry gm = same_geometry(h, w, k, stride);
-	ConvArgs a;
-	a.A = reinterpret_cast<const float*>(uintptr_t(256));
-	if (!data_gradient) {
-		a.g = ConvGeom{h, w, k, c_in, stride, gm.ho, gm.wo, gm.pt, gm.pl};
-		a.lda = k * k * c_in; a.M = f_n; a.N = gm.ho * gm.wo; a.K = k * k * c_in;
-		return plan_forward(a, batch).path == FWD_TILED_WINDOW ? 1 : 0;
-	}
+	if (!data_gradient) return plan_forward(fwd_product(nullptr, nullptr, nullptr, nullptr, batch, h, w, k, c_in, f_n, stride), batch).path == FWD_TILED_WINDOW ? 1 : 0;
 	if (stride != 1) return 0;                 // parity classes / zero dilation build their own sub-kernels
-	a.g = ConvGeom{h, w, k, f_n, 1, h, w, k - 1 - gm.pt, k - 1 - gm.pl};
-	a.lda = k * k * f_n; a.M = c_in; a.N = h * w; a.K = k * k * f_n;
-	// (conv2d_backward's one-launch pair for shapes that stay on the 32x32 kernel flips for itself: no prepared form there)
-	ConvArgs aw;
-	aw.g = ConvGeom{h, w, k, c_in, stride, gm.ho, gm.wo, gm.pt, gm.pl};
-	aw.A = a.A; aw.lda = gm.ho * gm.wo; aw.M = f_n; aw.N = k * k * c_in; aw.K = gm.ho * gm.wo;
-	if (!use_tiled_gather(aw, batch, 2) && !use_tiled_gather(a, batch, 1)) return 0;
-	return plan_forward(a, batch).path == FWD_TILED_WINDOW ? 2 : 3;
+	const ConvArgs ad = dgrad_product(nullptr, nullptr, nullptr, nullptr, batch, h, w, k, c_in, f_n, 1);
+	// (the one-launch pair for shapes that stay on the 32x32 kernel flips for itself: no prepared form there)
+	if (plan_backward(wgrad_product(nullptr, nullptr, nullptr, nullptr, batch, h, w, k, c_in, f_n, 1), ad, batch) == BWD_WSK_PAIR) return 0;
+	return plan_forward(ad, batch).path == FWD_TILED_WINDOW ? 2 : 3;
 }
 // Modes 2 and 3 transpose the (f, c) axes of [F][C][k*k]: read and written through a 16 x 16 tile of k*k-vectors in LDS so that both sides move whole
 // 16 * k*k-float runs (element by element the reads were 36-byte pieces a row apart: 49 us for the U-Net's 35 matrices).  Mode 1 only permutes inside a row.

@@ -56,23 +56,24 @@ inline const float* zero_word() { return reinterpret_cast<const float*>(ctx().ti
 //   mode 4: mode 2 transposed on a padded copy (stride 1): M = taps, N = rows of A (= del_y [image][N][HWo]), C [N][M] = the weight gradient
 // tables: {element offset, y | x << 16}.  Needs K % 16 == 0 (mode 2: HWo % 16 == 0), A 16-byte aligned with lda % 4 == 0.
 int gather3_splits(int M, int N, int K);                               // ... of a mode-3 product (forward / data gradient on few tiles)
-int gather_gemm_splits(int mode, int batch, int M, int N, int HWo);   // K splits (= slabs of M*N floats in the workspace) gather_gemm will use
 struct GatherEpilogue { const float* bias; int bias_stride; const float* add; float* out2; };   // mode 3: out = product + bias[image * stride + row]; out2 = out + add
-bool gather3_fuses_epilogue(int M, int N, int K);                      // true: gather_gemm(mode 3, ...) takes a GatherEpilogue
-bla_status gather_gemm(hipStream_t s, int mode, int batch, int M, int N, int K, const float* A, int lda, float* C, int ldc, const float* img,
-                       const int2* ktab, const int2* ntab, int H, int W, int HWo, int img_stride, const GatherEpilogue* ep = nullptr, int wo = 0);
-// (wo: mode 4 -- the output map's width; 4, 8 or a multiple of 16 puts the weight gradient on the half-slab kernel with fixed lane offsets, anything else (or 0) on the older form)
-// mode 3, up to four products over the same padded image in one launch (bla_gather.hip): each class its kernels A [M][K] (lda = K), tap table and output
+bool gather3_fuses_epilogue(int M, int N, int K);                      // true: a mode-3 product takes a GatherEpilogue
+// One gathered product: C = A . G (mode 4: its transpose), G gathered from img through the tables; H, W, HWo, img_stride as the mode reads them (the padded
+// modes: the copy's rows and row pitch).  wo: mode 4 -- the output map's width; 4, 8 or a multiple of 16 puts the weight gradient on the half-slab kernel
+// with fixed lane offsets, anything else (or 0) on the older form.  Mode 7 (the image window, bla_gemm_kernel.h) takes no tables.
+struct GatherProduct { int mode, M, N, K; const float* A; int lda; float* C; int ldc; const float* img; const int2* ktab; const int2* ntab; int H, W, HWo, img_stride; GatherEpilogue ep; int wo; };
+bla_status gather_gemm(hipStream_t s, const GatherProduct& g, int batch);
+// floats of the K-split slabs gather_gemm cuts the product into (0: one pass over K)
+size_t gather_product_slab_floats(const GatherProduct& g, int batch);
+// mode 3, up to four products over the same padded image in one launch (bla_gather.hip): each class its kernels A [M][K] (lda = K), tap table and output;
+// the image, the pixel table and the shapes from g
 struct GatherClass { const float* A; int K; const int2* ktab; float* C; };
 bool gather_classes_fit(int ncls, int M, int N);
-bla_status gather_gemm_classes(hipStream_t s, int batch, int M, int N, const GatherClass* cls, const GatherClass* d_cls, int ncls, int ldc, const float* img,
-                               const int2* ntab, int H, int W, int HWo, int img_stride);
+bla_status gather_gemm_classes(hipStream_t s, const GatherProduct& g, int batch, const GatherClass* cls, const GatherClass* d_cls, int ncls);
 
-// Both gradients of one batched convolution in ONE launch (gather_pair_kernel, bla_gemm_kernel.h): w = the weight gradient as gather_gemm(mode 4, ...) takes it,
-// d = the data gradient as gather_gemm(mode 7 or 3, ...) takes it (whole 128 x 128 tiles: gather_pair_fits); slabs: gather_product_slab_floats floats each (0: none)
-struct GatherProduct { int mode, M, N, K; const float* A; int lda; float* C; int ldc; const float* img; const int2* ktab; const int2* ntab; int H, W, HWo, img_stride; GatherEpilogue ep; int wo; };   // wo: as gather_gemm's
+// Both gradients of one batched convolution in ONE launch (gather_pair_kernel, bla_gemm_kernel.h): w = the weight gradient on mode 4, d = the data gradient
+// on mode 7 or 3 (whole 128 x 128 tiles: gather_pair_fits); slabs: gather_product_slab_floats floats each (0: none)
 bool gather_pair_fits(int mode, int M, int N);
-size_t gather_product_slab_floats(const GatherProduct& g, int batch);
 bla_status gather_pair_products(hipStream_t s, int batch, const GatherProduct& w, float* w_slab, const GatherProduct& d, float* d_slab);
 
 // bla_conv.hip: implicit-GEMM convolution with the adds the U-Net puts behind it: out = conv + ep_bias[image * ep_bias_stride + channel];
