@@ -6,6 +6,8 @@
 // value written here can be restated from (seed, offset) alone:
 //   noise  (seed, pass):  t_b = u32(seed, pass << 32)[b] % T,  eps = normal(seed, pass << 32)[0 .. B*F),  x_t = sqrt(abar_t) x0 + sqrt(1 - abar_t) eps
 //   step   (seed, t):     z = normal(seed, (t + 1) << 32)[0 .. B*F) (0 at t = 0);  x <- (x - beta_t / sqrt(1 - abar_t) eps_hat) / sqrt(alpha_t) + sqrt(beta_t) z
+//   DDIM   (seed, t):     the same z stream, drawn only when sigma > 0;  x0^ = (x - sqrt(1 - abar_t) eps_hat) / sqrt(abar_t) (clamped to [-1, 1] on request),
+//                         x <- sqrt(abar_p) x0^ + sqrt(1 - abar_p - sigma^2) eps_hat + sigma z  (Song, Meng, Ermon 2021; abar_p = 1 past the last step)
 // The schedule is formed in double on the host at create time; the kernels read fp32 tables of the per-step coefficients.  The time embedding is
 // the one examples/cifar_unet_gpu.c computes for BLA_UNET_TIMESTEP, evaluated in double: at t ~ 1000 its arguments reach 1000 rad, where an fp32
 // product t * w_i alone is off by ~6e-5.
@@ -191,6 +193,105 @@ __global__ void __launch_bounds__(1024) sq_diff_sum_kernel(const float* __restri
 bla_status check_images(const bla_diffusion* d, int batch, size_t image_floats, int time_dim) {
 	BLA_REQUIRE(d, BLA_ERR_INVALID, "null diffusion object");
 	BLA_REQUIRE(batch >= 1 && image_floats >= 1 && time_dim >= 1, BLA_ERR_INVALID, "batch %d, image_floats %zu, time_dim %d", batch, image_floats, time_dim);
+	return BLA_OK;
+}
+
+// ---- DDIM (Song, Meng, Ermon 2021) -------------------------------------------------------------------------------------------------------------
+// The step's five coefficients, formed in double on the host from the schedule and passed by value (nothing is uploaded per step, so a captured
+// sampler replays correctly):  x0^ = (x - s1m eps) inv_sab, clamped to [-1, 1] when clip;  x <- sab_prev x0^ + dir eps + sigma z
+struct DdimArgs { float inv_sab, s1m, sab_prev, dir, sigma; int clip; };
+
+DdimArgs ddim_args(const bla_diffusion* d, int t, int t_prev, float eta, int clip) {
+	const double ab = d->alpha_bar[t], abp = t_prev >= 0 ? d->alpha_bar[t_prev] : 1.0;
+	const double sigma = (double)eta * std::sqrt((1.0 - abp) / (1.0 - ab)) * std::sqrt(1.0 - ab / abp);
+	const double dir2 = 1.0 - abp - sigma * sigma;
+	return {(float)(1.0 / std::sqrt(ab)), (float)std::sqrt(1.0 - ab), (float)std::sqrt(abp), (float)std::sqrt(dir2 > 0 ? dir2 : 0.0), (float)sigma, clip ? 1 : 0};
+}
+
+__device__ __forceinline__ float ddim1(float x, float e, float z, const DdimArgs& a) {
+#pragma clang fp contract(off)   // the fused operations spelled out: left to the contraction heuristics, the guided and the unguided instance of the
+                                 // kernel below fused different products and missed bit-equality at guidance 0 (measured)
+	float x0 = fmaf(-a.s1m, e, x) * a.inv_sab;
+	if (a.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+	return fmaf(a.sab_prev, x0, fmaf(a.dir, e, a.sigma * z));
+}
+
+// One DDIM step from t to t_prev in place.  GUIDED = false: eps_u is eps_hat.  GUIDED = true: eps~ = eps_u + s (eps_c - eps_u) by guided_step_kernel's
+// single fmaf (at s = 0 eps~ is eps_u bit for bit, and so is the step), x_copy (may be NULL) receives the new x, temb_next is [2 batch][dim] with the
+// class rows added as guided_step_kernel adds them.  z is step_kernel's stream (seed, (t + 1) << 32), drawn only when sigma > 0; temb_next (may be
+// NULL) receives the embedding of t_prev, nothing at t_prev = -1.
+template <bool GUIDED>
+__global__ void __launch_bounds__(kThreads) ddim_step_kernel(float* __restrict__ x, float* __restrict__ x_copy, const float* __restrict__ eps_c,
+                                                             const float* __restrict__ eps_u, float s, size_t n, DdimArgs a, int t, int t_prev,
+                                                             unsigned long long seed, int batch, int dim, float* __restrict__ temb_next,
+                                                             const float* __restrict__ ctable, int classes, const int* __restrict__ rows, int vec) {
+	const unsigned long long offset = (unsigned long long)(t + 1) << 32;
+	const bool noise = a.sigma > 0.f;
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	if (temb_next && t_prev >= 0) {
+		const size_t ne = (size_t)(GUIDED ? 2 : 1) * batch * dim;
+		for (size_t i = tid; i < ne; i += stride) {
+			const float e = temb_value(t_prev, (int)(i % dim), dim);
+			const int r = GUIDED && ctable ? rows[i / dim] : -1;
+			temb_next[i] = r >= 0 && r <= classes ? e + ctable[(size_t)r * dim + i % dim] : e;
+		}
+	}
+	const size_t n4 = vec ? n / 4 : 0;
+	for (size_t q = tid; q < n4; q += stride) {
+		const float4 z = noise ? philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL)) : make_float4(0.f, 0.f, 0.f, 0.f);
+		float4 e = reinterpret_cast<const float4*>(eps_u)[q];
+		if constexpr (GUIDED) {
+			const float4 c = reinterpret_cast<const float4*>(eps_c)[q];
+			e = make_float4(fmaf(s, c.x - e.x, e.x), fmaf(s, c.y - e.y, e.y), fmaf(s, c.z - e.z, e.z), fmaf(s, c.w - e.w, e.w));
+		}
+		float4 v = reinterpret_cast<float4*>(x)[q];
+		v = make_float4(ddim1(v.x, e.x, z.x, a), ddim1(v.y, e.y, z.y, a), ddim1(v.z, e.z, z.z, a), ddim1(v.w, e.w, z.w, a));
+		reinterpret_cast<float4*>(x)[q] = v;
+		if (GUIDED && x_copy) reinterpret_cast<float4*>(x_copy)[q] = v;
+	}
+	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
+		const float z = noise ? normal_at(seed, offset, i) : 0.f;
+		const float e = GUIDED ? fmaf(s, eps_c[i] - eps_u[i], eps_u[i]) : eps_u[i];
+		const float v = ddim1(x[i], e, z, a);
+		x[i] = v;
+		if (GUIDED && x_copy) x_copy[i] = v;
+	}
+}
+
+bla_status check_ddim(const bla_diffusion* d, int t, int t_prev, float eta) {
+	BLA_REQUIRE(t >= 0 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", t, d->steps);
+	BLA_REQUIRE(t_prev >= -1 && t_prev < t, BLA_ERR_INVALID, "t_prev %d outside [-1, %d)", t_prev, t);
+	BLA_REQUIRE(eta >= 0.f && eta <= 1.f, BLA_ERR_INVALID, "eta %g outside [0, 1]", eta);
+	return BLA_OK;
+}
+
+// "trailing" spacing: out[i] = floor(T (i + 1) / S) - 1, the last always T - 1
+std::vector<int> ddim_timesteps(int T, int S) {
+	std::vector<int> ts(S);
+	for (int i = 0; i < S; i++) ts[i] = (int)((long long)T * (i + 1) / S) - 1;
+	return ts;
+}
+
+// the samplers' workspaces of the diffusion object (scratch, not part of the schedule), grown to at least the sizes given; waits for the stream when
+// it has to grow one, so the first call is not capturable
+bla_status grow_workspaces(bla_diffusion* dm, hipStream_t s, size_t temb_floats, size_t xg_floats, int rows) {
+	if (dm->temb_floats >= temb_floats && dm->xg_floats >= xg_floats && dm->rows_count >= rows) return BLA_OK;
+	BLA_HIP(hipStreamSynchronize(s));
+	if (dm->temb_floats < temb_floats) {
+		(void)hipFree(dm->temb); dm->temb = nullptr; dm->temb_floats = 0;
+		BLA_HIP(hipMalloc((void**)&dm->temb, temb_floats * sizeof(float)));
+		dm->temb_floats = temb_floats;
+	}
+	if (dm->xg_floats < xg_floats) {
+		(void)hipFree(dm->xg); dm->xg = nullptr; dm->xg_floats = 0;
+		BLA_HIP(hipMalloc((void**)&dm->xg, xg_floats * sizeof(float)));
+		dm->xg_floats = xg_floats;
+	}
+	if (dm->rows_count < rows) {
+		(void)hipFree(dm->rows); dm->rows = nullptr; dm->rows_count = 0;
+		BLA_HIP(hipMalloc((void**)&dm->rows, (size_t)rows * sizeof(int)));
+		dm->rows_count = rows;
+	}
 	return BLA_OK;
 }
 
@@ -389,6 +490,114 @@ bla_status bla_mse_accumulate_f32(void* stream, const float* d_a, const float* d
 	BLA_REQUIRE(d_a && d_b && d_acc, BLA_ERR_INVALID, "null argument");
 	hipLaunchKernelGGL(sq_diff_sum_kernel, dim3(1), dim3(1024), 0, pick_stream(stream), d_a, d_b, n, d_acc);
 	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_ddim_timesteps(const bla_diffusion* d, int sample_steps, int* out) {
+	BLA_REQUIRE(d && out, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(sample_steps >= 1 && sample_steps <= d->steps, BLA_ERR_INVALID, "sample_steps %d outside [1, %d]", sample_steps, d->steps);
+	const std::vector<int> ts = ddim_timesteps(d->steps, sample_steps);
+	for (int i = 0; i < sample_steps; i++) out[i] = ts[i];
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_ddim_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, int batch, size_t image_floats, int t, int t_prev,
+                                       float eta, int clip, unsigned long long seed, int time_dim, float* d_temb_next) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(d_x && d_eps_hat, BLA_ERR_INVALID, "null argument");
+	if ((st = check_ddim(d, t, t_prev, eta))) return st;
+	const size_t n = (size_t)batch * image_floats;
+	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_hat) % 16 == 0;
+	hipLaunchKernelGGL((ddim_step_kernel<false>), dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, (float*)nullptr,
+	                   (const float*)nullptr, d_eps_hat, 0.f, n, ddim_args(d, t, t_prev, eta, clip), t, t_prev, seed, batch, time_dim, d_temb_next,
+	                   (const float*)nullptr, 0, (const int*)nullptr, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_unet_sample_ddim_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, int sample_steps, float eta, int clip, unsigned long long seed) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d && d_x, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(sample_steps >= 1 && sample_steps <= d->steps, BLA_ERR_INVALID, "sample_steps %d outside [1, %d]", sample_steps, d->steps);
+	BLA_REQUIRE(eta >= 0.f && eta <= 1.f, BLA_ERR_INVALID, "eta %g outside [0, 1]", eta);
+	const bla_unet_config& c = *unet_config(m);
+	const int B = bla_unet_batch(m);
+	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);
+	if ((st = grow_workspaces(dm, pick_stream(stream), ne, 0, 0))) return st;
+	const std::vector<int> ts = ddim_timesteps(d->steps, sample_steps);
+	hipLaunchKernelGGL(time_embedding_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, pick_stream(stream), (const int*)nullptr, ts.back(), B, c.time_dim, dm->temb);
+	BLA_HIP(hipGetLastError());
+	for (int i = sample_steps - 1; i >= 0; i--) {
+		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
+		if ((st = bla_diffusion_ddim_step_f32(d, stream, d_x, bla_unet_output(m), B, F, ts[i], i > 0 ? ts[i - 1] : -1, eta, clip, seed, c.time_dim, dm->temb)))
+			return st;
+	}
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_guided_ddim_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond, const float* d_eps_uncond,
+                                              float guidance, int batch, size_t image_floats, int t, int t_prev, float eta, int clip, unsigned long long seed,
+                                              int time_dim, float* d_temb_next, const float* d_table, int classes, const int* d_rows) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(d_x && d_eps_cond && d_eps_uncond, BLA_ERR_INVALID, "null argument");
+	if ((st = check_ddim(d, t, t_prev, eta))) return st;
+	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
+	BLA_REQUIRE(!d_table || (d_rows && classes >= 1), BLA_ERR_INVALID, "a class table needs the rows [2 batch] and classes >= 1");
+	const size_t n = (size_t)batch * image_floats;
+	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_cond | (uintptr_t)d_eps_uncond | (uintptr_t)d_x_copy) % 16 == 0;
+	hipLaunchKernelGGL((ddim_step_kernel<true>), dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_x_copy, d_eps_cond, d_eps_uncond,
+	                   guidance, n, ddim_args(d, t, t_prev, eta, clip), t, t_prev, seed, batch, time_dim, d_temb_next, d_table, classes, d_rows, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_unet_sample_guided_ddim_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes, const int* labels,
+                                           float guidance, int sample_steps, float eta, int clip, unsigned long long seed) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d && d_x && d_table && labels, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(classes >= 1, BLA_ERR_INVALID, "classes %d", classes);
+	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
+	BLA_REQUIRE(sample_steps >= 1 && sample_steps <= d->steps, BLA_ERR_INVALID, "sample_steps %d outside [1, %d]", sample_steps, d->steps);
+	BLA_REQUIRE(eta >= 0.f && eta <= 1.f, BLA_ERR_INVALID, "eta %g outside [0, 1]", eta);
+	const bla_unet_config& c = *unet_config(m);
+	const int B = bla_unet_batch(m), n = B / 2;
+	BLA_REQUIRE(B % 2 == 0, BLA_ERR_INVALID, "the guided sampler needs an even model batch (n conditioned images + their n null-class copies), not %d", B);
+	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
+	hipStream_t s = pick_stream(stream);
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);
+	if ((st = grow_workspaces(dm, s, ne, (size_t)B * F, B))) return st;
+	const int* dev_labels = labels;
+	if (host_pointer(labels)) {   // host labels: checked here, the rows uploaded (not capturable: the copy waits for the host)
+		std::vector<int> rows(B);
+		for (int b = 0; b < n; b++) {
+			BLA_REQUIRE(labels[b] >= 0 && labels[b] <= classes, BLA_ERR_INVALID, "label %d of image %d outside [0, %d]", labels[b], b, classes);
+			rows[b] = labels[b]; rows[n + b] = classes;
+		}
+		BLA_HIP(hipMemcpyAsync(dm->rows, rows.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+		BLA_HIP(hipStreamSynchronize(s));
+		dev_labels = nullptr;
+	}
+	const std::vector<int> ts = ddim_timesteps(d->steps, sample_steps);
+	float* xg = dm->xg;
+	BLA_HIP(hipMemcpyAsync(xg, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	BLA_HIP(hipMemcpyAsync(xg + (size_t)n * F, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	hipLaunchKernelGGL(guided_start_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, s, dev_labels, n, classes, dm->rows, d_table, ts.back(), c.time_dim, dm->temb);
+	BLA_HIP(hipGetLastError());
+	const float* out = bla_unet_output(m);
+	for (int i = sample_steps - 1; i >= 0; i--) {
+		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
+		if ((st = bla_diffusion_guided_ddim_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, n, F, ts[i], i > 0 ? ts[i - 1] : -1, eta,
+		                                             clip, seed, c.time_dim, dm->temb, d_table, classes, dm->rows)))
+			return st;
+	}
+	BLA_HIP(hipMemcpyAsync(d_x, xg, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
 	return BLA_OK;
 }
 

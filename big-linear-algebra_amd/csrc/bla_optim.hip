@@ -1,4 +1,4 @@
-// bla_optim.hip -- fused Adam / AdamW over a flat parameter bucket.
+// bla_optim.hip -- fused Adam / AdamW over a flat parameter bucket, and the exponential moving average of a bucket.
 //
 // model/cifar_unet.c's train() allocates the two moment sets of Adam (:1887-1888) and never uses them; this is the update they were for.
 // One pass over the data: p, g, m, v are read once and p, m, v written once (7 streams, 28 bytes per parameter, nothing to compute): the roofline
@@ -7,6 +7,9 @@
 //   p += -(lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 // with the scalars formed in double on the host and rounded to fp32 once, as torch does with its Python-float scalars.  lerp is torch's CPU form,
 // fma(w, g - m, m) for w < 0.5 and fma(w - 1, g - m, g) otherwise.
+//
+// The exponential moving average of the parameters that DDPM samples from (Ho et al. 2020) is the same shape of pass with 3 streams: e read,
+// p read, e written (12 bytes per parameter):  e <- e + w (p - e),  w = 1 - decay, each operation rounded on its own.
 #include "bla_internal.h"
 #include <cmath>
 
@@ -60,6 +63,38 @@ __global__ void __launch_bounds__(kThreads) adam_kernel(float* __restrict__ p, c
 	}
 }
 
+__device__ __forceinline__ float ema1(float e, float p, float w) {
+#pragma clang fp contract(off)   // e + w * (p - e) with every operation rounded: bit-equal to numpy float32
+	return e + w * (p - e);
+}
+__device__ __forceinline__ float4 ema4(const float4 e, const float4 p, float w) {
+	return make_float4(ema1(e.x, p.x, w), ema1(e.y, p.y, w), ema1(e.z, p.z, w), ema1(e.w, p.w, w));
+}
+
+// adam_kernel's split: [head, head + 4 * n4) as float4, two per stream and lane per iteration; the scalar elements in front and behind one per lane
+__global__ void __launch_bounds__(kThreads) ema_kernel(float* __restrict__ e, const float* __restrict__ p, size_t n, size_t head, size_t n4, float w) {
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	float4* e4 = reinterpret_cast<float4*>(e + head);
+	const float4* p4 = reinterpret_cast<const float4*>(p + head);
+	const size_t n8 = n4 / 2;
+	for (size_t i = tid; i < n8; i += stride) {
+		const float4 e0 = e4[2 * i], e1 = e4[2 * i + 1], p0 = p4[2 * i], p1 = p4[2 * i + 1];
+		e4[2 * i] = ema4(e0, p0, w); e4[2 * i + 1] = ema4(e1, p1, w);
+	}
+	for (size_t i = n8 * 2 + tid; i < n4; i += stride) e4[i] = ema4(e4[i], p4[i], w);
+	const size_t body_end = head + 4 * n4, rest = head + (n - body_end);
+	for (size_t k = tid; k < rest; k += stride) {
+		const size_t i = k < head ? k : body_end + (k - head);
+		e[i] = ema1(e[i], p[i], w);
+	}
+}
+
+// workgroups for a pass of n4 float4 taken two per lane: two workgroups per CU at most (what Adam measured fastest)
+unsigned pass_blocks(size_t n4) {
+	const size_t need = (n4 / 2 + kThreads - 1) / kThreads, cap = 2 * (size_t)(ctx().num_cus > 0 ? ctx().num_cus : 256);
+	return (unsigned)(need < 1 ? 1 : (need > cap ? cap : need));
+}
+
 }  // namespace
 }  // namespace bla
 
@@ -85,9 +120,24 @@ bla_status bla_adam_f32(void* stream, float* d_params, const float* d_grads, flo
 	const double w1 = 1.0 - (double)beta1;
 	AdamArgs a = {grad_scale, (float)(1.0 - (double)lr * weight_decay), (float)w1, beta2, (float)(1.0 - (double)beta2), (float)((double)lr / bc1),
 	              (float)std::sqrt(bc2), eps, std::fabs(w1) < 0.5 ? 1 : 0};
-	const size_t need = (n4 / 2 + kThreads - 1) / kThreads, cap = 2 * (size_t)(ctx().num_cus > 0 ? ctx().num_cus : 256);
-	const unsigned blocks = (unsigned)(need < 1 ? 1 : (need > cap ? cap : need));
-	hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(kThreads), 0, pick_stream(stream), d_params, d_grads, d_m, d_v, n, head, n4, a);
+	hipLaunchKernelGGL(adam_kernel, dim3(pass_blocks(n4)), dim3(kThreads), 0, pick_stream(stream), d_params, d_grads, d_m, d_v, n, head, n4, a);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_ema_f32(void* stream, float* d_ema, const float* d_params, size_t n, float decay) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(decay >= 0.f && decay <= 1.f, BLA_ERR_INVALID, "decay %g outside [0, 1]", decay);
+	if (n == 0) return BLA_OK;
+	BLA_REQUIRE(d_ema && d_params, BLA_ERR_INVALID, "null operand");
+	const uintptr_t mis = (uintptr_t)d_ema % 16;
+	BLA_REQUIRE(mis % 4 == 0 && (uintptr_t)d_params % 4 == 0, BLA_ERR_INVALID, "buckets not 4-byte aligned");
+	size_t head = (uintptr_t)d_params % 16 == mis ? ((16 - mis) % 16) / 4 : n;   // buckets of different alignment: every element on the scalar path
+	if (head > n) head = n;
+	const size_t n4 = (n - head) / 4;
+	const float w = (float)(1.0 - (double)decay);
+	hipLaunchKernelGGL(ema_kernel, dim3(pass_blocks(n4)), dim3(kThreads), 0, pick_stream(stream), d_ema, d_params, n, head, n4, w);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
 }

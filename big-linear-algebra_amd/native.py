@@ -136,7 +136,7 @@ SIGNATURES = {
     "bla_mnist_nn_dp_step": (_I, [_VP, _VP, _VP, _F, _I]), "bla_mnist_nn_dp_step_direct": (_I, [_VP, _VP, _VP, _F, _I]),
     "bla_rand_u32": (_I, [_VP, _VP, _SZ, _U64, _U64]), "bla_rand_normal_f32": (_I, [_VP, _VP, _SZ, _F, _F, _U64, _U64]),
     "bla_rand_bernoulli_u8": (_I, [_VP, _VP, _SZ, _F, _U64, _U64]),
-    "bla_adam_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _F, _F, _F, _I]),
+    "bla_adam_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _F, _F, _F, _I]), "bla_ema_f32": (_I, [_VP, _VP, _VP, _SZ, _F]),
     "bla_diffusion_create": (_I, [C.POINTER(_VP), _I, _F, _F]), "bla_diffusion_destroy": (_I, [_VP]), "bla_diffusion_steps": (_I, [_VP]),
     "bla_diffusion_schedule": (_I, [_VP, _I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bla_time_embedding_f32": (_I, [_VP, _VP, _I, _I, _VP]),
@@ -148,6 +148,11 @@ SIGNATURES = {
     "bla_class_embedding_grad_f32": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
     "bla_diffusion_guided_step_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _I, _SZ, _I, _U64, _I, _VP, _VP, _I, _VP]),
     "bla_unet_sample_guided_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _F, _U64]),
+    "bla_diffusion_ddim_timesteps": (_I, [_VP, _I, _VP]),
+    "bla_diffusion_ddim_step_f32": (_I, [_VP, _VP, _VP, _VP, _I, _SZ, _I, _I, _F, _I, _U64, _I, _VP]),
+    "bla_unet_sample_ddim_f32": (_I, [_VP, _VP, _VP, _VP, _I, _F, _I, _U64]),
+    "bla_diffusion_guided_ddim_step_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _I, _SZ, _I, _I, _F, _I, _U64, _I, _VP, _VP, _I, _VP]),
+    "bla_unet_sample_guided_ddim_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _F, _I, _F, _I, _U64]),
 }
 
 

@@ -59,6 +59,20 @@
  *                                                      device is opened) and bla_unet_sample_guided_f32 at model batch 2 x min(n,
  *                                                      BLA_UNET_BATCH), guidance BLA_UNET_GUIDANCE (default 3); file names, BMP format and
  *                                                      per-batch seeds as without.  Without BLA_UNET_CLASS `sample` is unchanged.
+ *   (not in the reference)                             The weights DDPM samples from and few-step sampling (DDIM, Song, Meng, Ermon 2021).
+ *                                                      `fit` with BLA_UNET_EMA=<decay> (0 < decay < 1, e.g. 0.9999): an exponential moving
+ *                                                      average of the parameters (and of the class table when conditional) on the device,
+ *                                                      started from the parameters fit starts from and updated by bla_ema_f32 after each
+ *                                                      Adam step with min(decay, (1 + pass) / (10 + pass)); at the end a second, complete file
+ *                                                      set below <weights>/ema/ (BLA_UNET_WEIGHTS=<weights>/ema samples from it).  With
+ *                                                      BLA_UNET_RESUME=1 the average starts from <weights>/ema/ if that directory exists (a
+ *                                                      missing file there stops the program before the device is opened), else from the
+ *                                                      resumed parameters.  Without BLA_UNET_EMA `fit` writes what it wrote before.
+ *                                                      `sample` with BLA_UNET_SAMPLE_STEPS=S (1 .. BLA_DIFFUSION_STEPS): the DDIM samplers
+ *                                                      (guided with BLA_UNET_CLASS), S forward passes instead of BLA_DIFFUSION_STEPS;
+ *                                                      BLA_UNET_ETA (0 .. 1, default 0: deterministic) scales the noise, BLA_UNET_CLIP=1
+ *                                                      clamps the predicted x_0 to [-1, 1].  Bad values stop the program before the device is
+ *                                                      opened.  Without BLA_UNET_SAMPLE_STEPS `sample` is unchanged.
  *
  * BLA_UNET_DUMP=<dir> makes train write what it uploaded (params, x, time embedding, noise, dropout decisions) and what came back (prediction,
  * gradient bucket) as raw little-endian files; tests/test_c_unet.py compares those with the oracle.
@@ -232,7 +246,10 @@ static void draw_parameters(const char* default_init) {
 	rng_end();
 }
 
-static void data_path(char* out, size_t n, const char* below) { snprintf(out, n, "%s%s%s", env_or("BLA_UNET_WEIGHTS", "data/cifar_unet"), *below ? "/" : "", below); }
+static const char* g_set = "";   /* "" = the parameter set, "ema" = fit's moving average of it, one directory below */
+static void data_path(char* out, size_t n, const char* below) {
+	snprintf(out, n, "%s%s%s%s%s", env_or("BLA_UNET_WEIGHTS", "data/cifar_unet"), *g_set ? "/" : "", g_set, *below ? "/" : "", below);
+}
 
 /* save_parameters :1545-1660 */
 static void save_parameters(void) {
@@ -551,8 +568,48 @@ static void save_class_table(float* table) {
 	write_csv_contents(path, table, TIME_EMBED_DIM, CLASSES + 1);
 }
 
+/* BLA_UNET_EMA=<decay> for fit, 0 < decay < 1; 0 = not set */
+static double env_ema_decay(void) {
+	const char* v = getenv("BLA_UNET_EMA");
+	if (!v || !*v) return 0;
+	char* end = NULL;
+	const double decay = strtod(v, &end);
+	if (*end || !(decay > 0 && decay < 1)) { fprintf(stderr, "fit: BLA_UNET_EMA=%s; the decay must lie strictly between 0 and 1 (e.g. 0.9999)\n", v); exit(1); }
+	return decay;
+}
+/* exchanges the host tensors with another set of the same shapes */
+static void swap_sets(float** other) {
+	for (int t = 0; t < g_tensor_count; t++) { float* h = g_tensors[t].host; g_tensors[t].host = other[t]; other[t] = h; }
+}
+/* the EMA set a resumed fit starts from, <weights>/ema/ (and its class table into ema_table, when not NULL), every file checked before the device is
+ * opened; NULL when there is no such directory */
+static float** load_ema_set(float* ema_table) {
+	char path[512];
+	struct stat sb;
+	g_set = "ema";
+	data_path(path, sizeof path, "");
+	if (stat(path, &sb) != 0 || !S_ISDIR(sb.st_mode)) { g_set = ""; return NULL; }
+	for (int t = 0; t < g_tensor_count; t++) {
+		data_path(path, sizeof path, g_tensors[t].file);
+		if (access(path, R_OK) != 0) { fprintf(stderr, "fit: the EMA set is incomplete: cannot open %s\n", path); exit(1); }
+	}
+	if (ema_table && !load_class_table(ema_table)) {
+		data_path(path, sizeof path, "class_embedding.csv");
+		fprintf(stderr, "fit: the EMA set is incomplete: cannot open %s\n", path);
+		exit(1);
+	}
+	float** set = malloc(g_tensor_count * sizeof(float*));
+	for (int t = 0; t < g_tensor_count; t++) set[t] = calloc((size_t)g_tensors[t].rows * g_tensors[t].cols, sizeof(float));
+	swap_sets(set);
+	load_parameters();
+	swap_sets(set);
+	g_set = "";
+	return set;
+}
+
 static void fit(int epochs, int batch) {
 	if (batch < 1 || epochs < 1) { fprintf(stderr, "fit: epochs and batch must be >= 1\n"); exit(1); }
+	const double ema_decay = env_ema_decay();
 	const int classes = env_flag("BLA_UNET_CLASSES");
 	size_t records = 0;
 	uint8_t* labels = NULL;
@@ -569,6 +626,13 @@ static void fit(int epochs, int batch) {
 		if (env_flag("BLA_UNET_RESUME")) (void)load_class_table(table);
 	}
 	if (env_flag("BLA_UNET_RESUME")) load_parameters(); else draw_parameters("unit");
+	const size_t table_floats = (size_t)(CLASSES + 1) * TIME_EMBED_DIM;
+	float* ema_table = NULL;   /* BLA_UNET_EMA: the average's class table (host), and the resumed EMA set (NULL: the average starts from the parameters) */
+	float** ema_set = NULL;
+	if (ema_decay > 0) {
+		if (classes) { ema_table = malloc(table_floats * sizeof(float)); memcpy(ema_table, table, table_floats * sizeof(float)); }
+		if (env_flag("BLA_UNET_RESUME")) ema_set = load_ema_set(ema_table);
+	}
 	const unsigned long long seed = env_seed();
 	const double lr = atof(env_or("BLA_ADAM_LR", "2e-4"));
 	int log_every = atoi(env_or("BLA_UNET_LOG_EVERY", "50"));
@@ -586,7 +650,17 @@ static void fit(int epochs, int batch) {
 	CHECK(bla_malloc((void**)&d_v, params * sizeof(float))); CHECK(bla_memset(d_v, 0, params * sizeof(float), NULL));
 	CHECK(bla_malloc((void**)&d_t, batch * sizeof(int)));
 	CHECK(bla_malloc((void**)&d_loss, sizeof(double))); CHECK(bla_memset(d_loss, 0, sizeof(double), NULL));
-	const size_t table_floats = (size_t)(CLASSES + 1) * TIME_EMBED_DIM;
+	float *d_ema = NULL, *d_ema_table = NULL;
+	if (ema_decay > 0) {   /* device_set_params reuses the bucket's host image: each upload is waited for before the next */
+		CHECK(bla_malloc((void**)&d_ema, params * sizeof(float)));
+		if (ema_set) { CHECK(bla_stream_sync(NULL)); swap_sets(ema_set); device_set_params(&dv); }
+		CHECK(bla_memcpy_d2d(d_ema, bla_unet_params(dv.net), params * sizeof(float), NULL));
+		if (ema_set) { CHECK(bla_stream_sync(NULL)); swap_sets(ema_set); device_set_params(&dv); }
+		if (classes) {
+			CHECK(bla_malloc((void**)&d_ema_table, table_floats * sizeof(float)));
+			CHECK(bla_memcpy_h2d(d_ema_table, ema_table, table_floats * sizeof(float), NULL));
+		}
+	}
 	float *d_table = NULL, *d_gtable = NULL, *d_tm = NULL, *d_tv = NULL, *d_dtemb = NULL; int *d_labels = NULL, *d_rows = NULL;
 	if (classes) {
 		int* lab = malloc(used * sizeof(int));
@@ -625,6 +699,11 @@ static void fit(int epochs, int batch) {
 		CHECK(bla_adam_f32(NULL, bla_unet_params(dv.net), bla_unet_grads(dv.net), d_m, d_v, params, (float)lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
 		if (classes)
 			CHECK(bla_adam_f32(NULL, d_table, d_gtable, d_tm, d_tv, table_floats, (float)lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
+		if (ema_decay > 0) {   /* the warm-up keeps the early average from holding on to the initial draw */
+			const float decay = (float)fmin(ema_decay, (1.0 + pass) / (10.0 + pass));
+			CHECK(bla_ema_f32(NULL, d_ema, bla_unet_params(dv.net), params, decay));
+			if (classes) CHECK(bla_ema_f32(NULL, d_ema_table, d_table, table_floats, decay));
+		}
 		if ((pass + 1) % log_every == 0 || pass + 1 == passes) {
 			double sum = 0;
 			CHECK(bla_memcpy_d2h(&sum, d_loss, sizeof sum, NULL));
@@ -637,6 +716,22 @@ static void fit(int epochs, int batch) {
 	}
 	device_get_params(&dv);
 	save_parameters();
+	if (ema_decay > 0) {   /* the average as a second complete set below ema/: tensors the device model does not use keep the values just written */
+		CHECK(bla_memcpy_d2d(bla_unet_params(dv.net), d_ema, params * sizeof(float), NULL));
+		device_get_params(&dv);
+		g_set = "ema";
+		save_parameters();
+		if (classes) {
+			CHECK(bla_memcpy_d2h(ema_table, d_ema_table, table_floats * sizeof(float), NULL));
+			CHECK(bla_stream_sync(NULL));
+			save_class_table(ema_table);
+			CHECK(bla_free(d_ema_table));
+			free(ema_table);
+		}
+		g_set = "";
+		CHECK(bla_free(d_ema));
+		if (ema_set) { for (int t = 0; t < g_tensor_count; t++) free(ema_set[t]); free(ema_set); }
+	}
 	if (classes) {
 		CHECK(bla_memcpy_d2h(table, d_table, table_floats * sizeof(float), NULL));
 		CHECK(bla_stream_sync(NULL));
@@ -654,6 +749,22 @@ static void sample(int count, const char* dir) {
 	int batch = atoi(env_or("BLA_UNET_BATCH", "16"));
 	if (batch > count) batch = count;
 	if (batch < 1) return;
+	/* BLA_UNET_SAMPLE_STEPS=S: DDIM with S steps, BLA_UNET_ETA, BLA_UNET_CLIP; checked before the device is opened */
+	const char* steps_env = getenv("BLA_UNET_SAMPLE_STEPS");
+	const int ddim = steps_env && *steps_env;
+	int sample_steps = 0;
+	if (ddim) {
+		char* end = NULL;
+		const long s = strtol(steps_env, &end, 10);
+		const int T = env_steps();
+		if (*end || s < 1 || s > T) { fprintf(stderr, "sample: BLA_UNET_SAMPLE_STEPS=%s; DDIM takes 1..%d steps (BLA_DIFFUSION_STEPS)\n", steps_env, T); exit(1); }
+		sample_steps = (int)s;
+	}
+	const char* eta_env = env_or("BLA_UNET_ETA", "0");
+	char* eta_end = NULL;
+	const double eta = strtod(eta_env, &eta_end);
+	if (*eta_end || !(eta >= 0 && eta <= 1)) { fprintf(stderr, "sample: BLA_UNET_ETA=%s; eta must lie in [0, 1]\n", eta_env); exit(1); }
+	const int clip = env_flag("BLA_UNET_CLIP");
 	/* BLA_UNET_CLASS=k: guided sampling of class k with the table fit wrote; both checked before the device is opened */
 	const char* class_env = getenv("BLA_UNET_CLASS");
 	const int guided = class_env && *class_env;
@@ -697,7 +808,10 @@ static void sample(int count, const char* dir) {
 	int done = 0;
 	for (unsigned long long k = 0; done < count; k++) {
 		CHECK(bla_rand_normal_f32(NULL, dv.x, (size_t)batch * IMAGE_FLOATS, 0.f, 1.f, seed + k, 0));   /* x_T */
-		if (guided) CHECK(bla_unet_sample_guided_f32(dv.net, diff, NULL, dv.x, d_table, CLASSES, d_labels, guidance, seed + k));
+		if (guided && ddim)
+			CHECK(bla_unet_sample_guided_ddim_f32(dv.net, diff, NULL, dv.x, d_table, CLASSES, d_labels, guidance, sample_steps, (float)eta, clip, seed + k));
+		else if (guided) CHECK(bla_unet_sample_guided_f32(dv.net, diff, NULL, dv.x, d_table, CLASSES, d_labels, guidance, seed + k));
+		else if (ddim) CHECK(bla_unet_sample_ddim_f32(dv.net, diff, NULL, dv.x, sample_steps, (float)eta, clip, seed + k));
 		else CHECK(bla_unet_sample_f32(dv.net, diff, NULL, dv.x, seed + k));
 		CHECK(bla_memcpy_d2h(x, dv.x, (size_t)batch * IMAGE_FLOATS * sizeof(float), NULL));
 		CHECK(bla_stream_sync(NULL));

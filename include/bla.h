@@ -435,6 +435,11 @@ BLA_API bla_status bla_rand_bernoulli_u8(void* stream, unsigned char* d_out, siz
  * gradients (summed over the images).  m and v start zeroed. */
 BLA_API bla_status bla_adam_f32(void* stream, float* d_params, const float* d_grads, float* d_m, float* d_v, size_t n, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, float grad_scale, int step);
+/* Exponential moving average of a bucket (the weights DDPM samples from, Ho et al. 2020): e <- e + w (p - e), w = 1 - decay formed in double on the
+ * host and rounded to fp32 once, every operation rounded on its own -- bit-equal to numpy float32 e + float32(w) * (p - e).  decay in [0, 1] (else
+ * BLA_ERR_INVALID; 1 leaves e as it is).  This applies the decay it is given: any warm-up (e.g. min(decay, (1 + step) / (10 + step)), what
+ * examples/cifar_unet_gpu.c uses) is the caller's.  Any alignment and any n (0: nothing); 16-byte loads and stores in the body. */
+BLA_API bla_status bla_ema_f32(void* stream, float* d_ema, const float* d_params, size_t n, float decay);
 /* Linear beta schedule over `steps` timesteps (DDPM: 1e-4 .. 0.02, steps = 1000): beta_t = beta_start + (beta_end - beta_start) t / (steps - 1),
  * alpha_bar_t = prod_{s <= t} (1 - beta_s), in double at create time; the kernels read fp32 tables of the per-step coefficients. */
 typedef struct bla_diffusion bla_diffusion;
@@ -459,6 +464,28 @@ BLA_API bla_status bla_diffusion_step_f32(const bla_diffusion* d, void* stream, 
  * output.  d_x: in x_T, out x_0, [B][C][H][W].  The [B][time_dim] embedding workspace belongs to the diffusion object and is allocated on first use:
  * like the model's own workspaces, run the sampler once eagerly before capturing it into a graph. */
 BLA_API bla_status bla_unet_sample_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, unsigned long long seed);
+/* Few-step sampling with DDIM (Song, Meng, Ermon 2021): the same trained network, S << steps forward passes.
+ * The timesteps of a run of S = sample_steps, "trailing" spacing: out[i] = floor(steps (i + 1) / S) - 1 for i = 0 .. S-1, increasing; the last is
+ * always steps - 1, and S = steps gives every step.  1 <= S <= steps, else BLA_ERR_INVALID.  Host only. */
+BLA_API bla_status bla_diffusion_ddim_timesteps(const bla_diffusion* d, int sample_steps, int* out);
+/* One DDIM step from t to t_prev (-1: to the data) in place, one launch.  With abar_p = alpha_bar[t_prev] (1 at t_prev = -1):
+ *   x0^ = (x - sqrt(1 - abar_t) eps_hat) / sqrt(abar_t), clamped to [-1, 1] (the data range of load_example) when clip is non-zero (eps_hat is
+ *         used as it is);
+ *   sigma = eta sqrt((1 - abar_p) / (1 - abar_t)) sqrt(1 - abar_t / abar_p);
+ *   x <- sqrt(abar_p) x0^ + sqrt(max(0, 1 - abar_p - sigma^2)) eps_hat + sigma z,
+ * z = bla_rand_normal_f32(batch * image_floats, 0, 1, seed, (t + 1) << 32) -- bla_diffusion_step_f32's stream layout, x_T keeps offset 0 -- drawn
+ * only when sigma > 0 (eta = 0 is deterministic).  The five coefficients are formed in double on the host and passed by value: nothing is uploaded
+ * per step, so a captured sampler replays correctly.  d_temb_next (may be NULL) [batch][time_dim]: the embedding of t_prev (nothing at t_prev = -1).
+ * t outside [0, steps), t_prev outside [-1, t), eta outside [0, 1] or not finite: BLA_ERR_INVALID.
+ * eta = 1 at S = steps is DDPM with the posterior variance beta~_t = beta_t (1 - abar_{t-1}) / (1 - abar_t); the ancestral step above uses
+ * sigma_t^2 = beta_t, so the two samplers are not bit-equal there. */
+BLA_API bla_status bla_diffusion_ddim_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, int batch, size_t image_floats, int t,
+                                               int t_prev, float eta, int clip, unsigned long long seed, int time_dim, float* d_temb_next);
+/* DDIM sampling on the model's batch: over the bla_diffusion_ddim_timesteps of sample_steps from the last, bla_unet_forward_f32 (no dropout) then
+ * bla_diffusion_ddim_step_f32 with the model's output.  d_x: in x_T, out x_0.  The embedding workspace is bla_unet_sample_f32's (allocated on first
+ * use: run once eagerly before capturing it into a graph).  Bad sample_steps or eta: BLA_ERR_INVALID. */
+BLA_API bla_status bla_unet_sample_ddim_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, int sample_steps, float eta, int clip,
+                                            unsigned long long seed);
 /* *d_acc += sum_i (a_i - b_i)^2, accumulated in double in a fixed order (one workgroup): the training loss without a host round trip per pass */
 BLA_API bla_status bla_mse_accumulate_f32(void* stream, const float* d_a, const float* d_b, size_t n, double* d_acc);
 
@@ -501,6 +528,17 @@ BLA_API bla_status bla_diffusion_guided_step_f32(const bla_diffusion* d, void* s
  * embedding and row workspaces belong to the diffusion object and are allocated on first use: run once eagerly before capturing it into a graph. */
 BLA_API bla_status bla_unet_sample_guided_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes,
                                               const int* labels, float guidance, unsigned long long seed);
+/* The guided DDIM step: eps~ = eps_u + guidance (eps_c - eps_u) with bla_diffusion_guided_step_f32's single fmaf, then bla_diffusion_ddim_step_f32's
+ * update from t to t_prev (the same kernel: guidance 0 = the unguided DDIM step on eps_u, bit for bit).  d_x_copy and d_temb_next [2 batch][time_dim]
+ * (the embedding of t_prev plus the class rows; nothing at t_prev = -1) as for bla_diffusion_guided_step_f32.  One launch. */
+BLA_API bla_status bla_diffusion_guided_ddim_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond,
+                                                      const float* d_eps_uncond, float guidance, int batch, size_t image_floats, int t, int t_prev,
+                                                      float eta, int clip, unsigned long long seed, int time_dim, float* d_temb_next,
+                                                      const float* d_table, int classes, const int* d_rows);
+/* Guided DDIM sampling: bla_unet_sample_guided_f32's loop (model batch 2n, labels, workspaces and their rules) over the DDIM timesteps of
+ * sample_steps, one batch-2n forward pass and one bla_diffusion_guided_ddim_step_f32 per step. */
+BLA_API bla_status bla_unet_sample_guided_ddim_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes,
+                                                   const int* labels, float guidance, int sample_steps, float eta, int clip, unsigned long long seed);
 
 /* ---- device-resident MNIST-NN trainer: the hot loop of model/mnist_nn.c:218-315 with everything in HBM -------
  * sizes = {n0, n1, n2, n3} (784, 256, 128, 10 in the reference, model/mnist_nn.c:25-28); samples are columns.
