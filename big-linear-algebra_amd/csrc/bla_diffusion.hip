@@ -5,6 +5,7 @@
 // an image at a timestep and leaves run() empty (:1936).  Random draws come from the Philox streams of bla_philox.h (see include/bla.h), so every
 // value written here can be restated from (seed, offset) alone:
 //   noise  (seed, pass):  t_b = u32(seed, pass << 32)[b] % T,  eps = normal(seed, pass << 32)[0 .. B*F),  x_t = sqrt(abar_t) x0 + sqrt(1 - abar_t) eps
+//   gather (seed, pass):  the same on the batch whose image b is record index[b], mirrored where bernoulli(0.5, seed, (pass << 32) + 2^31 + 2^30)[b] is 1
 //   step   (seed, t):     z = normal(seed, (t + 1) << 32)[0 .. B*F) (0 at t = 0);  x <- (x - beta_t / sqrt(1 - abar_t) eps_hat) / sqrt(alpha_t) + sqrt(beta_t) z
 //   DDIM   (seed, t):     the same z stream, drawn only when sigma > 0;  x0^ = (x - sqrt(1 - abar_t) eps_hat) / sqrt(abar_t) (clamped to [-1, 1] on request),
 //                         x <- sqrt(abar_p) x0^ + sqrt(1 - abar_p - sigma^2) eps_hat + sigma z  (Song, Meng, Ermon 2021; abar_p = 1 past the last step)
@@ -60,36 +61,84 @@ __global__ void __launch_bounds__(kThreads) time_embedding_kernel(const int* __r
 		out[i] = temb_value(d_t ? d_t[i / dim] : t_const, (int)(i % dim), dim);
 }
 
-__global__ void __launch_bounds__(kThreads) noise_kernel(const float* __restrict__ x0, int batch, size_t F, int dim, unsigned long long seed, unsigned long long offset,
-                                                         int steps, const float* __restrict__ table, int* __restrict__ d_t, float* __restrict__ eps,
-                                                         float* __restrict__ xt, float* __restrict__ temb, int vec) {
+// x_t = sqrt(abar_t) x0 + sqrt(1 - abar_t) z.  The float4 body has always fused the first product into the sum and the scalar path has always rounded
+// both products; each form is spelled out so that neither depends on the contraction heuristics and both keep the bits they have always written.
+__device__ __forceinline__ float noise1_vec(float a, float x, float c, float z) {
+#pragma clang fp contract(off)
+	return fmaf(a, x, c * z);
+}
+__device__ __forceinline__ float noise1_scalar(float a, float x, float c, float z) {
+#pragma clang fp contract(off)
+	return a * x + c * z;
+}
+
+constexpr int kFlipBit = 1 << 30;   // steps <= 2^24: the bit is free in the LDS copy of t_b
+constexpr unsigned long long kFlipOffset = (1ull << 31) + (1ull << 30);   // the flip decisions' Philox blocks, behind the label dropout's (bla.h)
+
+// Noises the batch whose image b is record index[b] (NULL: record b) of data [records][F], mirrored along its rows of `width` where flip is set and
+// the image's Bernoulli(0.5) decision is 1.  A record outside [0, records) reads nothing: the image is zero and its label -1.  t_b, eps and the
+// embedding are indexed by output position, so they depend on neither the index nor the flips.  x0_out (may be NULL) receives the assembled batch,
+// labels_out (with labels) the gathered labels.
+__global__ void __launch_bounds__(kThreads) noise_kernel(const float* __restrict__ data, size_t records, const unsigned int* __restrict__ index, int flip, unsigned width,
+                                                         const int* __restrict__ labels, int* __restrict__ labels_out, int batch, size_t F, int dim,
+                                                         unsigned long long seed, unsigned long long offset, int steps, const float* __restrict__ table,
+                                                         int* __restrict__ d_t, float* __restrict__ eps, float* __restrict__ xt, float* __restrict__ temb,
+                                                         float* __restrict__ x0_out, int vec) {
 	__shared__ int ts[kMaxNoiseBatch];
 	for (int b = threadIdx.x; b < batch; b += blockDim.x) {
-		ts[b] = (int)(u32_at(seed, offset, (size_t)b) % (uint32_t)steps);
-		if (blockIdx.x == 0) d_t[b] = ts[b];
+		const int t = (int)(u32_at(seed, offset, (size_t)b) % (uint32_t)steps);
+		ts[b] = flip && u32_at(seed, offset + kFlipOffset, (size_t)b, PHILOX_TAG_BERNOULLI) < 0x80000000u ? t | kFlipBit : t;
+		if (blockIdx.x == 0) {
+			d_t[b] = t;
+			if (labels && labels_out) {
+				const size_t r = index ? index[b] : (size_t)b;
+				labels_out[b] = r < records ? labels[r] : -1;
+			}
+		}
 	}
 	__syncthreads();
 	const float* sab = table + TAB_SQRT_AB * steps;
 	const float* s1m = table + TAB_SQRT_1MAB * steps;
 	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
 	const size_t ne = (size_t)batch * dim;
-	for (size_t i = tid; i < ne; i += stride) temb[i] = temb_value(ts[i / dim], (int)(i % dim), dim);
+	for (size_t i = tid; i < ne; i += stride) temb[i] = temb_value(ts[i / dim] & ~kFlipBit, (int)(i % dim), dim);
 	const size_t n = (size_t)batch * F;
-	if (vec) {   // F % 4 == 0, all three 16-byte aligned: Philox block q <-> float4 q, one image per float4
+	if (vec) {   // F % 4 == 0 (width % 4 == 0 when flipping), every pointer 16-byte aligned: Philox block q <-> float4 q, one image per float4
 		for (size_t q = tid; q < n / 4; q += stride) {
-			const int t = ts[(4 * q) / F];
+			const size_t b = (4 * q) / F, p = 4 * q - b * F;
+			const int t = ts[b] & ~kFlipBit;
 			const float4 z = philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL));
-			const float4 x = reinterpret_cast<const float4*>(x0)[q];
+			const size_t r = index ? index[b] : b;
+			float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+			if (r < records) {
+				if (ts[b] & kFlipBit) {   // the float4 at the mirrored position, its components reversed
+					const unsigned col = F >> 32 ? (unsigned)(p % width) : (unsigned)p % width;
+					const float4 m = *reinterpret_cast<const float4*>(data + r * F + (p - col) + (width - 4 - col));
+					x = make_float4(m.w, m.z, m.y, m.x);
+				} else {
+					x = *reinterpret_cast<const float4*>(data + r * F + p);
+				}
+			}
 			const float a = sab[t], c = s1m[t];
 			reinterpret_cast<float4*>(eps)[q] = z;
-			reinterpret_cast<float4*>(xt)[q] = make_float4(a * x.x + c * z.x, a * x.y + c * z.y, a * x.z + c * z.z, a * x.w + c * z.w);
+			reinterpret_cast<float4*>(xt)[q] = make_float4(noise1_vec(a, x.x, c, z.x), noise1_vec(a, x.y, c, z.y), noise1_vec(a, x.z, c, z.z), noise1_vec(a, x.w, c, z.w));
+			if (x0_out) reinterpret_cast<float4*>(x0_out)[q] = x;
 		}
 	} else {
 		for (size_t e = tid; e < n; e += stride) {
-			const int t = ts[e / F];
+			const size_t b = e / F;
+			size_t p = e - b * F;
+			const int t = ts[b] & ~kFlipBit;
 			const float z = normal_at(seed, offset, e);
+			const size_t r = index ? index[b] : b;
+			if (ts[b] & kFlipBit) {
+				const unsigned col = F >> 32 ? (unsigned)(p % width) : (unsigned)p % width;
+				p = (p - col) + (width - 1 - col);
+			}
+			const float x = r < records ? data[r * F + p] : 0.f;
 			eps[e] = z;
-			xt[e] = sab[t] * x0[e] + s1m[t] * z;
+			xt[e] = noise1_scalar(sab[t], x, s1m[t], z);
+			if (x0_out) x0_out[e] = x;
 		}
 	}
 }
@@ -354,20 +403,31 @@ bla_status bla_time_embedding_f32(void* stream, const int* d_t, int batch, int t
 	return BLA_OK;
 }
 
-bla_status bla_diffusion_noise_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, int time_dim, unsigned long long seed,
-                                   unsigned long long pass, int* d_t, float* d_eps, float* d_xt, float* d_temb) {
+bla_status bla_diffusion_noise_gather_f32(const bla_diffusion* d, void* stream, const float* d_data, size_t records, const unsigned int* d_index, int flip, int width,
+                                          const int* d_labels, int* d_labels_out, int batch, size_t image_floats, int time_dim, unsigned long long seed,
+                                          unsigned long long pass, int* d_t, float* d_eps, float* d_xt, float* d_temb, float* d_x0) {
 	bla_status st = require_ready();
 	if (st) return st;
 	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
-	BLA_REQUIRE(d_x0 && d_t && d_eps && d_xt && d_temb, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(d_data && d_t && d_eps && d_xt && d_temb, BLA_ERR_INVALID, "null argument");
 	BLA_REQUIRE(batch <= kMaxNoiseBatch, BLA_ERR_INVALID, "batch %d > %d", batch, kMaxNoiseBatch);
 	BLA_REQUIRE(pass < (1ull << 32), BLA_ERR_INVALID, "pass %llu does not fit the stream offset pass << 32", pass);
-	const int vec = image_floats % 4 == 0 && ((uintptr_t)d_x0 | (uintptr_t)d_eps | (uintptr_t)d_xt) % 16 == 0;
+	BLA_REQUIRE(width >= 1 && image_floats % (size_t)width == 0, BLA_ERR_INVALID, "image_floats %zu is not a whole number of rows of width %d", image_floats, width);
+	const int vec = image_floats % 4 == 0 && width % 4 == 0 &&
+	                ((uintptr_t)d_data | (uintptr_t)d_eps | (uintptr_t)d_xt | (uintptr_t)d_x0) % 16 == 0;
 	const size_t n = (size_t)batch * image_floats;
-	hipLaunchKernelGGL(noise_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x0, batch, image_floats, time_dim, seed, pass << 32,
-	                   d->steps, d->table, d_t, d_eps, d_xt, d_temb, vec);
+	hipLaunchKernelGGL(noise_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_data, records, d_index, flip ? 1 : 0, (unsigned)width,
+	                   d_labels, d_labels_out, batch, image_floats, time_dim, seed, pass << 32, d->steps, d->table, d_t, d_eps, d_xt, d_temb, d_x0, vec);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
+}
+
+// the gathering launch on the batch as it stands: records 0 .. batch-1, nothing mirrored.  Rows of 4 (or, when image_floats % 4 != 0, of 1) are never
+// looked at without flips and keep the float4 path open to exactly the shapes that had it before
+bla_status bla_diffusion_noise_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, int time_dim, unsigned long long seed,
+                                   unsigned long long pass, int* d_t, float* d_eps, float* d_xt, float* d_temb) {
+	return bla_diffusion_noise_gather_f32(d, stream, d_x0, (size_t)(batch > 0 ? batch : 0), nullptr, 0, image_floats % 4 == 0 ? 4 : 1, nullptr, nullptr, batch,
+	                                      image_floats, time_dim, seed, pass, d_t, d_eps, d_xt, d_temb, nullptr);
 }
 
 bla_status bla_diffusion_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, int batch, size_t image_floats, int t,

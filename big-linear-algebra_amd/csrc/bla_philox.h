@@ -41,8 +41,8 @@ __device__ __forceinline__ float normal_at(unsigned long long seed, unsigned lon
 	const int w = (int)(i % 4);
 	return w == 0 ? z.x : w == 1 ? z.y : w == 2 ? z.z : z.w;
 }
-__device__ __forceinline__ uint32_t u32_at(unsigned long long seed, unsigned long long offset, size_t i) {
-	const uint4 u = philox_block(seed, offset + i / 4, PHILOX_TAG_U32);
+__device__ __forceinline__ uint32_t u32_at(unsigned long long seed, unsigned long long offset, size_t i, uint32_t tag = PHILOX_TAG_U32) {
+	const uint4 u = philox_block(seed, offset + i / 4, tag);
 	const int w = (int)(i % 4);
 	return w == 0 ? u.x : w == 1 ? u.y : w == 2 ? u.z : u.w;
 }

@@ -1,4 +1,5 @@
-// bla_random.hip -- counter-based device random numbers (Philox4x32-10, bla_philox.h): uniform 32-bit words, normals, Bernoulli decisions.
+// bla_random.hip -- counter-based device random numbers (Philox4x32-10, bla_philox.h): uniform 32-bit words, normals, Bernoulli decisions, and a
+// permutation (the stable argsort of a stream of words).
 //
 // Not in the reference (its U-Net draws dropout decisions and noise from libc rand(), one call per element on the host).  Every value is a pure
 // function of (seed, offset, element index), so a stream can be restated anywhere -- tests/test_diffusion_gpu.py does it in numpy -- and any
@@ -92,6 +93,26 @@ bla_status launch_rand(void* stream, typename Kind<KIND>::T* out, size_t n, cons
 	return BLA_OK;
 }
 
+// The stable ascending argsort of keys [n] by counting: lane i holds key i, every workgroup streams all keys through LDS in tiles (each LDS read is
+// one address for the whole wave: a broadcast), rank_i = #{j : key_j < key_i or (key_j == key_i and j < i)} -- one 64-bit compare of (key, index)
+// pairs -- and out[rank_i] = i.  The pairs are distinct, so the ranks are a permutation of 0 .. n-1: every store lands inside out [n], and no two
+// lanes write the same element.  O(n^2) compares, meant for a shuffle once per epoch.
+constexpr int kRankTile = 2048;
+__global__ void __launch_bounds__(kThreads) rank_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ out) {
+	__shared__ uint32_t tile[kRankTile];
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	const unsigned long long mine = i < n ? ((unsigned long long)keys[i] << 32) | i : 0;
+	uint32_t rank = 0;
+	for (uint32_t base = 0; base < n; base += kRankTile) {
+		const uint32_t count = n - base < (uint32_t)kRankTile ? n - base : (uint32_t)kRankTile;
+		__syncthreads();
+		for (uint32_t k = threadIdx.x; k < count; k += blockDim.x) tile[k] = keys[base + k];
+		__syncthreads();
+		for (uint32_t k = 0; k < count; k++) rank += ((((unsigned long long)tile[k] << 32) | (base + k)) < mine);
+	}
+	if (i < n) out[rank] = i;
+}
+
 }  // namespace
 }  // namespace bla
 
@@ -114,6 +135,18 @@ bla_status bla_rand_bernoulli_u8(void* stream, unsigned char* d_out, size_t n, f
 	const double t = std::floor((double)p * 4294967296.0);
 	RandArgs a = {seed, offset, 0.f, 0.f, (unsigned long long)(t < 0 ? 0.0 : (t > 4294967296.0 ? 4294967296.0 : t))};
 	return launch_rand<KIND_BERNOULLI>(stream, d_out, n, a);
+}
+
+bla_status bla_rand_permutation_u32(void* stream, unsigned int* d_out, unsigned int* d_keys, size_t n, unsigned long long seed, unsigned long long offset) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if (n == 0) return BLA_OK;
+	BLA_REQUIRE(n <= ((size_t)1 << 20), BLA_ERR_INVALID, "n %zu > 2^20", n);
+	BLA_REQUIRE(d_out && d_keys && d_out != d_keys && (uintptr_t)d_out % 4 == 0, BLA_ERR_INVALID, "outputs null, the same or not 4-byte aligned");
+	if ((st = bla_rand_u32(stream, d_keys, n, seed, offset))) return st;
+	hipLaunchKernelGGL(rank_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, pick_stream(stream), (const uint32_t*)d_keys, (uint32_t)n, d_out);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
 }
 
 }  // extern "C"

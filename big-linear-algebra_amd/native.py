@@ -136,7 +136,11 @@ SIGNATURES = {
     "bla_mnist_nn_dp_step": (_I, [_VP, _VP, _VP, _F, _I]), "bla_mnist_nn_dp_step_direct": (_I, [_VP, _VP, _VP, _F, _I]),
     "bla_rand_u32": (_I, [_VP, _VP, _SZ, _U64, _U64]), "bla_rand_normal_f32": (_I, [_VP, _VP, _SZ, _F, _F, _U64, _U64]),
     "bla_rand_bernoulli_u8": (_I, [_VP, _VP, _SZ, _F, _U64, _U64]),
+    "bla_rand_permutation_u32": (_I, [_VP, _VP, _VP, _SZ, _U64, _U64]),
     "bla_adam_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _F, _F, _F, _I]), "bla_ema_f32": (_I, [_VP, _VP, _VP, _SZ, _F]),
+    "bla_sumsq_accumulate_f32": (_I, [_VP, _VP, _SZ, _VP, _VP]), "bla_clip_scale_f32": (_I, [_VP, _VP, _F, _F, _VP, _VP]),
+    "bla_adam_scaled_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _F, _F, _VP, _I]),
+    "bla_diffusion_noise_gather_f32": (_I, [_VP, _VP, _VP, _SZ, _VP, _I, _I, _VP, _VP, _I, _SZ, _I, _U64, _U64, _VP, _VP, _VP, _VP, _VP]),
     "bla_diffusion_create": (_I, [C.POINTER(_VP), _I, _F, _F]), "bla_diffusion_destroy": (_I, [_VP]), "bla_diffusion_steps": (_I, [_VP]),
     "bla_diffusion_schedule": (_I, [_VP, _I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bla_time_embedding_f32": (_I, [_VP, _VP, _I, _I, _VP]),

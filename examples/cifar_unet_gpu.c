@@ -73,6 +73,19 @@
  *                                                      BLA_UNET_ETA (0 .. 1, default 0: deterministic) scales the noise, BLA_UNET_CLIP=1
  *                                                      clamps the predicted x_0 to [-1, 1].  Bad values stop the program before the device is
  *                                                      opened.  Without BLA_UNET_SAMPLE_STEPS `sample` is unchanged.
+ *   (not in the reference)                             The rest of the DDPM training recipe (Ho et al. 2020), all on the device, all opt-in:
+ *                                                      `fit` with BLA_UNET_SHUFFLE=1: every record is uploaded, epoch e takes the permutation
+ *                                                      bla_rand_permutation_u32(records, BLA_SEED, (e << 32) + 2^31) and its pass k the entries
+ *                                                      [k batch, (k + 1) batch), so the dropped tail differs per epoch (at most 2^20 records);
+ *                                                      BLA_UNET_FLIP=1: each image mirrored left to right with probability 1/2.  Either one
+ *                                                      makes the pass start with bla_diffusion_noise_gather_f32 (index, flips and labels in the
+ *                                                      noising launch; without shuffling the index is 0, 1, 2, ...).  BLA_ADAM_CLIP_NORM=<x>
+ *                                                      (x > 0, finite): the gradient of the whole model (the class table included) is clipped
+ *                                                      to global norm x -- bla_memset, bla_sumsq_accumulate_f32 per bucket, bla_clip_scale_f32
+ *                                                      with grad_scale 1 / batch, bla_adam_scaled_f32 -- and every logged pass prints a second
+ *                                                      line, `Grad norm: <the last pass's norm before clipping>`.  BLA_ADAM_WARMUP=<n> (an
+ *                                                      integer >= 1): pass p uses BLA_ADAM_LR * min(1, (p + 1) / n).  Bad values stop the
+ *                                                      program before the device is opened.  With none of the four `fit` is unchanged.
  *
  * BLA_UNET_DUMP=<dir> makes train write what it uploaded (params, x, time embedding, noise, dropout decisions) and what came back (prediction,
  * gradient bucket) as raw little-endian files; tests/test_c_unet.py compares those with the oracle.
@@ -577,6 +590,32 @@ static double env_ema_decay(void) {
 	if (*end || !(decay > 0 && decay < 1)) { fprintf(stderr, "fit: BLA_UNET_EMA=%s; the decay must lie strictly between 0 and 1 (e.g. 0.9999)\n", v); exit(1); }
 	return decay;
 }
+/* a flag of fit that takes 0 or 1 and nothing else (unset or empty: 0) */
+static int env_fit_flag(const char* name) {
+	const char* v = getenv(name);
+	if (!v || !*v || strcmp(v, "0") == 0) return 0;
+	if (strcmp(v, "1") != 0) { fprintf(stderr, "fit: %s=%s; the value must be 0 or 1\n", name, v); exit(1); }
+	return 1;
+}
+/* BLA_ADAM_CLIP_NORM=<x> for fit, x > 0 and finite; 0 = not set */
+static double env_clip_norm(void) {
+	const char* v = getenv("BLA_ADAM_CLIP_NORM");
+	if (!v || !*v) return 0;
+	char* end = NULL;
+	const double x = strtod(v, &end);
+	if (*end || !(x > 0) || !isfinite(x) || !isfinite((float)x)) { fprintf(stderr, "fit: BLA_ADAM_CLIP_NORM=%s; the norm must be positive and finite (e.g. 1)\n", v); exit(1); }
+	return x;
+}
+/* BLA_ADAM_WARMUP=<n> for fit, an integer >= 1; 0 = not set */
+static long env_warmup(void) {
+	const char* v = getenv("BLA_ADAM_WARMUP");
+	if (!v || !*v) return 0;
+	char* end = NULL;
+	errno = 0;
+	const long n = strtol(v, &end, 10);
+	if (*end || errno || n < 1) { fprintf(stderr, "fit: BLA_ADAM_WARMUP=%s; the warm-up is a whole number of passes >= 1\n", v); exit(1); }
+	return n;
+}
 /* exchanges the host tensors with another set of the same shapes */
 static void swap_sets(float** other) {
 	for (int t = 0; t < g_tensor_count; t++) { float* h = g_tensors[t].host; g_tensors[t].host = other[t]; other[t] = h; }
@@ -610,12 +649,16 @@ static float** load_ema_set(float* ema_table) {
 static void fit(int epochs, int batch) {
 	if (batch < 1 || epochs < 1) { fprintf(stderr, "fit: epochs and batch must be >= 1\n"); exit(1); }
 	const double ema_decay = env_ema_decay();
+	const int shuffle = env_fit_flag("BLA_UNET_SHUFFLE"), flip = env_fit_flag("BLA_UNET_FLIP"), gather = shuffle || flip;
+	const double clip_norm = env_clip_norm();
+	const long warmup = env_warmup();
 	const int classes = env_flag("BLA_UNET_CLASSES");
 	size_t records = 0;
 	uint8_t* labels = NULL;
 	float* data = read_training_set(&records, classes ? &labels : NULL);
 	const size_t per_epoch = records / batch;                                                   /* the last partial batch is dropped */
 	if (per_epoch == 0) { fprintf(stderr, "fit: %zu records, fewer than one batch of %d\n", records, batch); exit(1); }
+	if (shuffle && records > ((size_t)1 << 20)) { fprintf(stderr, "fit: BLA_UNET_SHUFFLE=1 takes at most 2^20 records, not %zu\n", records); exit(1); }
 	float* table = NULL;
 	const double p_uncond = atof(env_or("BLA_UNET_UNCOND", "0.1"));
 	if (classes) {
@@ -642,7 +685,8 @@ static void fit(int epochs, int batch) {
 	device_set_params(&dv);
 	bla_diffusion* diff;
 	CHECK(bla_diffusion_create(&diff, env_steps(), 1e-4f, 0.02f));
-	const size_t params = bla_unet_param_count(dv.net), drops = bla_unet_dropout_count(dv.net), used = per_epoch * batch;
+	/* a shuffled epoch draws from every record; otherwise the last partial batch is never seen and is not uploaded */
+	const size_t params = bla_unet_param_count(dv.net), drops = bla_unet_dropout_count(dv.net), used = shuffle ? records : per_epoch * batch;
 	float *d_data, *d_m, *d_v; int* d_t; double* d_loss;
 	CHECK(bla_malloc((void**)&d_data, used * IMAGE_FLOATS * sizeof(float)));
 	CHECK(bla_memcpy_h2d(d_data, data, used * IMAGE_FLOATS * sizeof(float), NULL));
@@ -661,7 +705,25 @@ static void fit(int epochs, int batch) {
 			CHECK(bla_memcpy_h2d(d_ema_table, ema_table, table_floats * sizeof(float), NULL));
 		}
 	}
-	float *d_table = NULL, *d_gtable = NULL, *d_tm = NULL, *d_tv = NULL, *d_dtemb = NULL; int *d_labels = NULL, *d_rows = NULL;
+	unsigned int *d_index = NULL, *d_keys = NULL;   /* BLA_UNET_SHUFFLE / BLA_UNET_FLIP: the epoch's record order (0, 1, 2, ... without shuffling) */
+	if (gather) {
+		CHECK(bla_malloc((void**)&d_index, used * sizeof(unsigned int)));
+		if (shuffle) {
+			CHECK(bla_malloc((void**)&d_keys, used * sizeof(unsigned int)));
+		} else {
+			unsigned int* order = malloc(used * sizeof(unsigned int));
+			for (size_t r = 0; r < used; r++) order[r] = (unsigned int)r;
+			CHECK(bla_memcpy_h2d(d_index, order, used * sizeof(unsigned int), NULL));
+			CHECK(bla_stream_sync(NULL));
+			free(order);
+		}
+	}
+	double *d_sumsq = NULL, *d_partials = NULL; float *d_scale = NULL, *d_norm = NULL;   /* BLA_ADAM_CLIP_NORM */
+	if (clip_norm > 0) {
+		CHECK(bla_malloc((void**)&d_sumsq, sizeof(double))); CHECK(bla_malloc((void**)&d_partials, BLA_SUMSQ_SCRATCH_DOUBLES * sizeof(double)));
+		CHECK(bla_malloc((void**)&d_scale, sizeof(float))); CHECK(bla_malloc((void**)&d_norm, sizeof(float)));
+	}
+	float *d_table = NULL, *d_gtable = NULL, *d_tm = NULL, *d_tv = NULL, *d_dtemb = NULL; int *d_labels = NULL, *d_rows = NULL, *d_batch_labels = NULL;
 	if (classes) {
 		int* lab = malloc(used * sizeof(int));
 		for (size_t r = 0; r < used; r++) lab[r] = labels[r];
@@ -674,6 +736,7 @@ static void fit(int epochs, int batch) {
 		CHECK(bla_malloc((void**)&d_tv, table_floats * sizeof(float))); CHECK(bla_memset(d_tv, 0, table_floats * sizeof(float), NULL));
 		CHECK(bla_malloc((void**)&d_dtemb, (size_t)batch * TIME_EMBED_DIM * sizeof(float)));
 		CHECK(bla_malloc((void**)&d_rows, batch * sizeof(int)));
+		if (gather) CHECK(bla_malloc((void**)&d_batch_labels, batch * sizeof(int)));
 		CHECK(bla_stream_sync(NULL));
 		free(lab);
 	}
@@ -683,10 +746,19 @@ static void fit(int epochs, int batch) {
 	const size_t passes = per_epoch * epochs;
 	size_t logged = 0;
 	for (size_t pass = 0; pass < passes; pass++) {
-		const float* x0 = d_data + (pass % per_epoch) * batch * IMAGE_FLOATS;
-		CHECK(bla_diffusion_noise_f32(diff, NULL, x0, batch, IMAGE_FLOATS, TIME_EMBED_DIM, seed, pass, d_t, dv.noise, dv.x, dv.temb));
+		const size_t k = pass % per_epoch;
+		const int* pass_labels = classes ? d_labels + k * batch : NULL;
+		if (gather) {   /* index, flips and labels inside the noising launch; a shuffled epoch starts with its permutation (Philox offsets: bla.h) */
+			if (shuffle && k == 0)
+				CHECK(bla_rand_permutation_u32(NULL, d_index, d_keys, records, seed, ((unsigned long long)(pass / per_epoch) << 32) + (1ull << 31)));
+			CHECK(bla_diffusion_noise_gather_f32(diff, NULL, d_data, used, d_index + k * batch, flip, IMAGE_SIDE, d_labels, d_batch_labels, batch, IMAGE_FLOATS,
+			                                     TIME_EMBED_DIM, seed, pass, d_t, dv.noise, dv.x, dv.temb, NULL));
+			pass_labels = d_batch_labels;
+		} else {
+			CHECK(bla_diffusion_noise_f32(diff, NULL, d_data + k * batch * IMAGE_FLOATS, batch, IMAGE_FLOATS, TIME_EMBED_DIM, seed, pass, d_t, dv.noise, dv.x, dv.temb));
+		}
 		if (classes)   /* the label dropout's Philox blocks start at (pass << 32) + 2^31, behind the dropout decisions' (bla.h) */
-			CHECK(bla_class_embedding_f32(NULL, d_table, CLASSES, d_labels + (pass % per_epoch) * batch, batch, TIME_EMBED_DIM, (float)p_uncond, seed,
+			CHECK(bla_class_embedding_f32(NULL, d_table, CLASSES, pass_labels, batch, TIME_EMBED_DIM, (float)p_uncond, seed,
 			                              ((unsigned long long)pass << 32) + (1ull << 31), d_rows, dv.temb));
 		CHECK(bla_rand_bernoulli_u8(NULL, dv.drop, drops, DROPOUT_RATE, seed, (unsigned long long)pass << 32));
 		CHECK(bla_unet_forward_f32(dv.net, NULL, dv.x, dv.temb, dv.drop));
@@ -696,9 +768,20 @@ static void fit(int epochs, int batch) {
 			CHECK(bla_class_embedding_grad_f32(NULL, d_dtemb, d_rows, batch, CLASSES, TIME_EMBED_DIM, d_gtable));
 		}
 		CHECK(bla_mse_accumulate_f32(NULL, bla_unet_output(dv.net), dv.noise, (size_t)batch * IMAGE_FLOATS, d_loss));
-		CHECK(bla_adam_f32(NULL, bla_unet_params(dv.net), bla_unet_grads(dv.net), d_m, d_v, params, (float)lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
-		if (classes)
-			CHECK(bla_adam_f32(NULL, d_table, d_gtable, d_tm, d_tv, table_floats, (float)lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
+		const float pass_lr = warmup ? (float)(lr * fmin(1.0, (double)(pass + 1) / (double)warmup)) : (float)lr;
+		if (clip_norm > 0) {   /* the global norm of the mean gradient over both buckets, the clipping coefficient and Adam's grad_scale all stay on the device */
+			CHECK(bla_memset(d_sumsq, 0, sizeof(double), NULL));
+			CHECK(bla_sumsq_accumulate_f32(NULL, bla_unet_grads(dv.net), params, d_sumsq, d_partials));
+			if (classes) CHECK(bla_sumsq_accumulate_f32(NULL, d_gtable, table_floats, d_sumsq, d_partials));
+			CHECK(bla_clip_scale_f32(NULL, d_sumsq, 1.0f / batch, (float)clip_norm, d_scale, d_norm));
+			CHECK(bla_adam_scaled_f32(NULL, bla_unet_params(dv.net), bla_unet_grads(dv.net), d_m, d_v, params, pass_lr, 0.9f, 0.999f, 1e-8f, 0.f, d_scale, (int)(pass + 1)));
+			if (classes)
+				CHECK(bla_adam_scaled_f32(NULL, d_table, d_gtable, d_tm, d_tv, table_floats, pass_lr, 0.9f, 0.999f, 1e-8f, 0.f, d_scale, (int)(pass + 1)));
+		} else {
+			CHECK(bla_adam_f32(NULL, bla_unet_params(dv.net), bla_unet_grads(dv.net), d_m, d_v, params, pass_lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
+			if (classes)
+				CHECK(bla_adam_f32(NULL, d_table, d_gtable, d_tm, d_tv, table_floats, pass_lr, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f / batch, (int)(pass + 1)));
+		}
 		if (ema_decay > 0) {   /* the warm-up keeps the early average from holding on to the initial draw */
 			const float decay = (float)fmin(ema_decay, (1.0 + pass) / (10.0 + pass));
 			CHECK(bla_ema_f32(NULL, d_ema, bla_unet_params(dv.net), params, decay));
@@ -706,10 +789,13 @@ static void fit(int epochs, int batch) {
 		}
 		if ((pass + 1) % log_every == 0 || pass + 1 == passes) {
 			double sum = 0;
+			float norm = 0;
 			CHECK(bla_memcpy_d2h(&sum, d_loss, sizeof sum, NULL));
+			if (clip_norm > 0) CHECK(bla_memcpy_d2h(&norm, d_norm, sizeof norm, NULL));
 			CHECK(bla_memset(d_loss, 0, sizeof(double), NULL));
 			CHECK(bla_stream_sync(NULL));
 			printf("Pass %zu:\tAvg loss: %f\n", pass, sum / ((double)(pass + 1 - logged) * batch * IMAGE_FLOATS));
+			if (clip_norm > 0) printf("Grad norm: %f\n", norm);
 			fflush(stdout);
 			logged = pass + 1;
 		}
@@ -737,9 +823,11 @@ static void fit(int epochs, int batch) {
 		CHECK(bla_stream_sync(NULL));
 		save_class_table(table);
 		CHECK(bla_free(d_labels)); CHECK(bla_free(d_table)); CHECK(bla_free(d_gtable)); CHECK(bla_free(d_tm)); CHECK(bla_free(d_tv));
-		CHECK(bla_free(d_dtemb)); CHECK(bla_free(d_rows));
+		CHECK(bla_free(d_dtemb)); CHECK(bla_free(d_rows)); CHECK(bla_free(d_batch_labels));
 		free(table);
 	}
+	if (gather) { CHECK(bla_free(d_index)); CHECK(bla_free(d_keys)); }
+	if (clip_norm > 0) { CHECK(bla_free(d_sumsq)); CHECK(bla_free(d_partials)); CHECK(bla_free(d_scale)); CHECK(bla_free(d_norm)); }
 	CHECK(bla_free(d_data)); CHECK(bla_free(d_m)); CHECK(bla_free(d_v)); CHECK(bla_free(d_t)); CHECK(bla_free(d_loss));
 	CHECK(bla_diffusion_destroy(diff));
 	inputs_free(&in); device_close(&dv);

@@ -429,12 +429,31 @@ BLA_API bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float*
 BLA_API bla_status bla_rand_u32(void* stream, unsigned int* d_out, size_t n, unsigned long long seed, unsigned long long offset);
 BLA_API bla_status bla_rand_normal_f32(void* stream, float* d_out, size_t n, float mean, float stddev, unsigned long long seed, unsigned long long offset);
 BLA_API bla_status bla_rand_bernoulli_u8(void* stream, unsigned char* d_out, size_t n, float p, unsigned long long seed, unsigned long long offset);
+/* A permutation from the stream, one per epoch for a shuffled training set: d_keys [n] = bla_rand_u32(seed, offset)[0..n); d_out [n] = the stable
+ * ascending argsort of d_keys (equal keys: lower index first) -- np.argsort(keys, kind="stable"), bit-reproducible.  A rank kernel, O(n^2) compares
+ * (2.5e9 for CIFAR-10's 50,000 records).  1 <= n <= 2^20, else BLA_ERR_INVALID; n = 0 does nothing.  The two buffers must differ. */
+BLA_API bla_status bla_rand_permutation_u32(void* stream, unsigned int* d_out, unsigned int* d_keys, size_t n, unsigned long long seed,
+                                            unsigned long long offset);
 /* Adam / AdamW over n floats in one pass (torch.optim.AdamW(foreach=False), step for step): g = grad_scale * grad; p *= 1 - lr * weight_decay;
  * m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2; p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).  The bias
  * corrections are formed in double on the host.  step >= 1 counts the updates so far, this one included; grad_scale = 1 / B for the U-Net's
  * gradients (summed over the images).  m and v start zeroed. */
 BLA_API bla_status bla_adam_f32(void* stream, float* d_params, const float* d_grads, float* d_m, float* d_v, size_t n, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, float grad_scale, int step);
+/* Global-norm gradient clipping without a host round trip (torch.nn.utils.clip_grad_norm_): bla_memset the accumulator, one
+ * bla_sumsq_accumulate_f32 per gradient bucket, bla_clip_scale_f32, then bla_adam_scaled_f32 on every bucket.  None of the three allocates or waits,
+ * so the sequence can be captured.
+ * *d_acc += sum_i a_i^2, double, fixed order: bit-reproducible run to run.  Many workgroups (partials into d_scratch [BLA_SUMSQ_SCRATCH_DOUBLES],
+ * combined in index order).  Any alignment and any n (0: nothing); 16-byte loads in the body.  A non-finite sum is passed on as it is. */
+#define BLA_SUMSQ_SCRATCH_DOUBLES 1024
+BLA_API bla_status bla_sumsq_accumulate_f32(void* stream, const float* d_a, size_t n, double* d_acc, double* d_scratch);
+/* norm = |grad_scale| sqrt(*d_sumsq); *d_scale = (float)(grad_scale * min(1, max_norm / (norm + 1e-6))), formed in double on the device;
+ * *d_norm (may be NULL) = (float)norm.  max_norm <= 0 or not finite: BLA_ERR_INVALID.  torch.nn.utils.clip_grad_norm_'s coefficient. */
+BLA_API bla_status bla_clip_scale_f32(void* stream, const double* d_sumsq, float grad_scale, float max_norm, float* d_scale, float* d_norm);
+/* bla_adam_f32 with grad_scale read from device memory: the clipped gradient is (*d_grad_scale) * grad, a single fp32 factor, and the update is bit
+ * for bit bla_adam_f32's with that value as grad_scale. */
+BLA_API bla_status bla_adam_scaled_f32(void* stream, float* d_params, const float* d_grads, float* d_m, float* d_v, size_t n, float lr, float beta1,
+                                       float beta2, float eps, float weight_decay, const float* d_grad_scale, int step);
 /* Exponential moving average of a bucket (the weights DDPM samples from, Ho et al. 2020): e <- e + w (p - e), w = 1 - decay formed in double on the
  * host and rounded to fp32 once, every operation rounded on its own -- bit-equal to numpy float32 e + float32(w) * (p - e).  decay in [0, 1] (else
  * BLA_ERR_INVALID; 1 leaves e as it is).  This applies the decay it is given: any warm-up (e.g. min(decay, (1 + step) / (10 + step)), what
@@ -455,6 +474,21 @@ BLA_API bla_status bla_time_embedding_f32(void* stream, const int* d_t, int batc
  * d_temb [batch][time_dim] = the embedding of t_b; all four written.  batch <= 4096. */
 BLA_API bla_status bla_diffusion_noise_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, int time_dim,
                                            unsigned long long seed, unsigned long long pass, int* d_t, float* d_eps, float* d_xt, float* d_temb);
+/* Batch assembly fused into the noising launch: exactly bla_diffusion_noise_f32's job, in one launch, on the batch whose image b is record
+ * d_index[b] of d_data [records][image_floats] (d_index NULL = records 0 .. batch-1).  Images are [C][H][W] with W = width; when flip is non-zero,
+ * image b is mirrored along its innermost axis (out[.., i] = in[.., width-1-i]) where bla_rand_bernoulli_u8(0.5, seed, (pass << 32) + 2^31 + 2^30)[b]
+ * is 1 (see the offset table below).  t_b, d_eps and d_temb are indexed by OUTPUT position as in bla_diffusion_noise_f32, so they depend on neither
+ * d_index nor flip, and d_xt is bit-equal to what bla_diffusion_noise_f32 writes for the same assembled batch and the same alignment of the buffers.
+ * d_x0 (may be NULL) receives the clean assembled batch; d_labels_out[b] = d_labels[d_index[b]] when both are given, ready for
+ * bla_class_embedding_f32.  An index >= records reads nothing: that image is all zero and its label -1 (which the class embedding skips).
+ * image_floats % width != 0: BLA_ERR_INVALID.  16-byte loads and stores when image_floats % 4 == 0, width % 4 == 0 and d_data, d_eps, d_xt, d_x0 are
+ * 16-byte aligned (a mirrored float4 is the float4 at the mirrored position with its components reversed), one element per lane otherwise.
+ * batch <= 4096. */
+BLA_API bla_status bla_diffusion_noise_gather_f32(const bla_diffusion* d, void* stream, const float* d_data /* [records][image_floats] */, size_t records,
+                                                  const unsigned int* d_index /* [batch]; NULL = 0 .. batch-1 */, int flip, int width,
+                                                  const int* d_labels /* [records], may be NULL */, int* d_labels_out /* [batch], may be NULL */, int batch,
+                                                  size_t image_floats, int time_dim, unsigned long long seed, unsigned long long pass, int* d_t, float* d_eps,
+                                                  float* d_xt, float* d_temb, float* d_x0 /* [batch][image_floats], may be NULL */);
 /* The DDPM ancestral step at t (sigma_t^2 = beta_t), in place: x <- (x - beta_t / sqrt(1 - alpha_bar_t) eps_hat) / sqrt(1 - beta_t) + sigma_t z,
  * z = bla_rand_normal_f32(batch * image_floats, 0, 1, seed, (t + 1) << 32) (offset 0 stays free for x_T), z = 0 at t = 0.  d_temb_next (may be
  * NULL): the same launch writes the embedding of t - 1 for every image ([batch][time_dim]; nothing at t = 0). */
@@ -497,7 +531,10 @@ BLA_API bla_status bla_mse_accumulate_f32(void* stream, const float* d_a, const 
  *
  * Philox offsets of a conditional training pass `pass` (bla_diffusion_noise_f32's layout above): noise and timesteps at pass << 32 (tags 0 and 1),
  * the dropout decisions at pass << 32 (tag 2, bla_unet_dropout_count() / 4 blocks), the label dropout at (pass << 32) + (1 << 31) (tag 2, batch / 4
- * blocks).  The two tag-2 ranges are disjoint as long as bla_unet_dropout_count() < 2^33, and both stay below the next pass's (pass + 1) << 32. */
+ * blocks, at most 1024), the horizontal flips of bla_diffusion_noise_gather_f32 at (pass << 32) + (1 << 31) + (1 << 30) (tag 2, batch / 4 blocks, at most
+ * 1024).  The three tag-2 ranges are disjoint as long as bla_unet_dropout_count() < 2^33, and all stay below the next pass's (pass + 1) << 32.
+ * A shuffled epoch e draws its permutation with bla_rand_permutation_u32 at (e << 32) + (1 << 31) (tag 0, at most 2^18 blocks), behind the timestep
+ * draws of pass e (tag 0 at e << 32, at most 1024 blocks). */
 
 /* Gradient of the time-embedding input: d_dtemb [B][time_dim] = dL/dtemb for the loss of the last bla_unet_backward_f32 (del_Y = 2 (pred - noise)).
  * The embedding feeds nothing but the 18 ResNet blocks' projections temb . W_k + bias_k, so dtemb[b] = sum_k W_k . dtb_k[b] with dtb_k[b] the per-image
