@@ -24,6 +24,24 @@ namespace bla {
 
 constexpr int kThreads = 256;
 
+// ---- bla_conv_last_plan: a record of what ran ---------------------------------------------------------------------------------------------------
+// Host side only, as bla_gemm_last_kernel: conv2d_forward / conv2d_backward reset it, every launch site of the family appends (bla_internal.h).
+static char g_plan[512] = "";
+static size_t g_plan_len = 0;
+static const char* g_plan_role = "fwd";
+static bool g_plan_pass = false, g_plan_prepared = false;   // the entry's word to launch_implicit: the epilogue runs as a pass behind it / the kernel matrix is the caller's prepared one
+void conv_plan_reset() { g_plan[0] = 0; g_plan_len = 0; g_plan_pass = g_plan_prepared = false; }
+void conv_plan_role(const char* role) { g_plan_role = role; }
+void conv_plan_note(const char* fmt, ...) {
+	if (g_plan_len + 1 >= sizeof(g_plan)) return;
+	va_list ap;
+	va_start(ap, fmt);
+	const int n = vsnprintf(g_plan + g_plan_len, sizeof(g_plan) - g_plan_len, fmt, ap);
+	va_end(ap);
+	if (n > 0) g_plan_len = std::min(g_plan_len + (size_t)n, sizeof(g_plan) - 1);
+}
+void conv_plan_begin() { conv_plan_note("%s%s:", g_plan_len ? " " : "", g_plan_role); }
+
 struct Geometry { int ho, wo, pt, pl; };
 
 // TF "SAME" geometry exactly as lib/conv.c:13-28,55-56 computes it (ceil on a float quotient).
@@ -969,6 +987,14 @@ static const float* padded_operand(hipStream_t s, const ConvArgs& a, float* room
 	return room;
 }
 
+static const char* padded_name(const ConvArgs& a) { return a.padded_src ? "caller" : ready_padded(a) ? "image" : "copy"; }
+// closes a forward-shaped product's plan token: the epilogue where no tile store or fold took it, the padded operand, a prepared kernel matrix
+static void note_forward_tail(bool fused, const char* pad) {
+	if (!fused) conv_plan_note(g_plan_pass ? "/ep=pass" : "/ep=none");
+	if (pad) conv_plan_note("/pad=%s", pad);
+	if (g_plan_prepared) conv_plan_note("/A=prep");
+}
+
 // one product of a convolution as the *_product constructors below made it (batch, strides and padded copy set)
 template <int MODE>
 static bla_status launch_implicit(hipStream_t s, ConvArgs& a) {
@@ -990,7 +1016,10 @@ static bla_status launch_implicit(hipStream_t s, ConvArgs& a) {
 		}
 		GatherProduct g = gather_product(a, 7, a.img, nullptr, nullptr);
 		g.A = ordered;
-		return gather_gemm(s, g, batch);
+		conv_plan_begin();
+		const bla_status st = gather_gemm(s, g, batch);
+		note_forward_tail(a.ep_fused_tiled, nullptr);
+		return st;
 	}
 	if (MODE == CONV_FWD ? plan.path != FWD_WSK : use_tiled_gather(a, batch, 2)) {
 		const int2* ptab;
@@ -1001,7 +1030,12 @@ static bla_status launch_implicit(hipStream_t s, ConvArgs& a) {
 		// forward: pad (and split by stride parity) once, then the B slab is fetched with the same 16-byte DMA as a dense operand; weight gradient: the
 		// transposed product on the padded copy -- taps are the rows, both operands stream in 16-byte chunks.  Else the bounds-checked gather.
 		const int mode = MODE == CONV_FWD ? (plan.path == FWD_TILED_PADDED ? 3 : 1) : (fits32 && a.g.wo % 4 == 0 && a.N % 4 == 0 ? 4 : 2);
-		if (mode == 1 || mode == 2) return gather_gemm(s, gather_product(a, mode, a.img, a.tab, ptab), batch);
+		conv_plan_begin();
+		if (mode == 1 || mode == 2) {
+			st = gather_gemm(s, gather_product(a, mode, a.img, a.tab, ptab), batch);
+			if (MODE == CONV_FWD) note_forward_tail(false, nullptr);
+			return st;
+		}
 		const int2 *taps, *pix;
 		st = get_padded_tables(s, a.g, &taps, &pix);
 		if (st) return st;
@@ -1014,7 +1048,10 @@ static bla_status launch_implicit(hipStream_t s, ConvArgs& a) {
 		if (st) return st;
 		g.img = padded_operand(s, a, (float*)((char*)ws + slab_bytes));
 		BLA_HIP(hipGetLastError());
-		return gather_gemm(s, g, batch);
+		st = gather_gemm(s, g, batch);
+		if (MODE == CONV_FWD) note_forward_tail(a.ep_fused_tiled, padded_name(a));
+		else conv_plan_note("/pad=%s", padded_name(a));
+		return st;
 	}
 	size_t slab_bytes;
 	dim3 grid;
@@ -1033,6 +1070,12 @@ static bla_status launch_implicit(hipStream_t s, ConvArgs& a) {
 	if (a.splits > 1)
 		hipLaunchKernelGGL(conv_slab_reduce_kernel, dim3(grid_for((size_t)a.M * a.N), (unsigned)(wgrad ? 1 : batch)), dim3(kThreads), 0, s, a);
 	BLA_HIP(hipGetLastError());
+	conv_plan_begin();
+	conv_plan_note("wsk/%s/s%d", vec ? "vec" : "scalar", a.psplits);
+	if (!wgrad) {   // (the 32x32 kernel applies the adds where it stores, or where it folds its slabs)
+		if (a.ep_bias || a.ep_out2) conv_plan_note("/ep=wsk");
+		note_forward_tail(a.ep_bias || a.ep_out2, nullptr);
+	}
 	return BLA_OK;
 }
 
@@ -1075,6 +1118,9 @@ static bla_status launch_backward_pair(hipStream_t s, ConvArgs& w, ConvArgs& d, 
 		hipLaunchKernelGGL(conv_slab_reduce_pair_kernel, dim3(rw + rd * (unsigned)batch), dim3(kThreads), 0, s, w, d, rw, rd);
 	}
 	BLA_HIP(hipGetLastError());
+	conv_plan_role("wskpair");
+	conv_plan_begin();
+	conv_plan_note("wsk/%s/s%d+wsk/%s/s%d", vw ? "vec" : "scalar", w.psplits, vd ? "vec" : "scalar", d.psplits);
 	return BLA_OK;
 }
 
@@ -1163,7 +1209,13 @@ static bla_status launch_tiled_pair(hipStream_t s, const ConvArgs& aw, const Con
 		gd.A = d_scratch;
 	}
 	BLA_HIP(hipGetLastError());
-	return gather_pair_products(s, batch, gw, w_slab, gd, d_slab);
+	conv_plan_role("pair");
+	conv_plan_begin();
+	st = gather_pair_products(s, batch, gw, w_slab, gd, d_slab);
+	conv_plan_note("/ep=none/padw=%s", padded_name(aw));
+	if (!window) conv_plan_note("/padd=%s", padded_name(ad));
+	if (prepared) conv_plan_note("/A=prep");
+	return st;
 }
 
 template <bool RELU>
@@ -1392,6 +1444,8 @@ static bla_status conv2d_forward(void* stream, const float* d_x, const float* d_
 	BLA_REQUIRE(d_x && d_kern && d_out, BLA_ERR_INVALID, "null operand");
 	hipStream_t s = pick_stream(stream);
 	Geometry gm = same_geometry(h, w, k, stride);
+	conv_plan_reset();
+	conv_plan_role("fwd");
 	BLA_REQUIRE((ep_add == nullptr) == (ep_out2 == nullptr), BLA_ERR_INVALID, "ep_add and ep_out2 go together");
 	if (thin_conv_applies(k, c_in, f_n, stride)) return thin_conv_forward(s, d_x, d_kern, d_out, batch, h, w, k, c_in, f_n, gm.pt, gm.pl, ep_bias, ep_bias_stride, ep_add, ep_out2);
 	ConvArgs a = fwd_product(d_x, d_kern, d_out, x_padded, batch, h, w, k, c_in, f_n, stride);
@@ -1400,7 +1454,9 @@ static bla_status conv2d_forward(void* stream, const float* d_x, const float* d_
 	const bool ep = ep_bias || ep_out2;
 	const FwdPlan plan = plan_forward(a, batch);
 	if (prepared && plan.path == FWD_TILED_WINDOW) a.prepared_A = prepared;   // (mode 1 of conv_kernel_prep_mode: the only prepared form a forward pass takes)
+	g_plan_prepared = a.prepared_A != nullptr;
 	if (ep && !plan.fuses_epilogue) {
+		g_plan_pass = true;
 		// the half-slab forward kernels apply the adds where they store their tiles (one pass over K, whole tiles) and the 32x32 kernel does for a single
 		// image; the other kernels carry no epilogue (the 32x32 kernel's knows one bias set): one pass behind them
 		st = launch_implicit<CONV_FWD>(s, a);
@@ -1536,16 +1592,20 @@ static bla_status conv2d_backward_parity(hipStream_t s, const float* d_del_y, co
 	BLA_HIP(hipGetLastError());
 	GatherProduct g = {};   // what the classes share: c_in x (image, class pixel) outputs gathered from the padded del_y
 	g.mode = 3; g.M = c_in; g.N = N; g.ldc = hc * wc; g.img = padded; g.ntab = t.tab[4]; g.H = hh; g.W = wh; g.HWo = hc * wc; g.img_stride = f_n * hh * wh;
+	conv_plan_begin();
+	conv_plan_note(one_launch ? "parity/one[" : "parity/each[");
 	if (one_launch) {
 		st = gather_gemm_classes(s, g, batch, sorted.c, d_tab, 4);
 		if (st) return st;
 	} else {
 		for (int cls = 0; cls < 4; cls++) {
 			g.A = gc[cls].A; g.K = g.lda = gc[cls].K; g.ktab = gc[cls].ktab; g.C = gc[cls].C;
+			if (cls) conv_plan_note(",");
 			st = gather_gemm(s, g, batch);
 			if (st) return st;
 		}
 	}
+	conv_plan_note("]");
 	hipLaunchKernelGGL(parity_interleave_kernel, dim3(grid_for((size_t)batch * c_in * h * (w / 2))), dim3(kThreads), 0, s, planes, d_del_x, (unsigned)(batch * c_in), h, w);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
@@ -1560,10 +1620,12 @@ static bla_status conv2d_backward(void* stream, const float* d_del_y, const floa
 	BLA_REQUIRE(d_del_y, BLA_ERR_INVALID, "null operand");
 	hipStream_t s = pick_stream(stream);
 	Geometry gm = same_geometry(h, w, k, stride);
+	conv_plan_reset();
 	if (thin_conv_applies(k, c_in, f_n, stride)) {
 		// a side of at most four channels: direct kernels (bla_conv_thin.hip); the data gradient is the forward form on del_y with the flipped kernels
 		if (d_del_kern) {
 			BLA_REQUIRE(d_x, BLA_ERR_INVALID, "weight gradient needs the forward input");
+			conv_plan_role("wgrad");
 			st = thin_conv_wgrad(s, d_del_y, d_x, d_del_kern, batch, h, w, k, c_in, f_n, gm.pt, gm.pl);
 			if (st) return st;
 		}
@@ -1571,6 +1633,7 @@ static bla_status conv2d_backward(void* stream, const float* d_del_y, const floa
 			BLA_REQUIRE(d_kern && d_scratch, BLA_ERR_INVALID, "data gradient needs the kernels and a scratch buffer of F*C*k*k floats");
 			hipLaunchKernelGGL(flip_kernels_kernel, dim3(grid_for((size_t)f_n * c_in * k * k)), dim3(kThreads), 0, s, d_kern, d_scratch, f_n, c_in, k);
 			BLA_HIP(hipGetLastError());
+			conv_plan_role("dgrad");
 			return thin_conv_forward(s, d_del_y, d_scratch, d_del_x, batch, h, w, k, f_n, c_in, k - 1 - gm.pt, k - 1 - gm.pl, nullptr, 0, nullptr, nullptr);
 		}
 		return BLA_OK;
@@ -1587,6 +1650,7 @@ static bla_status conv2d_backward(void* stream, const float* d_del_y, const floa
 		BLA_REQUIRE(d_x, BLA_ERR_INVALID, "weight gradient needs the forward input");
 		st = get_table(s, aw.g, &aw.tab);
 		if (st) return st;
+		conv_plan_role("wgrad");
 		st = launch_implicit<CONV_WGRAD>(s, aw);
 		if (st) return st;
 	}
@@ -1596,6 +1660,7 @@ static bla_status conv2d_backward(void* stream, const float* d_del_y, const floa
 			return BLA_ERR_UNDEFINED;
 		}
 		BLA_REQUIRE(d_kern && d_scratch, BLA_ERR_INVALID, "data gradient needs the kernels and a scratch buffer of F*C*k*k floats");
+		conv_plan_role("dgrad");
 		if (parity_dgrad_applies(batch, h, w, k, c_in, f_n, stride, gm)) return conv2d_backward_parity(s, d_del_y, d_kern, d_del_x, d_scratch, batch, h, w, k, c_in, f_n, gm);
 		// Stride s > 1 (the intended adjoint; the reference is undefined there): the same stride-1 convolution over del_y with s-1 zeros
 		// put between its pixels (dgrad_product) -- the U-Net's three down-convolutions (model/cifar_unet.c:1105,1111,1115).
@@ -1605,11 +1670,13 @@ static bla_status conv2d_backward(void* stream, const float* d_del_y, const floa
 			if (st) return st;
 			hipLaunchKernelGGL(dilate_kernel, dim3(grid_for(ad.img_stride * batch)), dim3(kThreads), 0, s, d_del_y, (float*)ws, batch * f_n, gm.ho, gm.wo, stride, ad.g.h, ad.g.w);
 			BLA_HIP(hipGetLastError());
+			conv_plan_role("dgrad.dil");
 			ad.img = (const float*)ws;
 		}
 		st = get_table(s, ad.g, &ad.tab);
 		if (st) return st;
 		const bool window = plan_forward(ad, batch).path == FWD_TILED_WINDOW;
+		g_plan_prepared = prepared && stride == 1;
 		if (prepared && stride == 1) { if (window) ad.prepared_A = prepared; else ad.A = prepared; }   // conv_kernel_prep_mode 2 / 3: already flipped (and window-ordered)
 		else if (window) ad.flip_src = d_kern;      // flipped and window-ordered in one pass, inside launch_implicit
 		else {
@@ -1649,6 +1716,47 @@ bla_status bla_conv2d_forward_batched_f32(void* stream, const float* d_x, const 
 bla_status bla_conv2d_backward_batched_f32(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x,
                                            float* d_scratch, int batch, int h, int w, int k, int c_in, int f_n, int stride) {
 	return conv2d_backward(stream, d_del_y, d_x, d_kern, d_del_kern, d_del_x, d_scratch, batch, h, w, k, c_in, f_n, stride);
+}
+
+/* The record of what the last convolution call launched (bla.h has the grammar) */
+const char* bla_conv_last_plan(void) { return g_plan; }
+
+/* The operand forms the U-Net uses internally, as entry points: no kernel and no decision of their own */
+bla_status bla_conv2d_forward_fused_f32(void* stream, const float* d_x, const float* d_kern, float* d_out, int batch, int h, int w, int k, int c_in, int f_n, int stride,
+                                        const float* ep_bias, int ep_bias_stride, const float* ep_add, float* ep_out2, const float* x_padded, const float* prepared) {
+	return conv2d_forward(stream, d_x, d_kern, d_out, batch, h, w, k, c_in, f_n, stride, ep_bias, ep_add, ep_out2, ep_bias_stride, x_padded, prepared);
+}
+bla_status bla_conv2d_backward_prepared_f32(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x, float* d_scratch,
+                                            int batch, int h, int w, int k, int c_in, int f_n, int stride, const float* x_padded, const float* prepared, const float* dy_padded) {
+	return conv2d_backward(stream, d_del_y, d_x, d_kern, d_del_kern, d_del_x, d_scratch, batch, h, w, k, c_in, f_n, stride, x_padded, prepared, dy_padded);
+}
+int bla_conv_prep_mode(int batch, int h, int w, int k, int c_in, int f_n, int stride, int data_gradient) {
+	return conv_kernel_prep_mode(batch, h, w, k, c_in, f_n, stride, data_gradient != 0);
+}
+bla_status bla_conv_padded_layout(int h, int w, int k, int stride, int* w_out, int* wh, int* plane, int* pt, int* pl) {
+	BLA_REQUIRE(h > 0 && w > 0 && k > 0 && stride > 0 && w_out && wh && plane && pt && pl, BLA_ERR_INVALID, "bad padded-layout query");
+	const PadLayout L = conv_padded_layout(h, w, k, stride);
+	*w_out = L.w; *wh = L.wh; *plane = L.plane; *pt = L.pt; *pl = L.pl;
+	return BLA_OK;
+}
+bla_status bla_conv_prepare_kernels_f32(void* stream, const float* d_src, float* d_dst, int f_n, int c_n, int k, int mode) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(d_src && d_dst && f_n > 0 && c_n > 0 && k > 0 && mode >= 1 && mode <= 3, BLA_ERR_INVALID, "bad kernel preparation job");
+	BLA_REQUIRE(mode == 3 || (k == 3 && (mode == 1 ? c_n : f_n) % 16 == 0), BLA_ERR_INVALID, "window order needs 3x3 kernels and channel groups of 16");
+	hipStream_t s = pick_stream(stream);
+	const KernelPrepJob job = {d_src, d_dst, f_n, c_n, k, mode};
+	KernelPrepJob* d_job = nullptr;       // the one-entry job table in device memory
+	BLA_HIP(hipMalloc((void**)&d_job, sizeof(job)));
+	hipError_t e = hipMemcpyAsync(d_job, &job, sizeof(job), hipMemcpyHostToDevice, s);
+	if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the pageable source must stay alive until the copy is done)
+	if (e == hipSuccess) {
+		st = conv_prepare_kernels(stream, d_job, 1, (size_t)f_n * c_n * k * k);
+		e = hipStreamSynchronize(s);
+	}
+	(void)hipFree(d_job);
+	if (e != hipSuccess) return hip_fail(e, "bla_conv_prepare_kernels_f32");
+	return st;
 }
 
 bla_status bla_group_norm_f32(void* stream, const float* d_in, float* d_out, float* d_stdevs, float* d_means, int channels, int group_size, int hw) {

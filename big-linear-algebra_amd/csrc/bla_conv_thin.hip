@@ -200,6 +200,8 @@ bla_status thin_conv_forward(hipStream_t s, const float* x, const float* kern, f
 		else hipLaunchKernelGGL(thin_few_outputs_kernel<1>, grid, dim3(256), lds, s, x, kern, out, h, w, c_in, f_n, pt, pl, ep_bias, ep_bias_stride, ep_add, ep_out2);
 	}
 	BLA_HIP(hipGetLastError());
+	conv_plan_begin();
+	conv_plan_note(ep_bias || ep_out2 ? "thin/ep=thin" : "thin");
 	return BLA_OK;
 }
 
@@ -224,6 +226,8 @@ bla_status thin_conv_wgrad(hipStream_t s, const float* del_y, const float* x, fl
 	BLA_HIP(hipGetLastError());
 	hipLaunchKernelGGL(thin_wgrad_fold_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const float*)ws, del_kern, total, chunks);
 	BLA_HIP(hipGetLastError());
+	conv_plan_begin();
+	conv_plan_note("thin");
 	return BLA_OK;
 }
 

@@ -78,6 +78,15 @@ static size_t window_lds_bytes(int W) {
 // hs: the half-slab instantiation of modes 3 and 4; window: mode 7's image row width (16 or 32; 0 for the other modes).
 namespace { struct GatherPlan { GemmArgs a; dim3 grid; size_t lds, slab_floats; bool hs; int window; }; }
 
+// the part of a plan token (bla_conv_last_plan) a gathered product knows: mode, half-slab ("hs") or older form, window width, K splits, and the site of a
+// fused epilogue -- the tile store or the fold of the slabs
+static void note_product(const GatherProduct& g, const GatherPlan& p) {
+	if (g.mode == 7) conv_plan_note("m7w%d", p.window);
+	else if (g.mode == 1) conv_plan_note("m1");
+	else conv_plan_note("m%d%s/s%d", g.mode, p.hs ? "hs" : "", p.a.splits);
+	if (g.ep.bias || g.ep.out2) conv_plan_note(p.a.splits == 1 ? "/ep=tile" : "/ep=fold");
+}
+
 // the fields of a gathered product's GemmArgs that every form shares (gather_plan, gather_gemm_classes)
 static GemmArgs gather_args(const GatherProduct& g) {
 	GemmArgs a = {};
@@ -112,6 +121,7 @@ bla_status gather_gemm_classes(hipStream_t s, const GatherProduct& g, int batch,
 	const dim3 grid((unsigned)(a.tiles_m * a.tiles_n), (unsigned)ncls, 1), block(256);
 	hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 3, false, true>), grid, block, 2 * (128 + 128) * 16 * sizeof(float), s, a);
 	BLA_HIP(hipGetLastError());
+	conv_plan_note("m3hs/x%d", ncls);
 	return BLA_OK;
 }
 
@@ -200,6 +210,7 @@ bla_status gather_gemm(hipStream_t s, const GatherProduct& g, int batch) {
 	else if (g.mode == 3) hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 3>), p.grid, block, p.lds, s, p.a);
 	else hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, true, 1, 2, false, 4>), p.grid, block, p.lds, s, p.a);
 	BLA_HIP(hipGetLastError());
+	note_product(g, p);
 	return gather_fold(s, p, g.ep);
 }
 
@@ -228,6 +239,7 @@ bla_status gather_pair_products(hipStream_t s, int batch, const GatherProduct& w
 	else if (pd.window) hipLaunchKernelGGL((gather_pair_kernel<7, 16>), grid, block, lds, s, pw.a, pd.a, blocks_w, wx, wz, dx, dz);
 	else hipLaunchKernelGGL((gather_pair_kernel<3, 0>), grid, block, lds, s, pw.a, pd.a, blocks_w, wx, wz, dx, dz);
 	BLA_HIP(hipGetLastError());
+	note_product(w, pw); conv_plan_note("+"); note_product(d, pd);
 	st = gather_fold(s, pw, w.ep);
 	if (st) return st;
 	return gather_fold(s, pd, d.ep);

@@ -97,6 +97,12 @@ struct PadLayout { int w, wh, plane, pt, pl; };      // plane = 0: none
 PadLayout conv_padded_layout(int h, int w, int k, int stride);
 struct PadOut { float* dst; PadLayout L; };          // a producer's second output: dst[plane_index * L.plane + (y + L.pt) * L.wh + x + L.pl], halo zeroed once by the owner
 
+// bla_conv_last_plan(): what the last conv2d_forward / conv2d_backward call launched, one token per product (bla.h has the grammar).  Host side only: the
+// entry resets the record, says whose product comes next (role: fwd, wgrad, dgrad, dgrad.dil) and every launch site of the family writes its part
+void conv_plan_reset();
+void conv_plan_role(const char* role);
+void conv_plan_begin();                       // starts a token: " <role>:"
+void conv_plan_note(const char* fmt, ...);    // appends to the token
 // bla_conv_thin.hip: direct convolutions for at most four channels on one side (stride 1, k 1 or 3): forward with the optional epilogue, weight gradient
 bool thin_conv_applies(int k, int c_in, int f_n, int stride);
 bla_status thin_conv_forward(hipStream_t s, const float* x, const float* kern, float* out, int batch, int h, int w, int k, int c_in, int f_n, int pt, int pl,

@@ -89,6 +89,11 @@ SIGNATURES = {
     "bla_conv_forward_f32": (_I, [_VP] * 7 + [_I] * 6), "bla_conv_backward_f32": (_I, [_VP] * 9 + [_I] * 6),
     "bla_conv2d_forward_f32": (_I, [_VP] * 4 + [_I] * 6), "bla_conv2d_backward_f32": (_I, [_VP] * 7 + [_I] * 6),
     "bla_conv2d_forward_batched_f32": (_I, [_VP] * 4 + [_I] * 7), "bla_conv2d_backward_batched_f32": (_I, [_VP] * 7 + [_I] * 7),
+    "bla_conv_last_plan": (C.c_char_p, []),
+    "bla_conv2d_forward_fused_f32": (_I, [_VP] * 4 + [_I] * 7 + [_VP, _I, _VP, _VP, _VP, _VP]),
+    "bla_conv2d_backward_prepared_f32": (_I, [_VP] * 7 + [_I] * 7 + [_VP] * 3),
+    "bla_conv_prepare_kernels_f32": (_I, [_VP, _VP, _VP, _I, _I, _I, _I]), "bla_conv_prep_mode": (_I, [_I] * 8),
+    "bla_conv_padded_layout": (_I, [_I] * 4 + [C.POINTER(_I)] * 5),
     "bla_group_norm_f32": (_I, [_VP] * 5 + [_I] * 3), "bla_group_norm_ddx_f32": (_I, [_VP] * 6 + [_I] * 3),
     "bla_relu_mask_f32": (_I, [_VP, _VP, _VP, _VP, _SZ]), "bla_dropout_f32": (_I, [_VP, _VP, _VP, _VP, _SZ]),
     "bla_dropout_mask_f32": (_I, [_VP, _VP, _VP, _SZ]), "bla_nearest_neighbours_f32": (_I, [_VP, _VP, _VP] + [_I] * 6),

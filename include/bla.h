@@ -285,6 +285,39 @@ BLA_API bla_status bla_conv2d_forward_batched_f32(void* stream, const float* d_x
                                                   int c_in, int f_n, int stride);
 BLA_API bla_status bla_conv2d_backward_batched_f32(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern,
                                                    float* d_del_x, float* d_scratch, int batch, int h, int w, int k, int c_in, int f_n, int stride);
+/* What the last bla_conv2d_* call launched (host side only, as bla_gemm_last_kernel): reset on entry to every forward / backward call, one token per product
+ * in launch order, separated by spaces.  A token is <role>:<path>[/<attribute>...]:
+ *   role   fwd, wgrad, dgrad, dgrad.dil (the data gradient on a zero-dilated del_y); pair (both gradients in one launch of the tiled kernels, weight
+ *          gradient + data gradient); wskpair (the same on the 32x32 kernel)
+ *   path   m1 / m2/sN      the bounds-checked tiled gather (forward shape / weight gradient), N = K splits
+ *          m3hs/sN, m3/s1  the padded copy on the half-slab kernel with its taps cut over N workgroups, or on the older form
+ *          m4hs/sN, m4/sN  the weight gradient on the padded copy, half-slab or older form
+ *          m7w16, m7w32    the image window, rows of 16 or 32 pixels
+ *          wsk/vec/sN, wsk/scalar/sN   the 32x32 wave-split-K kernel with 16-byte or 4-byte loads of its dense operand, N = K splits
+ *          parity/one[m3hs/x4]         the stride-2 data gradient by output parity, four classes in one launch
+ *          parity/each[m3hs/sN,...]    ... class by class
+ *          thin            the direct kernels for at most four channels on one side
+ *   attributes   ep=tile|fold|pass|wsk|thin|none  where the epilogue was applied: the tile store, the fold of the K-split slabs, a pass behind the product,
+ *                                                 inside the 32x32 (thin) kernel; none = the call had no epilogue
+ *                pad=caller|image|copy            the padded operand: the caller's, the image itself, a copy made by the call (pair: padw / padd)
+ *                A=prep                           the product read the caller's prepared kernel matrix */
+BLA_API const char* bla_conv_last_plan(void);
+/* The operand forms the U-Net uses internally, as entry points (no kernel and no decision of their own).
+ * bla_conv2d_forward_fused_f32: out = conv + ep_bias[image * ep_bias_stride + channel]; ep_out2 = out + ep_add (ep_add and ep_out2 go together; any may be NULL).
+ * x_padded / dy_padded: zero-padded copies of x / del_y in bla_conv_padded_layout(h, w, k, stride) -- per plane `plane` floats, rows of `wh` floats, the
+ * image at row pt, column pl, zeros elsewhere (plane = 0: this geometry has none); ignored by the paths that gather from no padded copy.
+ * prepared: the kernels in the form bla_conv_prep_mode names for this convolution's forward (data_gradient = 0) or data-gradient product -- 0: none is
+ * taken; 1: window order [F][(g, tap, c16)]; 2: flipped and transposed, window order [C][(g, tap, f16)]; 3: flipped and transposed [C][F][k][k] --
+ * written by bla_conv_prepare_kernels_f32 (mode 1, 2: 3x3 kernels, the grouped channel count a multiple of 16). */
+BLA_API bla_status bla_conv2d_forward_fused_f32(void* stream, const float* d_x, const float* d_kern, float* d_out, int batch, int h, int w, int k, int c_in, int f_n,
+                                                int stride, const float* ep_bias, int ep_bias_stride, const float* ep_add, float* ep_out2, const float* x_padded,
+                                                const float* prepared);
+BLA_API bla_status bla_conv2d_backward_prepared_f32(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x,
+                                                    float* d_scratch, int batch, int h, int w, int k, int c_in, int f_n, int stride, const float* x_padded,
+                                                    const float* prepared, const float* dy_padded);
+BLA_API bla_status bla_conv_prepare_kernels_f32(void* stream, const float* d_src, float* d_dst, int f_n, int c_n, int k, int mode);
+BLA_API int bla_conv_prep_mode(int batch, int h, int w, int k, int c_in, int f_n, int stride, int data_gradient);
+BLA_API bla_status bla_conv_padded_layout(int h, int w, int k, int stride, int* w_out, int* wh, int* plane, int* pt, int* pl);
 /* group_norm / group_norm_ddx, lib/norm.c:5-93, on [C][H*W]; quirk Q3 kept (epsilon == 0, "stdevs" holds the variance,
  * out = (x - mean) / variance).  Note the reference's argument orders (lib/norm.h:6-7). */
 BLA_API bla_status bla_group_norm_f32(void* stream, const float* d_in, float* d_out, float* d_stdevs, float* d_means, int channels, int group_size, int hw);

@@ -367,5 +367,8 @@ def test_headline_shapes_batch_64_against_the_oracle(dev, ora, shape):
 def test_tiled_gather_straight_from_the_image(dev, ora, shape):
     """Stride-1 geometries that stress the tiled gather paths' edge handling -- 1x1 and even kernels, tiles that straddle images, maps whose rows are one
     or two 16-byte chunks -- against the oracle like the shapes above (same checks, same tolerances).  (Written for the unpadded tap-major kernels of
-    commit 77757e6, which were correct on all of them and slower than the padded copy; the shapes now run the padded / window / checked paths.)"""
+    commit 77757e6, which were correct on all of them and slower than the padded copy.  On 256 CUs every one of these shapes now runs the padded-copy
+    kernels: the half-slab forward and data gradient, in one pass or with the taps cut over workgroups (the 1x1 case on the image as its own padded
+    copy), and the half-slab weight gradient in a launch of its own.  None reaches the image window or the bounds-checked gather: tests/test_conv_paths_gpu.py drives those,
+    and asserts by name which path ran.)"""
     test_batched_conv_tiled_gather_kernel(dev, ora, shape)
