@@ -1,5 +1,6 @@
 // bla_diffusion.hip -- what turns the U-Net of model/cifar_unet.c into a DDPM (Ho, Jain, Abbeel 2020): the linear beta schedule, the forward noising
-// of a training batch, the sinusoidal time embedding, the ancestral sampler step and the sampling loop around bla_unet_forward_f32.
+// of a training batch, the sinusoidal time embedding, the ancestral sampler step and the sampling loop around bla_unet_forward_f32, and the held-out
+// evaluation of the trained model (the variational bound, per image).
 //
 // The reference has the network (time embedding input, noise prediction, MSE against the noise) but never writes the embedding (:535), never noises
 // an image at a timestep and leaves run() empty (:1936).  Random draws come from the Philox streams of bla_philox.h (see include/bla.h), so every
@@ -9,7 +10,9 @@
 //   step   (seed, t):     z = normal(seed, (t + 1) << 32)[0 .. B*F) (0 at t = 0);  x <- (x - beta_t / sqrt(1 - abar_t) eps_hat) / sqrt(alpha_t) + sqrt(beta_t) z
 //   DDIM   (seed, t):     the same z stream, drawn only when sigma > 0;  x0^ = (x - sqrt(1 - abar_t) eps_hat) / sqrt(abar_t) (clamped to [-1, 1] on request),
 //                         x <- sqrt(abar_p) x0^ + sqrt(1 - abar_p - sigma^2) eps_hat + sigma z  (Song, Meng, Ermon 2021; abar_p = 1 past the last step)
-// The schedule is formed in double on the host at create time; the kernels read fp32 tables of the per-step coefficients.  The time embedding is
+//   eval   (seed, t):     eps = normal(seed, offset_base + ((t + 1) << 32))[0 .. B*F), x_t as in noise at the given t; then per image, in double, its term of
+//                         the variational bound: F c_t + w_t sum (eps - eps_hat)^2 at t >= 1, the discretised decoder's -sum ln p at t = 0 (Ho et al. eq. 5)
+// The schedule is formed in double on the host at create time; the kernels read fp32 tables of the per-step coefficients (the evaluation: doubles).  The time embedding is
 // the one examples/cifar_unet_gpu.c computes for BLA_UNET_TIMESTEP, evaluated in double: at t ~ 1000 its arguments reach 1000 rad, where an fp32
 // product t * w_i alone is off by ~6e-5.
 #include "bla_internal.h"
@@ -29,6 +32,11 @@ struct bla_diffusion {
 	size_t xg_floats = 0;
 	int* rows = nullptr;
 	int rows_count = 0;
+	double* vlb = nullptr;         // device, 2 x steps: c_t, w_t of bla_diffusion_vlb_weights (0 at t = 0)
+	float* ev = nullptr;           // the evaluation loop's eps and x_t, [2][B][C][H][W], and its embedding [B][time_dim] (grow on first use)
+	size_t ev_floats = 0;
+	float* ev_temb = nullptr;
+	size_t ev_temb_floats = 0;
 };
 
 namespace {
@@ -239,6 +247,161 @@ __global__ void __launch_bounds__(1024) sq_diff_sum_kernel(const float* __restri
 	}
 }
 
+// ---- held-out evaluation: the variational bound of Ho et al. 2020, eq. 5 (include/bla.h) -------------------------------------------------------
+// noise_kernel's job at timesteps that are given, not drawn: d_t [batch] (NULL: every image at t_const), eps = normal(seed, offset), x_t by noise1_vec /
+// noise1_scalar (noise_kernel's bits on either path).  An image whose t lies outside [0, steps) gets zero rows of x_t and of the embedding.
+__global__ void __launch_bounds__(kThreads) noise_at_kernel(const float* __restrict__ x0, int batch, size_t F, int dim, const int* __restrict__ d_t, int t_const,
+                                                            unsigned long long seed, unsigned long long offset, int steps, const float* __restrict__ table,
+                                                            float* __restrict__ eps, float* __restrict__ xt, float* __restrict__ temb, int vec) {
+	__shared__ int ts[kMaxNoiseBatch];
+	for (int b = threadIdx.x; b < batch; b += blockDim.x) {
+		const int t = d_t ? d_t[b] : t_const;
+		ts[b] = t >= 0 && t < steps ? t : -1;
+	}
+	__syncthreads();
+	const float* sab = table + TAB_SQRT_AB * steps;
+	const float* s1m = table + TAB_SQRT_1MAB * steps;
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	const size_t ne = (size_t)batch * dim;
+	for (size_t i = tid; i < ne; i += stride) {
+		const int t = ts[i / dim];
+		temb[i] = t >= 0 ? temb_value(t, (int)(i % dim), dim) : 0.f;
+	}
+	const size_t n = (size_t)batch * F;
+	if (vec) {   // F % 4 == 0, every pointer 16-byte aligned: Philox block q <-> float4 q, one image per float4
+		for (size_t q = tid; q < n / 4; q += stride) {
+			const int t = ts[(4 * q) / F];
+			const float4 z = philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL));
+			reinterpret_cast<float4*>(eps)[q] = z;
+			float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+			if (t >= 0) {
+				const float4 x = reinterpret_cast<const float4*>(x0)[q];
+				const float a = sab[t], c = s1m[t];
+				r = make_float4(noise1_vec(a, x.x, c, z.x), noise1_vec(a, x.y, c, z.y), noise1_vec(a, x.z, c, z.z), noise1_vec(a, x.w, c, z.w));
+			}
+			reinterpret_cast<float4*>(xt)[q] = r;
+		}
+	} else {
+		for (size_t e = tid; e < n; e += stride) {
+			const int t = ts[e / F];
+			const float z = normal_at(seed, offset, e);
+			eps[e] = z;
+			xt[e] = t >= 0 ? noise1_scalar(sab[t], x0[e], s1m[t], z) : 0.f;
+		}
+	}
+}
+
+// The 256 per-lane partials of a workgroup summed through LDS in a fixed tree (no atomics: bit-reproducible); the total is returned to thread 0
+__device__ __forceinline__ double block_sum(double v, double* part) {
+	part[threadIdx.x] = v;
+	__syncthreads();
+	for (int s = kThreads / 2; s > 0; s >>= 1) {
+		if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+		__syncthreads();
+	}
+	const double total = part[0];
+	__syncthreads();   // part is free for the next sum
+	return total;
+}
+
+// the decoder's constants at t = 0, formed in double on the host: mu = (x_t - k eps_hat) / sqrt_a, z = (x0 +- 1/255 - mu) / sigma
+struct DecoderArgs { double k, sqrt_a, sigma; };
+
+// -ln p of one element under the discretised Gaussian decoder of 8-bit data on [-1, 1] (Ho et al. 2020, section 3.3).  Phi through erfc on the side where it
+// is small: Phi(z) = erfc(-z / sqrt 2) / 2, 1 - Phi(z) = erfc(z / sqrt 2) / 2; the interior difference between two tails of the same side
+__device__ __forceinline__ double decoder_nll(double x0, double xt, double eh, const DecoderArgs& a) {
+	const double rs2 = 0.70710678118654752440;
+	const double mu = (xt - a.k * eh) / a.sqrt_a;
+	const double zp = (x0 + 1.0 / 255.0 - mu) / a.sigma, zm = (x0 - 1.0 / 255.0 - mu) / a.sigma;
+	double p;
+	if (x0 < -0.999) p = 0.5 * erfc(-zp * rs2);
+	else if (x0 > 0.999) p = 0.5 * erfc(zm * rs2);
+	else if (zm > 0) p = 0.5 * (erfc(zm * rs2) - erfc(zp * rs2));
+	else p = 0.5 * (erfc(-zp * rs2) - erfc(-zm * rs2));
+	return -log(p > 1e-12 ? p : 1e-12);
+}
+
+// One workgroup per image: sqerr_b = sum (eps - eps_hat)^2, and the image's term of the bound -- F c_t + w_t sqerr_b at t >= 1 (vlb: c_t, w_t), the decoder's
+// -sum ln p at t = 0.  The branch on t is uniform over the workgroup, so erfc and log run only in the workgroups at t = 0.  Every lane accumulates in
+// double over its elements in index order.  A t outside [0, steps): term NaN, sqerr 0, nothing read.
+__global__ void __launch_bounds__(kThreads) vlb_terms_kernel(const float* __restrict__ x0, const float* __restrict__ xt, const float* __restrict__ eps,
+                                                             const float* __restrict__ eps_hat, const int* __restrict__ d_t, int t_const, size_t F, int steps,
+                                                             const double* __restrict__ vlb, DecoderArgs dec, double* __restrict__ terms,
+                                                             double* __restrict__ sqerr, int vec) {
+	__shared__ double part[kThreads];
+	const int b = blockIdx.x, t = d_t ? d_t[b] : t_const;
+	if (t < 0 || t >= steps) {
+		if (threadIdx.x == 0) { terms[b] = __longlong_as_double(0x7ff8000000000000ll); if (sqerr) sqerr[b] = 0.0; }
+		return;
+	}
+	const size_t base = (size_t)b * F;
+	double sq = 0.0, nll = 0.0;
+	if (vec) {
+		const float4* e4 = reinterpret_cast<const float4*>(eps + base);
+		const float4* h4 = reinterpret_cast<const float4*>(eps_hat + base);
+		const float4* x4 = reinterpret_cast<const float4*>(x0 + base);
+		const float4* n4 = reinterpret_cast<const float4*>(xt + base);
+		for (size_t q = threadIdx.x; q < F / 4; q += kThreads) {
+			const float4 e = e4[q], h = h4[q];
+			const double dx = (double)e.x - (double)h.x, dy = (double)e.y - (double)h.y, dz = (double)e.z - (double)h.z, dw = (double)e.w - (double)h.w;
+			sq += dx * dx; sq += dy * dy; sq += dz * dz; sq += dw * dw;
+			if (t == 0) {
+				const float4 x = x4[q], n = n4[q];
+				nll += decoder_nll(x.x, n.x, h.x, dec); nll += decoder_nll(x.y, n.y, h.y, dec);
+				nll += decoder_nll(x.z, n.z, h.z, dec); nll += decoder_nll(x.w, n.w, h.w, dec);
+			}
+		}
+	} else {
+		for (size_t i = threadIdx.x; i < F; i += kThreads) {
+			const double d = (double)eps[base + i] - (double)eps_hat[base + i];
+			sq += d * d;
+			if (t == 0) nll += decoder_nll(x0[base + i], xt[base + i], eps_hat[base + i], dec);
+		}
+	}
+	sq = block_sum(sq, part);
+	if (t == 0) nll = block_sum(nll, part);
+	if (threadIdx.x == 0) {
+		terms[b] = t == 0 ? nll : (double)F * vlb[t] + vlb[steps + t] * sq;
+		if (sqerr) sqerr[b] = sq;
+	}
+}
+
+// kl_b = (abar sum x0^2 - F abar - F ln(1 - abar)) / 2 with abar = alpha_bar of the last step: vlb_terms_kernel's reduction on one input
+__global__ void __launch_bounds__(kThreads) prior_kl_kernel(const float* __restrict__ x0, size_t F, double abar, double log_1m_abar, double* __restrict__ kl, int vec) {
+	__shared__ double part[kThreads];
+	const size_t base = (size_t)blockIdx.x * F;
+	double s = 0.0;
+	if (vec) {
+		const float4* x4 = reinterpret_cast<const float4*>(x0 + base);
+		for (size_t q = threadIdx.x; q < F / 4; q += kThreads) {
+			const float4 x = x4[q];
+			s += (double)x.x * x.x; s += (double)x.y * x.y; s += (double)x.z * x.z; s += (double)x.w * x.w;
+		}
+	} else {
+		for (size_t i = threadIdx.x; i < F; i += kThreads) { const double x = x0[base + i]; s += x * x; }
+	}
+	s = block_sum(s, part);
+	if (threadIdx.x == 0) kl[blockIdx.x] = 0.5 * (abar * s - (double)F * abar - (double)F * log_1m_abar);
+}
+
+// c_t = (ln(beta_t / beta~_t) + beta~_t / beta_t - 1) / 2 and w_t = beta_t / (2 alpha_t (1 - abar_t)), t >= 1, in this order of operations (the tests
+// restate it operation for operation)
+void vlb_weights(const std::vector<double>& beta, const std::vector<double>& alpha_bar, int t, double* c, double* w) {
+#pragma clang fp contract(off)
+	const double b = beta[t], ab = alpha_bar[t], abp = alpha_bar[t - 1];
+	const double bt = b * (1.0 - abp) / (1.0 - ab);
+	*c = 0.5 * (std::log(b / bt) + bt / b - 1.0);
+	*w = b / (2.0 * (1.0 - b) * (1.0 - ab));
+}
+
+// K midpoints of equal strata of 1 .. T-1 behind t = 0
+std::vector<int> eval_timesteps(int T, int K) {
+	std::vector<int> ts(K + 1);
+	ts[0] = 0;
+	for (int i = 0; i < K; i++) ts[1 + i] = 1 + (int)((long long)(T - 1) * (2 * i + 1) / (2 * K));
+	return ts;
+}
+
 bla_status check_images(const bla_diffusion* d, int batch, size_t image_floats, int time_dim) {
 	BLA_REQUIRE(d, BLA_ERR_INVALID, "null diffusion object");
 	BLA_REQUIRE(batch >= 1 && image_floats >= 1 && time_dim >= 1, BLA_ERR_INVALID, "batch %d, image_floats %zu, time_dim %d", batch, image_floats, time_dim);
@@ -371,7 +534,11 @@ bla_status bla_diffusion_create(bla_diffusion** out, int steps, float beta_start
 	}
 	hipError_t e = hipMalloc((void**)&d->table, tab.size() * sizeof(float));
 	if (e == hipSuccess) e = hipMemcpy(d->table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-	if (e != hipSuccess) { (void)hipFree(d->table); delete d; return hip_fail(e, "bla_diffusion_create"); }
+	std::vector<double> vlb((size_t)2 * steps, 0.0);
+	for (int t = 1; t < steps; t++) vlb_weights(d->beta, d->alpha_bar, t, &vlb[t], &vlb[steps + t]);
+	if (e == hipSuccess) e = hipMalloc((void**)&d->vlb, vlb.size() * sizeof(double));
+	if (e == hipSuccess) e = hipMemcpy(d->vlb, vlb.data(), vlb.size() * sizeof(double), hipMemcpyHostToDevice);
+	if (e != hipSuccess) { (void)hipFree(d->table); (void)hipFree(d->vlb); delete d; return hip_fail(e, "bla_diffusion_create"); }
 	*out = d;
 	return BLA_OK;
 }
@@ -380,6 +547,7 @@ bla_status bla_diffusion_destroy(bla_diffusion* d) {
 	if (!d) return BLA_OK;
 	(void)hipDeviceSynchronize();
 	(void)hipFree(d->table); (void)hipFree(d->temb); (void)hipFree(d->xg); (void)hipFree(d->rows);
+	(void)hipFree(d->vlb); (void)hipFree(d->ev); (void)hipFree(d->ev_temb);
 	delete d;
 	return BLA_OK;
 }
@@ -658,6 +826,110 @@ bla_status bla_unet_sample_guided_ddim_f32(bla_unet* m, const bla_diffusion* d, 
 			return st;
 	}
 	BLA_HIP(hipMemcpyAsync(d_x, xg, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	return BLA_OK;
+}
+
+// ---- held-out evaluation ------------------------------------------------------------------------------------------------------------------------
+
+bla_status bla_diffusion_noise_at_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, int time_dim, const int* d_t, int t_const,
+                                      unsigned long long seed, unsigned long long offset, float* d_eps, float* d_xt, float* d_temb) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(d_x0 && d_eps && d_xt && d_temb, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(batch <= kMaxNoiseBatch, BLA_ERR_INVALID, "batch %d > %d", batch, kMaxNoiseBatch);
+	BLA_REQUIRE(d_t || (t_const >= 0 && t_const < d->steps), BLA_ERR_INVALID, "timestep %d outside [0, %d)", t_const, d->steps);
+	const int vec = image_floats % 4 == 0 && ((uintptr_t)d_x0 | (uintptr_t)d_eps | (uintptr_t)d_xt) % 16 == 0;
+	const size_t n = (size_t)batch * image_floats;
+	hipLaunchKernelGGL(noise_at_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x0, batch, image_floats, time_dim, d_t, t_const, seed,
+	                   offset, d->steps, d->table, d_eps, d_xt, d_temb, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_vlb_terms_f32(const bla_diffusion* d, void* stream, const float* d_x0, const float* d_xt, const float* d_eps, const float* d_eps_hat,
+                                       const int* d_t, int t_const, int batch, size_t image_floats, double* d_terms, double* d_sqerr) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, 1))) return st;
+	BLA_REQUIRE(d_x0 && d_xt && d_eps && d_eps_hat && d_terms, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(d_t || (t_const >= 0 && t_const < d->steps), BLA_ERR_INVALID, "timestep %d outside [0, %d)", t_const, d->steps);
+	const int vec = image_floats % 4 == 0 && ((uintptr_t)d_x0 | (uintptr_t)d_xt | (uintptr_t)d_eps | (uintptr_t)d_eps_hat) % 16 == 0;
+	const double b0 = d->beta[0], ab0 = d->alpha_bar[0];
+	const DecoderArgs dec = {b0 / std::sqrt(1.0 - ab0), std::sqrt(1.0 - b0), std::sqrt(b0)};
+	hipLaunchKernelGGL(vlb_terms_kernel, dim3(batch), dim3(kThreads), 0, pick_stream(stream), d_x0, d_xt, d_eps, d_eps_hat, d_t, t_const, image_floats, d->steps, d->vlb,
+	                   dec, d_terms, d_sqerr, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_prior_kl_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, double* d_kl) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, 1))) return st;
+	BLA_REQUIRE(d_x0 && d_kl, BLA_ERR_INVALID, "null argument");
+	const int vec = image_floats % 4 == 0 && (uintptr_t)d_x0 % 16 == 0;
+	const double ab = d->alpha_bar[d->steps - 1];
+	hipLaunchKernelGGL(prior_kl_kernel, dim3(batch), dim3(kThreads), 0, pick_stream(stream), d_x0, image_floats, ab, std::log(1.0 - ab), d_kl, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_vlb_weights(const bla_diffusion* d, int t, double* c_t, double* w_t) {
+	BLA_REQUIRE(d && t >= 1 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [1, %d)", t, d ? d->steps : 0);
+	double c, w;
+	vlb_weights(d->beta, d->alpha_bar, t, &c, &w);
+	if (c_t) *c_t = c;
+	if (w_t) *w_t = w;
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_eval_timesteps(const bla_diffusion* d, int K, int* out) {
+	BLA_REQUIRE(d && out, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(K >= 0 && K <= d->steps - 1, BLA_ERR_INVALID, "%d KL terms outside [0, %d]", K, d->steps - 1);
+	const std::vector<int> ts = eval_timesteps(d->steps, K);
+	for (int i = 0; i <= K; i++) out[i] = ts[i];
+	return BLA_OK;
+}
+
+bla_status bla_unet_evaluate_f32(bla_unet* m, const bla_diffusion* d, void* stream, const float* d_x0, const int* timesteps, int count, unsigned long long seed,
+                                 unsigned long long offset_base, const float* d_table, int classes, const int* d_rows, double* d_terms, double* d_sqerr) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d && d_x0 && timesteps && d_terms, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(count >= 0, BLA_ERR_INVALID, "count %d", count);
+	BLA_REQUIRE(!d_table || (d_rows && classes >= 1), BLA_ERR_INVALID, "a class table needs the rows [batch] and classes >= 1");
+	for (int i = 0; i < count; i++) BLA_REQUIRE(timesteps[i] >= 0 && timesteps[i] < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", timesteps[i], d->steps);
+	const bla_unet_config& c = *unet_config(m);
+	const int B = bla_unet_batch(m);
+	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim, nx = (size_t)B * F;
+	hipStream_t s = pick_stream(stream);
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);   // workspaces, not part of the schedule
+	if (dm->ev_floats < 2 * nx || dm->ev_temb_floats < ne) {
+		BLA_HIP(hipStreamSynchronize(s));
+		if (dm->ev_floats < 2 * nx) {
+			(void)hipFree(dm->ev); dm->ev = nullptr; dm->ev_floats = 0;
+			BLA_HIP(hipMalloc((void**)&dm->ev, 2 * nx * sizeof(float)));
+			dm->ev_floats = 2 * nx;
+		}
+		if (dm->ev_temb_floats < ne) {
+			(void)hipFree(dm->ev_temb); dm->ev_temb = nullptr; dm->ev_temb_floats = 0;
+			BLA_HIP(hipMalloc((void**)&dm->ev_temb, ne * sizeof(float)));
+			dm->ev_temb_floats = ne;
+		}
+	}
+	if (d_table && (st = grow_workspaces(dm, s, 0, 0, B))) return st;   // the rows bla_class_embedding_f32 writes
+	float *eps = dm->ev, *xt = dm->ev + nx;
+	for (int i = 0; i < count; i++) {
+		const int t = timesteps[i];
+		if ((st = bla_diffusion_noise_at_f32(d, stream, d_x0, B, F, c.time_dim, nullptr, t, seed, offset_base + ((unsigned long long)(t + 1) << 32), eps, xt, dm->ev_temb)))
+			return st;
+		if (d_table && (st = bla_class_embedding_f32(stream, d_table, classes, d_rows, B, c.time_dim, 0.f, seed, 0, dm->rows, dm->ev_temb))) return st;
+		if ((st = bla_unet_forward_f32(m, stream, xt, dm->ev_temb, nullptr))) return st;
+		if ((st = bla_diffusion_vlb_terms_f32(d, stream, d_x0, xt, eps, bla_unet_output(m), nullptr, t, B, F, d_terms + (size_t)i * B,
+		                                      d_sqerr ? d_sqerr + (size_t)i * B : nullptr)))
+			return st;
+	}
 	return BLA_OK;
 }
 

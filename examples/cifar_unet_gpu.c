@@ -87,6 +87,22 @@
  *                                                      integer >= 1): pass p uses BLA_ADAM_LR * min(1, (p + 1) / n).  Bad values stop the
  *                                                      program before the device is opened.  With none of the four `fit` is unchanged.
  *
+ *   (not in the reference)                             Held-out evaluation: the variational bound of Ho et al. 2020 (eq. 5) in bits/dim (bla.h).
+ *                                                      `eval [<images>]`: BLA_CIFAR_EVAL_FILE (default $BLA_CIFAR_DIR/test_batch.bin) read as
+ *                                                      fit reads its records, the first <images> (default all) in batches of BLA_UNET_BATCH
+ *                                                      (default 64), the last partial batch dropped; the saved set, or the set below ema/ with
+ *                                                      BLA_UNET_EVAL_EMA=1; BLA_UNET_CLASSES=1: every image with its own label's row (no label
+ *                                                      dropout).  Timesteps: bla_diffusion_eval_timesteps of BLA_UNET_EVAL_STEPS (default
+ *                                                      min(T - 1, 50)).  The batch that starts at record r is bla_unet_evaluate_f32 with
+ *                                                      offset_base r x 3072 / 4 plus bla_diffusion_prior_kl_f32; the per-image doubles are copied
+ *                                                      out once per batch and summed in record order.  Prints the image count, `Bits/dim:
+ *                                                      <total> (prior, decoder, KL)` and the eps MSE per timestep.  A missing file, a bad option
+ *                                                      or a bound that is not finite stops the program with status 1.
+ *                                                      `fit` with BLA_UNET_EVAL_EVERY=<n> (an integer >= 1): the same evaluation of the live
+ *                                                      weights every n passes and after the last, on the first BLA_UNET_EVAL_IMAGES records of
+ *                                                      the evaluation file (default one batch; uploaded once), seed BLA_SEED, a fixed K; prints
+ *                                                      `Held-out bits/dim: <total>` behind the pass's loss line.  Without it `fit` is unchanged.
+ *
  * BLA_UNET_DUMP=<dir> makes train write what it uploaded (params, x, time embedding, noise, dropout decisions) and what came back (prediction,
  * gradient bucket) as raw little-endian files; tests/test_c_unet.py compares those with the oracle.
  *
@@ -527,6 +543,22 @@ static void draws(int images, const char* dir) {
 static unsigned long long env_seed(void) { return strtoull(env_or("BLA_SEED", "42"), NULL, 10); }
 static int env_steps(void) { const int T = atoi(env_or("BLA_DIFFUSION_STEPS", "1000")); if (T < 1) { fprintf(stderr, "BLA_DIFFUSION_STEPS must be >= 1\n"); exit(1); } return T; }
 
+/* the records of one CIFAR-10 binary file appended to *all (and their label bytes to *lab, if not NULL), mapped as load_example maps them (:221-233:
+ * planes with their rows flipped, (p - 127.5) / 127.5); *n counts the records held */
+static void read_records(FILE* f, float** all, size_t* n, uint8_t** lab) {
+	uint8_t rec[3073];
+	while (fread(rec, 1, sizeof rec, f) == sizeof rec) {
+		if (*n % 1024 == 0) { *all = realloc(*all, (*n + 1024) * IMAGE_FLOATS * sizeof(float)); if (lab) *lab = realloc(*lab, *n + 1024); }
+		if (lab) (*lab)[*n] = rec[0];
+		float* x = *all + *n * IMAGE_FLOATS;
+		for (int c = 0; c < IMAGE_CHANNELS; c++)
+			for (int y = 0; y < IMAGE_SIDE; y++)
+				for (int i = 0; i < IMAGE_SIDE; i++)
+					x[(c * IMAGE_SIDE + y) * IMAGE_SIDE + i] = (float)(((double)rec[1 + (c * IMAGE_SIDE + IMAGE_SIDE - 1 - y) * IMAGE_SIDE + i] - 127.5) / 127.5);
+		(*n)++;
+	}
+}
+
 /* every data_batch_{1..5}.bin below BLA_CIFAR_DIR, records in order, mapped as load_example maps them (:221-233: planes with their rows flipped,
  * (p - 127.5) / 127.5); *count = records read; *labels (if not NULL): the records' label bytes */
 static float* read_training_set(size_t* count, uint8_t** labels) {
@@ -543,17 +575,7 @@ static float* read_training_set(size_t* count, uint8_t** labels) {
 			continue;
 		}
 		files++;
-		uint8_t rec[3073];
-		while (fread(rec, 1, sizeof rec, f) == sizeof rec) {
-			if (n % 1024 == 0) { all = realloc(all, (n + 1024) * IMAGE_FLOATS * sizeof(float)); if (labels) lab = realloc(lab, n + 1024); }
-			if (labels) lab[n] = rec[0];
-			float* x = all + n * IMAGE_FLOATS;
-			for (int c = 0; c < IMAGE_CHANNELS; c++)
-				for (int y = 0; y < IMAGE_SIDE; y++)
-					for (int i = 0; i < IMAGE_SIDE; i++)
-						x[(c * IMAGE_SIDE + y) * IMAGE_SIDE + i] = (float)(((double)rec[1 + (c * IMAGE_SIDE + IMAGE_SIDE - 1 - y) * IMAGE_SIDE + i] - 127.5) / 127.5);
-			n++;
-		}
+		read_records(f, &all, &n, labels ? &lab : NULL);
 		fclose(f);
 	}
 	if (!files) { fprintf(stderr, "cannot open %s/data_batch_1.bin: %s (nor any data_batch_{2..5}.bin)\n", dir, strerror(ENOENT)); exit(1); }
@@ -616,6 +638,16 @@ static long env_warmup(void) {
 	if (*end || errno || n < 1) { fprintf(stderr, "fit: BLA_ADAM_WARMUP=%s; the warm-up is a whole number of passes >= 1\n", v); exit(1); }
 	return n;
 }
+/* BLA_UNET_EVAL_EVERY=<n> for fit, an integer >= 1; 0 = not set */
+static long env_eval_every(void) {
+	const char* v = getenv("BLA_UNET_EVAL_EVERY");
+	if (!v || !*v) return 0;
+	char* end = NULL;
+	errno = 0;
+	const long n = strtol(v, &end, 10);
+	if (*end || errno || n < 1) { fprintf(stderr, "fit: BLA_UNET_EVAL_EVERY=%s; the evaluation runs every whole number of passes >= 1\n", v); exit(1); }
+	return n;
+}
 /* exchanges the host tensors with another set of the same shapes */
 static void swap_sets(float** other) {
 	for (int t = 0; t < g_tensor_count; t++) { float* h = g_tensors[t].host; g_tensors[t].host = other[t]; other[t] = h; }
@@ -646,12 +678,157 @@ static float** load_ema_set(float* ema_table) {
 	return set;
 }
 
+/* ---- held-out evaluation: the variational bound in bits/dim (bla.h, "held-out evaluation"), for `eval` and for fit's BLA_UNET_EVAL_EVERY ------------- */
+typedef struct Evaluator {
+	size_t images;                       /* whole batches of the evaluation file's first records */
+	int batch, K, T, *ts;                /* ts [K + 1]: bla_diffusion_eval_timesteps */
+	float* d_data; int* d_labels;        /* the records, uploaded once; d_labels NULL: unconditional */
+	double *d_out, *out;                 /* per batch: terms [K + 1][B], sqerr [K + 1][B], prior [B] */
+	double prior, decoder, kl, *mse;     /* the last run: bits/dim of the three parts, eps MSE per timestep [K + 1] */
+} Evaluator;
+/* BLA_UNET_EVAL_STEPS: the number of KL terms, 0 .. T-1, default min(T - 1, 50) */
+static int env_eval_steps(const char* verb, int T) {
+	const char* v = getenv("BLA_UNET_EVAL_STEPS");
+	if (!v || !*v) return T - 1 < 50 ? T - 1 : 50;
+	char* end = NULL;
+	const long k = strtol(v, &end, 10);
+	if (*end || k < 0 || k > T - 1) { fprintf(stderr, "%s: BLA_UNET_EVAL_STEPS=%s; the bound has 0..%d KL terms (BLA_DIFFUSION_STEPS - 1)\n", verb, v, T - 1); exit(1); }
+	return (int)k;
+}
+/* the evaluation file, BLA_CIFAR_EVAL_FILE (default <BLA_CIFAR_DIR>/test_batch.bin), read as read_training_set reads its files */
+static float* read_eval_file(const char* verb, size_t* count, uint8_t** labels) {
+	char path[512];
+	snprintf(path, sizeof path, "%s/test_batch.bin", env_or("BLA_CIFAR_DIR", "data/cifar"));
+	const char* file = env_or("BLA_CIFAR_EVAL_FILE", path);
+	FILE* f = fopen(file, "rb");
+	if (!f) { fprintf(stderr, "%s: cannot open %s: %s\n", verb, file, strerror(errno)); exit(1); }
+	float* all = NULL;
+	*count = 0;
+	if (labels) *labels = NULL;
+	read_records(f, &all, count, labels);
+	fclose(f);
+	for (size_t r = 0; labels && r < *count; r++)
+		if ((*labels)[r] >= CLASSES) { fprintf(stderr, "%s: record %zu of %s has label %d; CIFAR-10 labels are 0..%d\n", verb, r, file, (*labels)[r], CLASSES - 1); exit(1); }
+	return all;
+}
+/* after the device is open: uploads the first `images` records (a whole number of batches) and their labels (NULL: unconditional) */
+static Evaluator eval_open(const bla_diffusion* diff, const float* data, const uint8_t* labels, size_t images, int batch, int K) {
+	Evaluator ev; memset(&ev, 0, sizeof ev);
+	ev.images = images; ev.batch = batch; ev.K = K; ev.T = bla_diffusion_steps(diff);
+	ev.ts = malloc((K + 1) * sizeof(int));
+	CHECK(bla_diffusion_eval_timesteps(diff, K, ev.ts));
+	CHECK(bla_malloc((void**)&ev.d_data, images * IMAGE_FLOATS * sizeof(float)));
+	CHECK(bla_memcpy_h2d(ev.d_data, data, images * IMAGE_FLOATS * sizeof(float), NULL));
+	if (labels) {
+		int* lab = malloc(images * sizeof(int));
+		for (size_t r = 0; r < images; r++) lab[r] = labels[r];
+		CHECK(bla_malloc((void**)&ev.d_labels, images * sizeof(int)));
+		CHECK(bla_memcpy_h2d(ev.d_labels, lab, images * sizeof(int), NULL));
+		CHECK(bla_stream_sync(NULL));
+		free(lab);
+	}
+	const size_t doubles = (size_t)(2 * (K + 1) + 1) * batch;
+	CHECK(bla_malloc((void**)&ev.d_out, doubles * sizeof(double)));
+	ev.out = malloc(doubles * sizeof(double));
+	ev.mse = malloc((K + 1) * sizeof(double));
+	CHECK(bla_stream_sync(NULL));
+	return ev;
+}
+/* One evaluation of the model's current weights: per batch bla_unet_evaluate_f32 (the batch that starts at record r draws at offset_base r F / 4, so every
+ * record has its own noise whatever the batch size) and bla_diffusion_prior_kl_f32, the per-image doubles copied out once and summed here in record order.
+ * Returns the bound in bits/dim: prior + decoder + (T - 1) / K x the K sampled KL terms, averaged over the images. */
+static double eval_run(Evaluator* ev, bla_unet* net, const bla_diffusion* diff, unsigned long long seed, const float* d_table) {
+	const int B = ev->batch, n = ev->K + 1;
+	double prior = 0, decoder = 0, kl = 0;
+	for (int i = 0; i < n; i++) ev->mse[i] = 0;
+	double *terms = ev->out, *sqerr = ev->out + (size_t)n * B, *pri = ev->out + (size_t)2 * n * B;
+	for (size_t r = 0; r < ev->images; r += B) {
+		const float* x0 = ev->d_data + r * IMAGE_FLOATS;
+		CHECK(bla_unet_evaluate_f32(net, diff, NULL, x0, ev->ts, n, seed, (unsigned long long)r * (IMAGE_FLOATS / 4), d_table, CLASSES,
+		                            d_table ? ev->d_labels + r : NULL, ev->d_out, ev->d_out + (size_t)n * B));
+		CHECK(bla_diffusion_prior_kl_f32(diff, NULL, x0, B, IMAGE_FLOATS, ev->d_out + (size_t)2 * n * B));
+		CHECK(bla_memcpy_d2h(ev->out, ev->d_out, (size_t)(2 * n + 1) * B * sizeof(double), NULL));
+		CHECK(bla_stream_sync(NULL));
+		for (int b = 0; b < B; b++) {
+			prior += pri[b]; decoder += terms[b];
+			for (int i = 1; i < n; i++) kl += terms[(size_t)i * B + b];
+			for (int i = 0; i < n; i++) ev->mse[i] += sqerr[(size_t)i * B + b];
+		}
+	}
+	const double dims = (double)ev->images * IMAGE_FLOATS, bits = dims * log(2.0);
+	ev->prior = prior / bits; ev->decoder = decoder / bits;
+	ev->kl = ev->K ? kl * ((double)(ev->T - 1) / ev->K) / bits : 0.0;
+	for (int i = 0; i < n; i++) ev->mse[i] /= dims;
+	return ev->prior + ev->decoder + ev->kl;
+}
+static void eval_close(Evaluator* ev) {
+	CHECK(bla_free(ev->d_data)); CHECK(bla_free(ev->d_labels)); CHECK(bla_free(ev->d_out));
+	free(ev->ts); free(ev->out); free(ev->mse);
+}
+
+/* `eval [<images>]`: the saved set (BLA_UNET_EVAL_EMA=1: the set below ema/) on the evaluation file's first <images> records (default all), the last partial
+ * batch dropped; BLA_UNET_BATCH (default 64), BLA_UNET_EVAL_STEPS, BLA_UNET_CLASSES=1: every image with its own label's row, no label dropout */
+static void eval(const char* images_arg) {
+	const int classes = env_flag("BLA_UNET_CLASSES"), T = env_steps(), K = env_eval_steps("eval", T);
+	const int batch = atoi(env_or("BLA_UNET_BATCH", "64"));
+	if (batch < 1) { fprintf(stderr, "eval: BLA_UNET_BATCH must be >= 1\n"); exit(1); }
+	long want = -1;
+	if (images_arg) {
+		char* end = NULL;
+		want = strtol(images_arg, &end, 10);
+		if (*end || want < 1) { fprintf(stderr, "eval: %s images; the number of images is a whole number >= 1\n", images_arg); exit(1); }
+	}
+	size_t records = 0;
+	uint8_t* labels = NULL;
+	float* data = read_eval_file("eval", &records, classes ? &labels : NULL);
+	if (want > 0 && (size_t)want < records) records = (size_t)want;
+	const size_t images = records / batch * batch;
+	if (!images) { fprintf(stderr, "eval: %zu records, fewer than one batch of %d\n", records, batch); exit(1); }
+	if (env_flag("BLA_UNET_EVAL_EMA")) g_set = "ema";
+	float* table = NULL;
+	if (classes) {
+		table = malloc((size_t)(CLASSES + 1) * TIME_EMBED_DIM * sizeof(float));
+		if (!load_class_table(table)) {
+			char path[512];
+			data_path(path, sizeof path, "class_embedding.csv");
+			fprintf(stderr, "eval: cannot open %s (run `fit` with BLA_UNET_CLASSES=1 first)\n", path);
+			exit(1);
+		}
+	}
+	load_parameters();
+	const unsigned long long seed = env_seed();
+	Inputs in = inputs_alloc(1);
+	Device dv = device_open(batch, in.drop_per_image);
+	device_set_params(&dv);
+	bla_diffusion* diff;
+	CHECK(bla_diffusion_create(&diff, T, 1e-4f, 0.02f));
+	float* d_table = NULL;
+	if (classes) {
+		CHECK(bla_malloc((void**)&d_table, (size_t)(CLASSES + 1) * TIME_EMBED_DIM * sizeof(float)));
+		CHECK(bla_memcpy_h2d(d_table, table, (size_t)(CLASSES + 1) * TIME_EMBED_DIM * sizeof(float), NULL));
+	}
+	Evaluator ev = eval_open(diff, data, labels, images, batch, K);
+	free(data); free(labels);
+	const double total = eval_run(&ev, dv.net, diff, seed, d_table);
+	if (!isfinite(total)) { fprintf(stderr, "eval: the bound is not finite (%f bits/dim)\n", total); exit(1); }
+	printf("eval: %zu images, %d steps, %d of %d KL terms\n", images, T, K, T - 1);
+	printf("Bits/dim: %.6f (prior %.6f, decoder %.6f, KL %.6f)\n", total, ev.prior, ev.decoder, ev.kl);
+	printf("Eps MSE by timestep:");
+	for (int i = 0; i <= K; i++) printf(" t=%d %.6f", ev.ts[i], ev.mse[i]);
+	printf("\n");
+	eval_close(&ev);
+	if (classes) { CHECK(bla_free(d_table)); free(table); }
+	CHECK(bla_diffusion_destroy(diff));
+	inputs_free(&in); device_close(&dv);
+}
+
 static void fit(int epochs, int batch) {
 	if (batch < 1 || epochs < 1) { fprintf(stderr, "fit: epochs and batch must be >= 1\n"); exit(1); }
 	const double ema_decay = env_ema_decay();
 	const int shuffle = env_fit_flag("BLA_UNET_SHUFFLE"), flip = env_fit_flag("BLA_UNET_FLIP"), gather = shuffle || flip;
 	const double clip_norm = env_clip_norm();
 	const long warmup = env_warmup();
+	const long eval_every = env_eval_every();
 	const int classes = env_flag("BLA_UNET_CLASSES");
 	size_t records = 0;
 	uint8_t* labels = NULL;
@@ -667,6 +844,19 @@ static void fit(int epochs, int batch) {
 		if (!(p_uncond >= 0 && p_uncond <= 1)) { fprintf(stderr, "fit: BLA_UNET_UNCOND must lie in [0, 1]\n"); exit(1); }
 		table = calloc((size_t)(CLASSES + 1) * TIME_EMBED_DIM, sizeof(float));
 		if (env_flag("BLA_UNET_RESUME")) (void)load_class_table(table);
+	}
+	/* BLA_UNET_EVAL_EVERY: the held-out records, read and checked before the device is opened */
+	float* eval_data = NULL; uint8_t* eval_labels = NULL; size_t eval_images = 0; int eval_K = 0;
+	if (eval_every) {
+		eval_K = env_eval_steps("fit", env_steps());
+		const char* v = getenv("BLA_UNET_EVAL_IMAGES");
+		char* end = NULL;
+		const long want = v && *v ? strtol(v, &end, 10) : batch;
+		if ((end && *end) || want < batch) { fprintf(stderr, "fit: BLA_UNET_EVAL_IMAGES=%s; the evaluation takes a whole number of images, at least one batch of %d\n", v ? v : "", batch); exit(1); }
+		size_t held = 0;
+		eval_data = read_eval_file("fit", &held, classes ? &eval_labels : NULL);
+		eval_images = (size_t)want / batch * batch;
+		if (held < eval_images) { fprintf(stderr, "fit: the evaluation file holds %zu records, fewer than the %zu asked for\n", held, eval_images); exit(1); }
 	}
 	if (env_flag("BLA_UNET_RESUME")) load_parameters(); else draw_parameters("unit");
 	const size_t table_floats = (size_t)(CLASSES + 1) * TIME_EMBED_DIM;
@@ -740,6 +930,8 @@ static void fit(int epochs, int batch) {
 		CHECK(bla_stream_sync(NULL));
 		free(lab);
 	}
+	Evaluator ev; memset(&ev, 0, sizeof ev);
+	if (eval_every) { ev = eval_open(diff, eval_data, eval_labels, eval_images, batch, eval_K); free(eval_data); free(eval_labels); }
 	CHECK(bla_stream_sync(NULL));
 	free(data); free(labels);
 	printf("fit: %zu records, %zu passes of %d per epoch, %d epochs\n", records, per_epoch, batch, epochs);
@@ -799,7 +991,12 @@ static void fit(int epochs, int batch) {
 			fflush(stdout);
 			logged = pass + 1;
 		}
+		if (eval_every && ((pass + 1) % (size_t)eval_every == 0 || pass + 1 == passes)) {   /* the live weights on the held-out records: a fixed seed and K */
+			printf("Held-out bits/dim: %.6f\n", eval_run(&ev, dv.net, diff, seed, d_table));
+			fflush(stdout);
+		}
 	}
+	if (eval_every) eval_close(&ev);
 	device_get_params(&dv);
 	save_parameters();
 	if (ema_decay > 0) {   /* the average as a second complete set below ema/: tensors the device model does not use keep the values just written */
@@ -946,6 +1143,8 @@ int main(int argc, char** argv) {
 			exit(1);
 		}
 		fit(atoi(argv[2]), argc < 4 ? 64 : atoi(argv[3]));
+	} else if (strcmp(argv[1], "eval") == 0) {
+		eval(argc < 3 ? NULL : argv[2]);
 	} else if (strcmp(argv[1], "sample") == 0) {
 		sample(argc < 3 ? 1 : atoi(argv[2]), argc < 4 ? "data/cifar_unet_samples" : argv[3]);
 	} else {

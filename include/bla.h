@@ -567,7 +567,11 @@ BLA_API bla_status bla_mse_accumulate_f32(void* stream, const float* d_a, const 
  * blocks, at most 1024), the horizontal flips of bla_diffusion_noise_gather_f32 at (pass << 32) + (1 << 31) + (1 << 30) (tag 2, batch / 4 blocks, at most
  * 1024).  The three tag-2 ranges are disjoint as long as bla_unet_dropout_count() < 2^33, and all stay below the next pass's (pass + 1) << 32.
  * A shuffled epoch e draws its permutation with bla_rand_permutation_u32 at (e << 32) + (1 << 31) (tag 0, at most 2^18 blocks), behind the timestep
- * draws of pass e (tag 0 at e << 32, at most 1024 blocks). */
+ * draws of pass e (tag 0 at e << 32, at most 1024 blocks).
+ * Held-out evaluation (bla_unet_evaluate_f32 below) noises its batch at timestep t with the normal stream (tag 1) at offset_base + ((t + 1) << 32),
+ * batch * image_floats / 4 blocks.  examples/cifar_unet_gpu.c `eval` gives the batch that starts at record r offset_base = r * image_floats / 4, so
+ * record r owns the blocks [r F / 4, (r + 1) F / 4) behind (t + 1) << 32 whatever the batch size (below the next timestep's range up to 2^32 / (F / 4)
+ * records).  With offset_base 0 these are the blocks of the samplers' z at the same seed: an evaluation and a sampling run are separate uses. */
 
 /* Gradient of the time-embedding input: d_dtemb [B][time_dim] = dL/dtemb for the loss of the last bla_unet_backward_f32 (del_Y = 2 (pred - noise)).
  * The embedding feeds nothing but the 18 ResNet blocks' projections temb . W_k + bias_k, so dtemb[b] = sum_k W_k . dtb_k[b] with dtb_k[b] the per-image
@@ -609,6 +613,55 @@ BLA_API bla_status bla_diffusion_guided_ddim_step_f32(const bla_diffusion* d, vo
  * sample_steps, one batch-2n forward pass and one bla_diffusion_guided_ddim_step_f32 per step. */
 BLA_API bla_status bla_unet_sample_guided_ddim_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes,
                                                    const int* labels, float guidance, int sample_steps, float eta, int clip, unsigned long long seed);
+
+/* ---- held-out evaluation: the variational bound of Ho et al. 2020 (eq. 5) in nats per image ------------------------------------------------
+ * Not in the reference.  With T = bla_diffusion_steps, beta_t / abar_t the doubles of bla_diffusion_schedule, alpha_t = 1 - beta_t, abar_{-1} = 1,
+ * beta~_t = beta_t (1 - abar_{t-1}) / (1 - abar_t), F = image_floats and this project's fixed variance sigma_t^2 = beta_t:
+ *   -ln p(x0) <= KL(q(x_{T-1} | x0) || N(0, I)) + sum_{t=1}^{T-1} KL(q(x_{t-1} | x_t, x0) || N(mu_theta, beta_t I)) + (-ln p(x0 | x_1 -> t = 0)),
+ * every expectation estimated by ONE draw of x_t per image and timestep.  All arithmetic on image data below is in double on the fp32 inputs as they are,
+ * with coefficients formed in double from the schedule (on the host and passed by value, or a double table made at create time): nothing is uploaded per
+ * call, so the sequences can be captured into a graph.  examples/cifar_unet_gpu.c `eval` drives these and reports bits/dim = nats / (F ln 2).
+ *
+ * Noising at given timesteps: d_t [batch] on the device (NULL: every image at t_const), d_eps = bla_rand_normal_f32(batch * image_floats, 0, 1, seed,
+ * offset), d_xt = sqrt(abar_t) x0 + sqrt(1 - abar_t) eps from the fp32 tables with bla_diffusion_noise_f32's rounding on either path (16-byte body when
+ * image_floats % 4 == 0 and d_x0, d_eps, d_xt are 16-byte aligned), d_temb [batch][time_dim] the embedding of each image's t.  With d_t what
+ * bla_diffusion_noise_f32(seed, pass) wrote and offset = pass << 32 all three are that call's, bit for bit.  t_const outside [0, T): BLA_ERR_INVALID; a
+ * device entry outside [0, T) cannot be checked without a round trip: that image's d_xt and d_temb rows are written as zeros.  batch <= 4096. */
+BLA_API bla_status bla_diffusion_noise_at_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, int time_dim,
+                                              const int* d_t /* [batch], may be NULL */, int t_const, unsigned long long seed, unsigned long long offset,
+                                              float* d_eps, float* d_xt, float* d_temb);
+/* One term of the bound per image, one launch: d_sqerr[b] (may be NULL) = sum_i (eps_i - eps_hat_i)^2 and
+ *   t_b >= 1: d_terms[b] = KL(q(x_{t-1} | x_t, x0) || N(mu_theta, beta_t I)) = F c_t + w_t sqerr_b, c_t = (ln(beta_t / beta~_t) + beta~_t / beta_t - 1) / 2,
+ *             w_t = beta_t / (2 alpha_t (1 - abar_t)): mu_theta is bla_diffusion_step_f32's mean and the posterior mean is the same expression with the true
+ *             eps, so the means differ by beta_t / sqrt(alpha_t (1 - abar_t)) (eps - eps_hat) and only the squared error enters;
+ *   t_b = 0:  d_terms[b] = -sum_i ln p_i, the discretised decoder of 8-bit data on [-1, 1] (Ho et al. 3.3): mu_i = (x_t,i - beta_0 / sqrt(1 - abar_0) eps_hat_i)
+ *             / sqrt(alpha_0), sigma = sqrt(beta_0), z+- = (x0_i +- 1/255 - mu_i) / sigma, p_i = Phi(z+) where x0_i < -0.999, 1 - Phi(z-) where x0_i > 0.999,
+ *             Phi(z+) - Phi(z-) otherwise, clamped below at 1e-12 (the floor of the published implementations).  Phi through erfc on the side where it is
+ *             small; the interior difference between the two upper tails when z- > 0, else between the two lower ones.
+ * d_t [batch] on the device (NULL: every image at t_const; t_const outside [0, T): BLA_ERR_INVALID); an image whose device-side t lies outside [0, T) gets
+ * d_terms[b] = NaN and d_sqerr[b] = 0.  One workgroup per image, 16-byte loads when image_floats % 4 == 0 and the four inputs are 16-byte aligned, every
+ * lane sums its elements in index order in double, the 256 partials go through LDS in a fixed tree: no atomics, bit-reproducible. */
+BLA_API bla_status bla_diffusion_vlb_terms_f32(const bla_diffusion* d, void* stream, const float* d_x0, const float* d_xt, const float* d_eps,
+                                               const float* d_eps_hat, const int* d_t /* [batch], may be NULL */, int t_const, int batch, size_t image_floats,
+                                               double* d_terms /* [batch] */, double* d_sqerr /* [batch], may be NULL */);
+/* d_kl[b] = KL(q(x_{T-1} | x0) || N(0, I)) = (abar_{T-1} sum_i x0_i^2 - F abar_{T-1} - F ln(1 - abar_{T-1})) / 2; the same reduction, one launch. */
+BLA_API bla_status bla_diffusion_prior_kl_f32(const bla_diffusion* d, void* stream, const float* d_x0, int batch, size_t image_floats, double* d_kl /* [batch] */);
+/* c_t and w_t above for 1 <= t < T (either pointer may be NULL); t = 0 or out of range: BLA_ERR_INVALID.  Host only. */
+BLA_API bla_status bla_diffusion_vlb_weights(const bla_diffusion* d, int t, double* c_t, double* w_t);
+/* The timesteps of an evaluation with K KL terms: out[0] = 0, out[1 + i] = 1 + floor((T - 1)(2 i + 1) / (2 K)) for i < K, the midpoints of K equal strata of
+ * 1 .. T-1 (strictly increasing; K = T - 1 gives every step, K = 0 only the decoder's).  out holds K + 1 ints; 0 <= K <= T - 1, else BLA_ERR_INVALID.  Host
+ * only.  The estimate of the bound is prior + terms(0) + (T - 1) / K sum_i terms(out[1 + i]).  It is exact (up to the one draw per term) only at K = T - 1:
+ * the midpoint rule is biased at small K, because c_t and w_t fall steeply at small t and a stratum's midpoint under-weights its first steps. */
+BLA_API bla_status bla_diffusion_eval_timesteps(const bla_diffusion* d, int K, int* out);
+/* The evaluation loop on the model's batch B, d_x0 [B][C][H][W]: for each of the `count` timesteps t (a host array, each in [0, T), else BLA_ERR_INVALID
+ * before anything runs) bla_diffusion_noise_at_f32 with t_const = t and offset offset_base + ((t + 1) << 32); where d_table is given, the class rows
+ * d_table[d_rows[b]] added to the embedding (bla_class_embedding_f32 with p_uncond 0 on the device rows d_rows [B]: a row outside [0, classes] adds
+ * nothing); bla_unet_forward_f32 without dropout; bla_diffusion_vlb_terms_f32 into d_terms [count][B] and d_sqerr [count][B] (may be NULL).  The values are
+ * those of that composition, bit for bit; no host round trip inside the loop.  The eps, x_t and embedding workspaces belong to the diffusion object and are
+ * allocated on first use: run once eagerly before capturing it into a graph. */
+BLA_API bla_status bla_unet_evaluate_f32(bla_unet* m, const bla_diffusion* d, void* stream, const float* d_x0, const int* timesteps, int count,
+                                         unsigned long long seed, unsigned long long offset_base, const float* d_table, int classes, const int* d_rows,
+                                         double* d_terms, double* d_sqerr);
 
 /* ---- device-resident MNIST-NN trainer: the hot loop of model/mnist_nn.c:218-315 with everything in HBM -------
  * sizes = {n0, n1, n2, n3} (784, 256, 128, 10 in the reference, model/mnist_nn.c:25-28); samples are columns.
