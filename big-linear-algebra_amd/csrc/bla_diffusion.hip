@@ -12,11 +12,14 @@
 //                         x <- sqrt(abar_p) x0^ + sqrt(1 - abar_p - sigma^2) eps_hat + sigma z  (Song, Meng, Ermon 2021; abar_p = 1 past the last step)
 //   eval   (seed, t):     eps = normal(seed, offset_base + ((t + 1) << 32))[0 .. B*F), x_t as in noise at the given t; then per image, in double, its term of
 //                         the variational bound: F c_t + w_t sum (eps - eps_hat)^2 at t >= 1, the discretised decoder's -sum ln p at t = 0 (Ho et al. eq. 5)
+//   DPM++  (no draws):    DPM-Solver++(2M) (Lu et al. 2022), deterministic: x0^ as in DDIM, D = w1 x0^ + w0 x0^_last (second order) or x0^,
+//                         x <- (sigma_p / sigma_t) x - alpha_p expm1(-h) D with h = lambda_p - lambda_t, lambda = ln(alpha / sigma); x0^ kept for the next step
 // The schedule is formed in double on the host at create time; the kernels read fp32 tables of the per-step coefficients (the evaluation: doubles).  The time embedding is
 // the one examples/cifar_unet_gpu.c computes for BLA_UNET_TIMESTEP, evaluated in double: at t ~ 1000 its arguments reach 1000 rad, where an fp32
 // product t * w_i alone is off by ~6e-5.
 #include "bla_internal.h"
 #include "bla_philox.h"
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -32,6 +35,8 @@ struct bla_diffusion {
 	size_t xg_floats = 0;
 	int* rows = nullptr;
 	int rows_count = 0;
+	float* hist = nullptr;         // the DPM-Solver++ samplers' previous x0 prediction, [B][C][H][W] (grows on first use)
+	size_t hist_floats = 0;
 	double* vlb = nullptr;         // device, 2 x steps: c_t, w_t of bla_diffusion_vlb_weights (0 at t = 0)
 	float* ev = nullptr;           // the evaluation loop's eps and x_t, [2][B][C][H][W], and its embedding [B][time_dim] (grow on first use)
 	size_t ev_floats = 0;
@@ -486,8 +491,8 @@ std::vector<int> ddim_timesteps(int T, int S) {
 
 // the samplers' workspaces of the diffusion object (scratch, not part of the schedule), grown to at least the sizes given; waits for the stream when
 // it has to grow one, so the first call is not capturable
-bla_status grow_workspaces(bla_diffusion* dm, hipStream_t s, size_t temb_floats, size_t xg_floats, int rows) {
-	if (dm->temb_floats >= temb_floats && dm->xg_floats >= xg_floats && dm->rows_count >= rows) return BLA_OK;
+bla_status grow_workspaces(bla_diffusion* dm, hipStream_t s, size_t temb_floats, size_t xg_floats, int rows, size_t hist_floats = 0) {
+	if (dm->temb_floats >= temb_floats && dm->xg_floats >= xg_floats && dm->rows_count >= rows && dm->hist_floats >= hist_floats) return BLA_OK;
 	BLA_HIP(hipStreamSynchronize(s));
 	if (dm->temb_floats < temb_floats) {
 		(void)hipFree(dm->temb); dm->temb = nullptr; dm->temb_floats = 0;
@@ -504,7 +509,133 @@ bla_status grow_workspaces(bla_diffusion* dm, hipStream_t s, size_t temb_floats,
 		BLA_HIP(hipMalloc((void**)&dm->rows, (size_t)rows * sizeof(int)));
 		dm->rows_count = rows;
 	}
+	if (dm->hist_floats < hist_floats) {
+		(void)hipFree(dm->hist); dm->hist = nullptr; dm->hist_floats = 0;
+		BLA_HIP(hipMalloc((void**)&dm->hist, hist_floats * sizeof(float)));
+		dm->hist_floats = hist_floats;
+	}
 	return BLA_OK;
+}
+
+// ---- DPM-Solver++(2M) (Lu, Zhou, Bao, Chen, Li, Zhu 2022) --------------------------------------------------------------------------------------
+// The multistep second-order solver of the probability-flow ODE in the data-prediction form.  alpha = sqrt(abar), sigma = sqrt(1 - abar),
+// lambda = ln(alpha / sigma) (strictly decreasing in t), alpha = 1 and sigma = 0 past the last step.
+
+double log_snr(const bla_diffusion* d, int t) { return 0.5 * std::log(d->alpha_bar[t] / (1.0 - d->alpha_bar[t])); }
+
+// lambda_a - lambda_b from one logarithm of one ratio: the difference of two log_snr values loses ulp(lambda) / |difference| to cancellation
+// (1e-14 at neighbouring steps near t = T), the ratio does not
+double log_snr_diff(const bla_diffusion* d, int a, int b) {
+	const double xa = d->alpha_bar[a], xb = d->alpha_bar[b];
+	return 0.5 * std::log((xa * (1.0 - xb)) / (xb * (1.0 - xa)));
+}
+
+// uniform in lambda between lambda_0 and lambda_{T-1}, each grid point taken to the nearest timestep, then made strictly increasing inside [0, T-1]
+std::vector<int> logsnr_timesteps(const bla_diffusion* d, int S) {
+	const int T = d->steps;
+	std::vector<int> ts(S);
+	if (S == 1) { ts[0] = T - 1; return ts; }
+	std::vector<double> lam(T);
+	for (int t = 0; t < T; t++) lam[t] = log_snr(d, t);
+	int j = 0;   // the first t with lam[t] <= g; the grid falls, so j only moves up
+	for (int i = 0; i < S; i++) {
+		const double g = lam[0] + (lam[T - 1] - lam[0]) * i / (S - 1);
+		while (j < T && lam[j] > g) j++;
+		if (j == 0) ts[i] = 0;
+		else if (j == T) ts[i] = T - 1;
+		else ts[i] = (lam[j - 1] - g) <= (g - lam[j]) ? j - 1 : j;   // a tie takes the lower t
+	}
+	for (int i = 1; i < S; i++) ts[i] = std::max(ts[i], ts[i - 1] + 1);
+	for (int i = S - 1; i >= 0; i--) ts[i] = std::min(ts[i], T - 1 - (S - 1 - i));
+	return ts;
+}
+
+bla_status sample_timesteps(const bla_diffusion* d, int S, int spacing, std::vector<int>* out) {
+	BLA_REQUIRE(S >= 1 && S <= d->steps, BLA_ERR_INVALID, "sample_steps %d outside [1, %d]", S, d->steps);
+	BLA_REQUIRE(spacing == BLA_SPACING_TRAILING || spacing == BLA_SPACING_LOGSNR, BLA_ERR_INVALID, "spacing %d is neither BLA_SPACING_TRAILING nor BLA_SPACING_LOGSNR", spacing);
+	*out = spacing == BLA_SPACING_LOGSNR ? logsnr_timesteps(d, S) : ddim_timesteps(d->steps, S);
+	return BLA_OK;
+}
+
+bla_status check_dpmpp(const bla_diffusion* d, int t_last, int t, int t_prev) {
+	BLA_REQUIRE(t >= 0 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", t, d->steps);
+	BLA_REQUIRE(t_prev >= -1 && t_prev < t, BLA_ERR_INVALID, "t_prev %d outside [-1, %d)", t_prev, t);
+	BLA_REQUIRE(t_last == -1 || (t_last > t && t_last < d->steps), BLA_ERR_INVALID, "t_last %d is neither -1 nor inside (%d, %d)", t_last, t, d->steps);
+	return BLA_OK;
+}
+
+// {inv_sab, s1m, c_x, c_d, w1, w0} of bla_diffusion_dpmpp_coefficients (include/bla.h), in double; the arguments are check_dpmpp's
+void dpmpp_coefficients(const bla_diffusion* d, int t_last, int t, int t_prev, double out[6]) {
+	const double ab = d->alpha_bar[t];
+	out[0] = 1.0 / std::sqrt(ab); out[1] = std::sqrt(1.0 - ab);
+	out[2] = 0.0; out[3] = 1.0; out[4] = 1.0; out[5] = 0.0;
+	if (t_prev < 0) return;   // to the data: the step returns the x0 prediction
+	const double abp = d->alpha_bar[t_prev], h = log_snr_diff(d, t_prev, t);
+	out[2] = std::sqrt(1.0 - abp) / std::sqrt(1.0 - ab);
+	out[3] = -std::sqrt(abp) * std::expm1(-h);
+	if (t_last >= 0) {
+		const double r = log_snr_diff(d, t, t_last) / h;
+		out[4] = 1.0 + 1.0 / (2.0 * r); out[5] = -1.0 / (2.0 * r);
+	}
+}
+
+// the six coefficients rounded to fp32 once on the host and passed by value (nothing is uploaded per step, so a captured sampler replays correctly)
+struct DpmppArgs { float inv_sab, s1m, c_x, c_d, w1, w0; int clip, second; };
+
+DpmppArgs dpmpp_args(const bla_diffusion* d, int t_last, int t, int t_prev, int clip) {
+	double c[6];
+	dpmpp_coefficients(d, t_last, t, t_prev, c);
+	return {(float)c[0], (float)c[1], (float)c[2], (float)c[3], (float)c[4], (float)c[5], clip ? 1 : 0, t_last >= 0 && t_prev >= 0 ? 1 : 0};
+}
+
+// the new x; *x0_out is the (clamped) x0 prediction, the next step's history
+__device__ __forceinline__ float dpmpp1(float x, float e, float hist, const DpmppArgs& a, float* x0_out) {
+#pragma clang fp contract(off)   // as in ddim1: the guided and the unguided instance must fuse the same products
+	float x0 = fmaf(-a.s1m, e, x) * a.inv_sab;
+	if (a.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+	const float D = a.second ? fmaf(a.w0, hist, a.w1 * x0) : x0;
+	*x0_out = x0;
+	return fmaf(a.c_x, x, a.c_d * D);
+}
+
+// One DPM-Solver++(2M) step from t to t_prev in place; ddim_step_kernel's structure (the GUIDED mix, x_copy, temb_next and the class rows are its).
+// hist [n] holds the previous step's x0 prediction: read only when a.second, always written with this step's.  No noise.
+template <bool GUIDED>
+__global__ void __launch_bounds__(kThreads) dpmpp_step_kernel(float* __restrict__ x, float* __restrict__ x_copy, const float* __restrict__ eps_c,
+                                                              const float* __restrict__ eps_u, float s, float* __restrict__ hist, size_t n, DpmppArgs a,
+                                                              int t_prev, int batch, int dim, float* __restrict__ temb_next,
+                                                              const float* __restrict__ ctable, int classes, const int* __restrict__ rows, int vec) {
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	if (temb_next && t_prev >= 0) {
+		const size_t ne = (size_t)(GUIDED ? 2 : 1) * batch * dim;
+		for (size_t i = tid; i < ne; i += stride) {
+			const float e = temb_value(t_prev, (int)(i % dim), dim);
+			const int r = GUIDED && ctable ? rows[i / dim] : -1;
+			temb_next[i] = r >= 0 && r <= classes ? e + ctable[(size_t)r * dim + i % dim] : e;
+		}
+	}
+	const size_t n4 = vec ? n / 4 : 0;
+	for (size_t q = tid; q < n4; q += stride) {
+		float4 e = reinterpret_cast<const float4*>(eps_u)[q];
+		if constexpr (GUIDED) {
+			const float4 c = reinterpret_cast<const float4*>(eps_c)[q];
+			e = make_float4(fmaf(s, c.x - e.x, e.x), fmaf(s, c.y - e.y, e.y), fmaf(s, c.z - e.z, e.z), fmaf(s, c.w - e.w, e.w));
+		}
+		const float4 h = a.second ? reinterpret_cast<const float4*>(hist)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+		float4 v = reinterpret_cast<float4*>(x)[q], p;
+		v = make_float4(dpmpp1(v.x, e.x, h.x, a, &p.x), dpmpp1(v.y, e.y, h.y, a, &p.y), dpmpp1(v.z, e.z, h.z, a, &p.z), dpmpp1(v.w, e.w, h.w, a, &p.w));
+		reinterpret_cast<float4*>(x)[q] = v;
+		reinterpret_cast<float4*>(hist)[q] = p;
+		if (GUIDED && x_copy) reinterpret_cast<float4*>(x_copy)[q] = v;
+	}
+	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
+		const float e = GUIDED ? fmaf(s, eps_c[i] - eps_u[i], eps_u[i]) : eps_u[i];
+		float p;
+		const float v = dpmpp1(x[i], e, a.second ? hist[i] : 0.f, a, &p);
+		x[i] = v;
+		hist[i] = p;
+		if (GUIDED && x_copy) x_copy[i] = v;
+	}
 }
 
 }  // namespace
@@ -546,7 +677,7 @@ bla_status bla_diffusion_create(bla_diffusion** out, int steps, float beta_start
 bla_status bla_diffusion_destroy(bla_diffusion* d) {
 	if (!d) return BLA_OK;
 	(void)hipDeviceSynchronize();
-	(void)hipFree(d->table); (void)hipFree(d->temb); (void)hipFree(d->xg); (void)hipFree(d->rows);
+	(void)hipFree(d->table); (void)hipFree(d->temb); (void)hipFree(d->xg); (void)hipFree(d->rows); (void)hipFree(d->hist);
 	(void)hipFree(d->vlb); (void)hipFree(d->ev); (void)hipFree(d->ev_temb);
 	delete d;
 	return BLA_OK;
@@ -823,6 +954,123 @@ bla_status bla_unet_sample_guided_ddim_f32(bla_unet* m, const bla_diffusion* d, 
 		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
 		if ((st = bla_diffusion_guided_ddim_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, n, F, ts[i], i > 0 ? ts[i - 1] : -1, eta,
 		                                             clip, seed, c.time_dim, dm->temb, d_table, classes, dm->rows)))
+			return st;
+	}
+	BLA_HIP(hipMemcpyAsync(d_x, xg, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	return BLA_OK;
+}
+
+// ---- DPM-Solver++(2M) ---------------------------------------------------------------------------------------------------------------------------
+
+bla_status bla_diffusion_sample_timesteps(const bla_diffusion* d, int sample_steps, int spacing, int* out) {
+	BLA_REQUIRE(d && out, BLA_ERR_INVALID, "null argument");
+	std::vector<int> ts;
+	bla_status st = sample_timesteps(d, sample_steps, spacing, &ts);
+	if (st) return st;
+	for (int i = 0; i < sample_steps; i++) out[i] = ts[i];
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_dpmpp_coefficients(const bla_diffusion* d, int t_last, int t, int t_prev, double out[6]) {
+	BLA_REQUIRE(d && out, BLA_ERR_INVALID, "null argument");
+	bla_status st = check_dpmpp(d, t_last, t, t_prev);
+	if (st) return st;
+	dpmpp_coefficients(d, t_last, t, t_prev, out);
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_dpmpp_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, float* d_x0_hist, int batch, size_t image_floats,
+                                        int t_last, int t, int t_prev, int clip, int time_dim, float* d_temb_next) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(d_x && d_eps_hat && d_x0_hist, BLA_ERR_INVALID, "null argument");
+	if ((st = check_dpmpp(d, t_last, t, t_prev))) return st;
+	const size_t n = (size_t)batch * image_floats;
+	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_hat | (uintptr_t)d_x0_hist) % 16 == 0;
+	hipLaunchKernelGGL((dpmpp_step_kernel<false>), dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, (float*)nullptr,
+	                   (const float*)nullptr, d_eps_hat, 0.f, d_x0_hist, n, dpmpp_args(d, t_last, t, t_prev, clip), t_prev, batch, time_dim, d_temb_next,
+	                   (const float*)nullptr, 0, (const int*)nullptr, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_guided_dpmpp_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond, const float* d_eps_uncond,
+                                               float guidance, float* d_x0_hist, int batch, size_t image_floats, int t_last, int t, int t_prev, int clip,
+                                               int time_dim, float* d_temb_next, const float* d_table, int classes, const int* d_rows) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(d_x && d_eps_cond && d_eps_uncond && d_x0_hist, BLA_ERR_INVALID, "null argument");
+	if ((st = check_dpmpp(d, t_last, t, t_prev))) return st;
+	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
+	BLA_REQUIRE(!d_table || (d_rows && classes >= 1), BLA_ERR_INVALID, "a class table needs the rows [2 batch] and classes >= 1");
+	const size_t n = (size_t)batch * image_floats;
+	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_cond | (uintptr_t)d_eps_uncond | (uintptr_t)d_x_copy | (uintptr_t)d_x0_hist) % 16 == 0;
+	hipLaunchKernelGGL((dpmpp_step_kernel<true>), dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_x_copy, d_eps_cond, d_eps_uncond,
+	                   guidance, d_x0_hist, n, dpmpp_args(d, t_last, t, t_prev, clip), t_prev, batch, time_dim, d_temb_next, d_table, classes, d_rows, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_unet_sample_dpmpp_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, int sample_steps, int spacing, int clip) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d && d_x, BLA_ERR_INVALID, "null argument");
+	std::vector<int> ts;
+	if ((st = sample_timesteps(d, sample_steps, spacing, &ts))) return st;
+	const bla_unet_config& c = *unet_config(m);
+	const int B = bla_unet_batch(m);
+	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);
+	if ((st = grow_workspaces(dm, pick_stream(stream), ne, 0, 0, (size_t)B * F))) return st;
+	hipLaunchKernelGGL(time_embedding_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, pick_stream(stream), (const int*)nullptr, ts.back(), B, c.time_dim, dm->temb);
+	BLA_HIP(hipGetLastError());
+	for (int i = sample_steps - 1, t_last = -1; i >= 0; t_last = ts[i], i--) {
+		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
+		if ((st = bla_diffusion_dpmpp_step_f32(d, stream, d_x, bla_unet_output(m), dm->hist, B, F, t_last, ts[i], i > 0 ? ts[i - 1] : -1, clip, c.time_dim, dm->temb)))
+			return st;
+	}
+	return BLA_OK;
+}
+
+bla_status bla_unet_sample_guided_dpmpp_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes, const int* labels,
+                                            float guidance, int sample_steps, int spacing, int clip) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d && d_x && d_table && labels, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(classes >= 1, BLA_ERR_INVALID, "classes %d", classes);
+	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
+	std::vector<int> ts;
+	if ((st = sample_timesteps(d, sample_steps, spacing, &ts))) return st;
+	const bla_unet_config& c = *unet_config(m);
+	const int B = bla_unet_batch(m), n = B / 2;
+	BLA_REQUIRE(B % 2 == 0, BLA_ERR_INVALID, "the guided sampler needs an even model batch (n conditioned images + their n null-class copies), not %d", B);
+	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
+	hipStream_t s = pick_stream(stream);
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);
+	if ((st = grow_workspaces(dm, s, ne, (size_t)B * F, B, (size_t)n * F))) return st;
+	const int* dev_labels = labels;
+	if (host_pointer(labels)) {   // host labels: checked here, the rows uploaded (not capturable: the copy waits for the host)
+		std::vector<int> rows(B);
+		for (int b = 0; b < n; b++) {
+			BLA_REQUIRE(labels[b] >= 0 && labels[b] <= classes, BLA_ERR_INVALID, "label %d of image %d outside [0, %d]", labels[b], b, classes);
+			rows[b] = labels[b]; rows[n + b] = classes;
+		}
+		BLA_HIP(hipMemcpyAsync(dm->rows, rows.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+		BLA_HIP(hipStreamSynchronize(s));
+		dev_labels = nullptr;
+	}
+	float* xg = dm->xg;
+	BLA_HIP(hipMemcpyAsync(xg, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	BLA_HIP(hipMemcpyAsync(xg + (size_t)n * F, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	hipLaunchKernelGGL(guided_start_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, s, dev_labels, n, classes, dm->rows, d_table, ts.back(), c.time_dim, dm->temb);
+	BLA_HIP(hipGetLastError());
+	const float* out = bla_unet_output(m);
+	for (int i = sample_steps - 1, t_last = -1; i >= 0; t_last = ts[i], i--) {
+		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
+		if ((st = bla_diffusion_guided_dpmpp_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, dm->hist, n, F, t_last, ts[i],
+		                                              i > 0 ? ts[i - 1] : -1, clip, c.time_dim, dm->temb, d_table, classes, dm->rows)))
 			return st;
 	}
 	BLA_HIP(hipMemcpyAsync(d_x, xg, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));

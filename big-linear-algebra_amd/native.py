@@ -162,6 +162,12 @@ SIGNATURES = {
     "bla_unet_sample_ddim_f32": (_I, [_VP, _VP, _VP, _VP, _I, _F, _I, _U64]),
     "bla_diffusion_guided_ddim_step_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _I, _SZ, _I, _I, _F, _I, _U64, _I, _VP, _VP, _I, _VP]),
     "bla_unet_sample_guided_ddim_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _F, _I, _F, _I, _U64]),
+    "bla_diffusion_sample_timesteps": (_I, [_VP, _I, _I, _VP]),
+    "bla_diffusion_dpmpp_coefficients": (_I, [_VP, _I, _I, _I, C.POINTER(C.c_double)]),
+    "bla_diffusion_dpmpp_step_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _SZ, _I, _I, _I, _I, _I, _VP]),
+    "bla_diffusion_guided_dpmpp_step_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, _I, _SZ, _I, _I, _I, _I, _I, _VP, _VP, _I, _VP]),
+    "bla_unet_sample_dpmpp_f32": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I]),
+    "bla_unet_sample_guided_dpmpp_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _F, _I, _I, _I]),
     "bla_diffusion_noise_at_f32": (_I, [_VP, _VP, _VP, _I, _SZ, _I, _VP, _I, _U64, _U64, _VP, _VP, _VP]),
     "bla_diffusion_vlb_terms_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _SZ, _VP, _VP]),
     "bla_diffusion_prior_kl_f32": (_I, [_VP, _VP, _VP, _I, _SZ, _VP]),

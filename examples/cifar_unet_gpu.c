@@ -73,6 +73,14 @@
  *                                                      BLA_UNET_ETA (0 .. 1, default 0: deterministic) scales the noise, BLA_UNET_CLIP=1
  *                                                      clamps the predicted x_0 to [-1, 1].  Bad values stop the program before the device is
  *                                                      opened.  Without BLA_UNET_SAMPLE_STEPS `sample` is unchanged.
+ *   (not in the reference)                             DPM-Solver++(2M) (Lu et al. 2022), the second-order few-step sampler.  `sample` with
+ *                                                      BLA_UNET_SAMPLER=dpmpp and BLA_UNET_SAMPLE_STEPS=S (required): bla_unet_sample_dpmpp_f32
+ *                                                      (bla_unet_sample_guided_dpmpp_f32 with BLA_UNET_CLASS), S forward passes, deterministic;
+ *                                                      BLA_UNET_SPACING=logsnr (default: timesteps uniform in log-SNR) or trailing (DDIM's);
+ *                                                      BLA_UNET_CLIP as for DDIM.  BLA_UNET_SAMPLER=ddim names the DDIM samplers above.  Any
+ *                                                      other sampler or spacing, a missing step count, or dpmpp with BLA_UNET_ETA other than 0
+ *                                                      stops the program before the device is opened.  Without BLA_UNET_SAMPLER `sample` is
+ *                                                      unchanged.
  *   (not in the reference)                             The rest of the DDPM training recipe (Ho et al. 2020), all on the device, all opt-in:
  *                                                      `fit` with BLA_UNET_SHUFFLE=1: every record is uploaded, epoch e takes the permutation
  *                                                      bla_rand_permutation_u32(records, BLA_SEED, (e << 32) + 2^31) and its pass k the entries
@@ -1050,6 +1058,18 @@ static void sample(int count, const char* dir) {
 	const double eta = strtod(eta_env, &eta_end);
 	if (*eta_end || !(eta >= 0 && eta <= 1)) { fprintf(stderr, "sample: BLA_UNET_ETA=%s; eta must lie in [0, 1]\n", eta_env); exit(1); }
 	const int clip = env_flag("BLA_UNET_CLIP");
+	/* BLA_UNET_SAMPLER=dpmpp: DPM-Solver++(2M) over BLA_UNET_SAMPLE_STEPS steps spaced by BLA_UNET_SPACING; checked before the device is opened */
+	const char* sampler_env = getenv("BLA_UNET_SAMPLER");
+	int dpmpp = 0, spacing = BLA_SPACING_LOGSNR;
+	if (sampler_env && *sampler_env) {
+		if (strcmp(sampler_env, "dpmpp") == 0) dpmpp = 1;
+		else if (strcmp(sampler_env, "ddim") != 0) { fprintf(stderr, "sample: BLA_UNET_SAMPLER=%s; the samplers are ddim and dpmpp\n", sampler_env); exit(1); }
+		const char* spacing_env = env_or("BLA_UNET_SPACING", "logsnr");
+		if (strcmp(spacing_env, "trailing") == 0) spacing = BLA_SPACING_TRAILING;
+		else if (strcmp(spacing_env, "logsnr") != 0) { fprintf(stderr, "sample: BLA_UNET_SPACING=%s; the spacings are logsnr and trailing\n", spacing_env); exit(1); }
+		if (!ddim) { fprintf(stderr, "sample: BLA_UNET_SAMPLER=%s needs BLA_UNET_SAMPLE_STEPS\n", sampler_env); exit(1); }
+		if (dpmpp && eta != 0) { fprintf(stderr, "sample: BLA_UNET_ETA=%s; BLA_UNET_SAMPLER=dpmpp is deterministic and takes no eta\n", eta_env); exit(1); }
+	}
 	/* BLA_UNET_CLASS=k: guided sampling of class k with the table fit wrote; both checked before the device is opened */
 	const char* class_env = getenv("BLA_UNET_CLASS");
 	const int guided = class_env && *class_env;
@@ -1093,7 +1113,10 @@ static void sample(int count, const char* dir) {
 	int done = 0;
 	for (unsigned long long k = 0; done < count; k++) {
 		CHECK(bla_rand_normal_f32(NULL, dv.x, (size_t)batch * IMAGE_FLOATS, 0.f, 1.f, seed + k, 0));   /* x_T */
-		if (guided && ddim)
+		if (guided && dpmpp)
+			CHECK(bla_unet_sample_guided_dpmpp_f32(dv.net, diff, NULL, dv.x, d_table, CLASSES, d_labels, guidance, sample_steps, spacing, clip));
+		else if (dpmpp) CHECK(bla_unet_sample_dpmpp_f32(dv.net, diff, NULL, dv.x, sample_steps, spacing, clip));
+		else if (guided && ddim)
 			CHECK(bla_unet_sample_guided_ddim_f32(dv.net, diff, NULL, dv.x, d_table, CLASSES, d_labels, guidance, sample_steps, (float)eta, clip, seed + k));
 		else if (guided) CHECK(bla_unet_sample_guided_f32(dv.net, diff, NULL, dv.x, d_table, CLASSES, d_labels, guidance, seed + k));
 		else if (ddim) CHECK(bla_unet_sample_ddim_f32(dv.net, diff, NULL, dv.x, sample_steps, (float)eta, clip, seed + k));

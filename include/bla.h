@@ -614,6 +614,58 @@ BLA_API bla_status bla_diffusion_guided_ddim_step_f32(const bla_diffusion* d, vo
 BLA_API bla_status bla_unet_sample_guided_ddim_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes,
                                                    const int* labels, float guidance, int sample_steps, float eta, int clip, unsigned long long seed);
 
+/* ---- DPM-Solver++(2M) sampling (Lu, Zhou, Bao, Chen, Li, Zhu 2022) ----------------------------------------------------------------------------
+ * Not in the reference.  The second-order multistep solver of the probability-flow ODE in the data-prediction form: one forward pass per step like
+ * DDIM at eta = 0 (which is its first-order member), plus one buffer with the previous step's x0 prediction.  Deterministic: no noise, no seed.
+ * With abar_t the doubles of bla_diffusion_schedule: alpha_t = sqrt(abar_t), sigma_t = sqrt(1 - abar_t), lambda_t = ln(alpha_t / sigma_t) =
+ * ln(abar_t / (1 - abar_t)) / 2 (half the log-SNR, strictly decreasing in t); past the last step (t_prev = -1) alpha = 1 and sigma = 0.
+ *
+ * The timesteps of a run of S = sample_steps, increasing, out[S - 1] = steps - 1.  Host only.
+ *   BLA_SPACING_TRAILING: exactly bla_diffusion_ddim_timesteps.
+ *   BLA_SPACING_LOGSNR:   uniform in lambda, where the solver's error constants are smallest.  S = 1: {steps - 1}.  S >= 2: the grid
+ *                         g_i = lambda_0 + (lambda_{T-1} - lambda_0) i / (S - 1), out[i] = the t whose lambda_t is nearest g_i (a tie takes the lower t),
+ *                         then out[i] = max(out[i], out[i-1] + 1) for i = 1 .. S-1 and out[i] = min(out[i], T-1 - (S-1-i)) for i = S-1 .. 0: strictly
+ *                         increasing, out[0] = 0, and S = steps gives every step.
+ * S outside [1, steps] or any other spacing: BLA_ERR_INVALID. */
+enum { BLA_SPACING_TRAILING = 0, BLA_SPACING_LOGSNR = 1 };
+BLA_API bla_status bla_diffusion_sample_timesteps(const bla_diffusion* d, int sample_steps, int spacing, int* out);
+/* The coefficients of the step from t to t_prev (-1: to the data) whose previous step came from t_last (-1: there was none), in double:
+ * out = {inv_sab = 1 / alpha_t, s1m = sigma_t, c_x, c_d, w1, w0}.  With h = lambda_{t_prev} - lambda_t (> 0):
+ *   t_prev >= 0:  c_x = sigma_p / sigma_t, c_d = -alpha_p expm1(-h);      t_prev = -1:  c_x = 0, c_d = 1 (the step returns the x0 prediction);
+ *   t_last >= 0 and t_prev >= 0 (second order):  r = (lambda_t - lambda_{t_last}) / h, w1 = 1 + 1 / (2 r), w0 = -1 / (2 r);      otherwise w1 = 1, w0 = 0.
+ * Differences of lambda are taken as one logarithm of one ratio of the schedule's doubles, not as a difference of two logarithms.
+ * t outside [0, steps), t_prev outside [-1, t), t_last neither -1 nor inside (t, steps): BLA_ERR_INVALID.  Host only. */
+BLA_API bla_status bla_diffusion_dpmpp_coefficients(const bla_diffusion* d, int t_last, int t, int t_prev, double out[6]);
+/* One DPM-Solver++(2M) step in place, one launch.  Per element, with the six coefficients above rounded to fp32 once on the host and passed by value
+ * (nothing is uploaded per step, so a captured sampler replays correctly) and every fused operation spelled out:
+ *   x0   = fmaf(-s1m, eps_hat, x) * inv_sab, clamped to [-1, 1] when clip is non-zero;
+ *   D    = fmaf(w0, hist, w1 * x0) in the second-order case, else x0;
+ *   x    = fmaf(c_x, x, c_d * D);      hist = x0 (the clamped one), always written.
+ * d_x0_hist [batch][image_floats] (never NULL) is the caller's: it is read only in the second-order case, so its contents before the first step of
+ * a run (t_last = -1) do not matter; hand the same buffer to every step of a run.  The last step (t_prev = -1) is first order and leaves x equal to
+ * the x0 prediction it stores.  With t_last = -1 and clip 0 the step is the DDIM step at eta = 0 in another arrangement (where the clamp acts the two differ: DDIM keeps eps_hat beside the clamped prediction, this solver's update sees eps only through it).  d_temb_next (may be NULL)
+ * [batch][time_dim]: the embedding of t_prev (nothing at t_prev = -1).  16-byte loads and stores when d_x, d_eps_hat and d_x0_hist are 16-byte
+ * aligned (a tail of batch * image_floats % 4 elements one by one), one element per lane otherwise.  Arguments refused as by
+ * bla_diffusion_ddim_step_f32 and bla_diffusion_dpmpp_coefficients. */
+BLA_API bla_status bla_diffusion_dpmpp_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, float* d_x0_hist, int batch,
+                                                size_t image_floats, int t_last, int t, int t_prev, int clip, int time_dim, float* d_temb_next);
+/* The guided step: eps~ = fmaf(guidance, eps_c - eps_u, eps_u) as in bla_diffusion_guided_ddim_step_f32, then the step above (the same kernel:
+ * guidance 0 = the unguided step on eps_u, bit for bit).  d_x_copy (may be NULL) receives the new x, d_temb_next [2 batch][time_dim] the embedding of
+ * t_prev plus the class rows (nothing at t_prev = -1), as for bla_diffusion_guided_step_f32.  d_x0_hist is [batch][image_floats].  One launch. */
+BLA_API bla_status bla_diffusion_guided_dpmpp_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond,
+                                                       const float* d_eps_uncond, float guidance, float* d_x0_hist, int batch, size_t image_floats,
+                                                       int t_last, int t, int t_prev, int clip, int time_dim, float* d_temb_next, const float* d_table,
+                                                       int classes, const int* d_rows);
+/* DPM-Solver++(2M) sampling on the model's batch: bla_unet_sample_ddim_f32's loop over bla_diffusion_sample_timesteps(sample_steps, spacing) from
+ * the last, bla_unet_forward_f32 (no dropout) then bla_diffusion_dpmpp_step_f32, t_last = -1 at the first step and the previous step's t afterwards.
+ * d_x: in x_T, out x_0.  The history buffer [B][C][H][W] joins the diffusion object's workspaces (allocated on first use: run once eagerly before
+ * capturing it into a graph); no host round trip inside the loop.  Bad sample_steps or spacing: BLA_ERR_INVALID. */
+BLA_API bla_status bla_unet_sample_dpmpp_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, int sample_steps, int spacing, int clip);
+/* Guided DPM-Solver++(2M) sampling: bla_unet_sample_guided_ddim_f32's loop (model batch 2n, labels, rows, workspaces and their rules) with the
+ * timesteps, the guided step and the t_last bookkeeping above; the history buffer is [n][C][H][W]. */
+BLA_API bla_status bla_unet_sample_guided_dpmpp_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes,
+                                                    const int* labels, float guidance, int sample_steps, int spacing, int clip);
+
 /* ---- held-out evaluation: the variational bound of Ho et al. 2020 (eq. 5) in nats per image ------------------------------------------------
  * Not in the reference.  With T = bla_diffusion_steps, beta_t / abar_t the doubles of bla_diffusion_schedule, alpha_t = 1 - beta_t, abar_{-1} = 1,
  * beta~_t = beta_t (1 - abar_{t-1}) / (1 - abar_t), F = image_floats and this project's fixed variance sigma_t^2 = beta_t:
