@@ -42,6 +42,10 @@ struct bla_diffusion {
 	size_t ev_floats = 0;
 	float* ev_temb = nullptr;
 	size_t ev_temb_floats = 0;
+	int prediction = BLA_PREDICT_EPS;   // what the model's output is read as (bla_diffusion_set_objective)
+	double min_snr_gamma = 0.0;         // 0: every timestep weighs 1
+	std::vector<double> loss_w;         // the loss weights w_t in double (empty until an objective is set: all 1)
+	float* loss_w_dev = nullptr;        // device, steps: loss_w rounded to fp32 once (NULL: all 1)
 };
 
 namespace {
@@ -638,25 +642,151 @@ __global__ void __launch_bounds__(kThreads) dpmpp_step_kernel(float* __restrict_
 	}
 }
 
-}  // namespace
+// ---- training objectives: what the network predicts and how a timestep's loss is weighted (include/bla.h) ---------------------------------------
+// a = sqrt(abar_t) and c = sqrt(1 - abar_t) are the fp32 table values.  v = a eps - c x0 (Salimans & Ho 2022); back to eps given the x_t the model saw:
+// eps = a v + c x_t from v, eps = (x_t - a x0) / c from x0.  Every fused operation is spelled out.
+__device__ __forceinline__ float v_target1(float a, float e, float c, float x0) {
+#pragma clang fp contract(off)
+	return fmaf(a, e, -(c * x0));
+}
+__device__ __forceinline__ float v_to_eps1(float a, float v, float c, float x) {
+#pragma clang fp contract(off)
+	return fmaf(a, v, c * x);
+}
+// a true division by the table's c (correctly rounded), not a product with a reciprocal; the numerator is one fused operation
+__device__ __forceinline__ float x0_to_eps1(float a, float x0, float c, float x) {
+#pragma clang fp contract(off)
+	return fmaf(-a, x0, x) / c;
+}
 
-extern "C" {
+// element e of [batch][F] belongs to image e / F; its timestep, -1 when outside [0, steps)
+__device__ __forceinline__ int step_of(const int* __restrict__ d_t, int t_const, size_t b, int steps) {
+	const int t = d_t ? d_t[b] : t_const;
+	return t >= 0 && t < steps ? t : -1;
+}
 
-bla_status bla_diffusion_create(bla_diffusion** out, int steps, float beta_start, float beta_end) {
-	bla_status st = require_ready();
-	if (st) return st;
-	BLA_REQUIRE(out, BLA_ERR_INVALID, "null argument");
-	BLA_REQUIRE(steps >= 1 && steps <= (1 << 24), BLA_ERR_INVALID, "steps %d", steps);
-	BLA_REQUIRE(beta_start > 0.f && beta_end > 0.f && beta_start < 1.f && beta_end < 1.f, BLA_ERR_INVALID, "betas (%g, %g) outside (0, 1)", beta_start, beta_end);
-	bla_diffusion* d = new bla_diffusion();
-	d->steps = steps;
-	d->beta.resize(steps); d->alpha_bar.resize(steps);
+// target [batch][F] of the prediction type `pred` and weight[b] = w[t_b] (1 where lw is NULL).  An image whose t lies outside [0, steps): zeros, weight 0.
+// x0 is read only for X0 and V, eps only for EPS and V.  The 16-byte body runs over the flat array, so a float4 may hold the end of one image and the
+// start of the next: each component looks up its own image.
+__global__ void __launch_bounds__(kThreads) target_kernel(const float* __restrict__ x0, const float* __restrict__ eps, const int* __restrict__ d_t, int t_const,
+                                                          int batch, size_t F, int steps, int pred, const float* __restrict__ table,
+                                                          const float* __restrict__ lw, float* __restrict__ target, float* __restrict__ weight, int vec) {
+	const float* sab = table + TAB_SQRT_AB * steps;
+	const float* s1m = table + TAB_SQRT_1MAB * steps;
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	if (weight)
+		for (size_t b = tid; b < (size_t)batch; b += stride) {
+			const int t = step_of(d_t, t_const, b, steps);
+			weight[b] = t < 0 ? 0.f : (lw ? lw[t] : 1.f);
+		}
+	const size_t n = (size_t)batch * F, n4 = vec ? n / 4 : 0;
+	for (size_t q = tid; q < n4; q += stride) {
+		const float4 e4 = pred != BLA_PREDICT_X0 ? reinterpret_cast<const float4*>(eps)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+		const float4 x4 = pred != BLA_PREDICT_EPS ? reinterpret_cast<const float4*>(x0)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+		const float e[4] = {e4.x, e4.y, e4.z, e4.w}, x[4] = {x4.x, x4.y, x4.z, x4.w};
+		float r[4];
+		size_t b = (4 * q) / F, p = 4 * q - b * F;
+		for (int k = 0; k < 4; k++, p++) {
+			while (p >= F) { p -= F; b++; }
+			const int t = step_of(d_t, t_const, b, steps);
+			if (t < 0) r[k] = 0.f;
+			else if (pred == BLA_PREDICT_EPS) r[k] = e[k];
+			else if (pred == BLA_PREDICT_X0) r[k] = x[k];
+			else r[k] = v_target1(sab[t], e[k], s1m[t], x[k]);
+		}
+		reinterpret_cast<float4*>(target)[q] = make_float4(r[0], r[1], r[2], r[3]);
+	}
+	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
+		const int t = step_of(d_t, t_const, i / F, steps);
+		float r = 0.f;
+		if (t >= 0) r = pred == BLA_PREDICT_EPS ? eps[i] : (pred == BLA_PREDICT_X0 ? x0[i] : v_target1(sab[t], eps[i], s1m[t], x0[i]));
+		target[i] = r;
+	}
+}
+
+// pred [batch][F] <- eps_hat in place, from v (pred_type V) or from x0 (X0), given the x_t the model saw.  An image whose t lies outside [0, steps) is
+// left as it is.  target_kernel's structure.
+__global__ void __launch_bounds__(kThreads) to_eps_kernel(float* __restrict__ pred, const float* __restrict__ x, const int* __restrict__ d_t, int t_const, int batch,
+                                                          size_t F, int steps, int pred_type, const float* __restrict__ table, int vec) {
+	const float* sab = table + TAB_SQRT_AB * steps;
+	const float* s1m = table + TAB_SQRT_1MAB * steps;
+	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+	const size_t n = (size_t)batch * F, n4 = vec ? n / 4 : 0;
+	for (size_t q = tid; q < n4; q += stride) {
+		const float4 p4 = reinterpret_cast<const float4*>(pred)[q], x4 = reinterpret_cast<const float4*>(x)[q];
+		float r[4] = {p4.x, p4.y, p4.z, p4.w};
+		const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
+		size_t b = (4 * q) / F, p = 4 * q - b * F;
+		for (int k = 0; k < 4; k++, p++) {
+			while (p >= F) { p -= F; b++; }
+			const int t = step_of(d_t, t_const, b, steps);
+			if (t >= 0) r[k] = pred_type == BLA_PREDICT_V ? v_to_eps1(sab[t], r[k], s1m[t], xs[k]) : x0_to_eps1(sab[t], r[k], s1m[t], xs[k]);
+		}
+		reinterpret_cast<float4*>(pred)[q] = make_float4(r[0], r[1], r[2], r[3]);
+	}
+	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
+		const int t = step_of(d_t, t_const, i / F, steps);
+		if (t >= 0) pred[i] = pred_type == BLA_PREDICT_V ? v_to_eps1(sab[t], pred[i], s1m[t], x[i]) : x0_to_eps1(sab[t], pred[i], s1m[t], x[i]);
+	}
+}
+
+// g = (2 w) (out - target): 2 w is exact, the difference is one rounding and the product one.  w = 1: 2 (out - target), the U-Net's own seed bit for bit.
+__device__ __forceinline__ float loss_grad1(float w2, float o, float t) {
+#pragma clang fp contract(off)
+	return w2 * (o - t);
+}
+
+// One workgroup per image (vlb_terms_kernel's reduction): g [F] of the image (g may be NULL) and loss[b] = w_b sum_i (out_i - target_i)^2 in double (loss
+// may be NULL).  Every lane sums its elements in index order, the 256 partials go through block_sum: no atomics, bit-reproducible.
+__global__ void __launch_bounds__(kThreads) weighted_loss_kernel(const float* __restrict__ out, const float* __restrict__ target, const float* __restrict__ weight,
+                                                                 size_t F, float* __restrict__ g, double* __restrict__ loss, int vec) {
+#pragma clang fp contract(off)
+	__shared__ double part[kThreads];
+	const size_t b = blockIdx.x, base = b * F;
+	const float w = weight ? weight[b] : 1.f, w2 = 2.f * w;
+	double sq = 0.0;
+	if (vec) {
+		const float4* o4 = reinterpret_cast<const float4*>(out + base);
+		const float4* t4 = reinterpret_cast<const float4*>(target + base);
+		for (size_t q = threadIdx.x; q < F / 4; q += kThreads) {
+			const float4 o = o4[q], t = t4[q];
+			if (loss) {
+				const double dx = (double)o.x - (double)t.x, dy = (double)o.y - (double)t.y, dz = (double)o.z - (double)t.z, dw = (double)o.w - (double)t.w;
+				sq += dx * dx; sq += dy * dy; sq += dz * dz; sq += dw * dw;
+			}
+			if (g) reinterpret_cast<float4*>(g + base)[q] = make_float4(loss_grad1(w2, o.x, t.x), loss_grad1(w2, o.y, t.y), loss_grad1(w2, o.z, t.z), loss_grad1(w2, o.w, t.w));
+		}
+	} else {
+		for (size_t i = threadIdx.x; i < F; i += kThreads) {
+			const float o = out[base + i], t = target[base + i];
+			if (loss) { const double d = (double)o - (double)t; sq += d * d; }
+			if (g) g[base + i] = loss_grad1(w2, o, t);
+		}
+	}
+	if (!loss) return;   // uniform over the workgroup
+	sq = block_sum(sq, part);
+	if (threadIdx.x == 0) loss[b] = (double)w * sq;
+}
+
+// w_t of bla_diffusion_set_objective in this order of operations (the tests restate it operation for operation)
+double loss_weight(double alpha_bar, int prediction, double gamma) {
+#pragma clang fp contract(off)
+	if (gamma == 0.0) return 1.0;
+	const double snr = alpha_bar / (1.0 - alpha_bar), m = snr < gamma ? snr : gamma;
+	if (prediction == BLA_PREDICT_EPS) return snr > 0.0 ? m / snr : 1.0;   // alpha_bar underflown to 0 (a very long schedule): the limit of min(SNR, gamma) / SNR, not 0 / 0
+	return prediction == BLA_PREDICT_X0 ? m : m / (snr + 1.0);
+}
+
+// the tail of both constructors: alpha_bar, the five fp32 tables and the VLB weights from d->beta (steps values inside (0, 1))
+bla_status finish_create(bla_diffusion* d, bla_diffusion** out, const char* who) {
+	const int steps = d->steps;
+	d->alpha_bar.resize(steps);
 	std::vector<float> tab((size_t)5 * steps);
 	double ab = 1.0;
 	for (int t = 0; t < steps; t++) {
-		const double b = steps == 1 ? (double)beta_start : (double)beta_start + ((double)beta_end - beta_start) * t / (steps - 1);   // linspace
+		const double b = d->beta[t];
 		ab *= 1.0 - b;
-		d->beta[t] = b; d->alpha_bar[t] = ab;
+		d->alpha_bar[t] = ab;
 		tab[TAB_SQRT_AB * steps + t] = (float)std::sqrt(ab);
 		tab[TAB_SQRT_1MAB * steps + t] = (float)std::sqrt(1.0 - ab);
 		tab[TAB_EPS_COEF * steps + t] = (float)(b / std::sqrt(1.0 - ab));
@@ -669,8 +799,139 @@ bla_status bla_diffusion_create(bla_diffusion** out, int steps, float beta_start
 	for (int t = 1; t < steps; t++) vlb_weights(d->beta, d->alpha_bar, t, &vlb[t], &vlb[steps + t]);
 	if (e == hipSuccess) e = hipMalloc((void**)&d->vlb, vlb.size() * sizeof(double));
 	if (e == hipSuccess) e = hipMemcpy(d->vlb, vlb.data(), vlb.size() * sizeof(double), hipMemcpyHostToDevice);
-	if (e != hipSuccess) { (void)hipFree(d->table); (void)hipFree(d->vlb); delete d; return hip_fail(e, "bla_diffusion_create"); }
+	if (e != hipSuccess) { (void)hipFree(d->table); (void)hipFree(d->vlb); delete d; return hip_fail(e, who); }
 	*out = d;
+	return BLA_OK;
+}
+
+// what every sampling and evaluation loop calls right behind bla_unet_forward_f32: the model's output read as d's prediction type becomes eps_hat in
+// place, given the buffer the model was given (all `batch` images at timestep t).  EPS: nothing is launched, so those loops keep their bits.
+bla_status output_to_eps(bla_unet* m, const bla_diffusion* d, void* stream, const float* d_x, int batch, size_t image_floats, int t) {
+	if (d->prediction == BLA_PREDICT_EPS) return BLA_OK;
+	return bla_diffusion_to_eps_f32(d, stream, bla_unet_output(m), d_x, nullptr, t, batch, image_floats);
+}
+
+}  // namespace
+
+extern "C" {
+
+bla_status bla_diffusion_create(bla_diffusion** out, int steps, float beta_start, float beta_end) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(out, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(steps >= 1 && steps <= (1 << 24), BLA_ERR_INVALID, "steps %d", steps);
+	BLA_REQUIRE(beta_start > 0.f && beta_end > 0.f && beta_start < 1.f && beta_end < 1.f, BLA_ERR_INVALID, "betas (%g, %g) outside (0, 1)", beta_start, beta_end);
+	bla_diffusion* d = new bla_diffusion();
+	d->steps = steps;
+	d->beta.resize(steps);
+	for (int t = 0; t < steps; t++)
+		d->beta[t] = steps == 1 ? (double)beta_start : (double)beta_start + ((double)beta_end - beta_start) * t / (steps - 1);   // linspace
+	return finish_create(d, out, "bla_diffusion_create");
+}
+
+bla_status bla_diffusion_cosine_betas(int steps, double s, double max_beta, double* out) {
+	BLA_REQUIRE(out, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(steps >= 1, BLA_ERR_INVALID, "steps %d", steps);
+	BLA_REQUIRE(s >= 0.0 && std::isfinite(s), BLA_ERR_INVALID, "offset s %g is negative or not finite", s);
+	BLA_REQUIRE(max_beta > 0.0 && max_beta < 1.0, BLA_ERR_INVALID, "max_beta %g outside (0, 1)", max_beta);
+	auto f = [&](int i) { const double c = std::cos(((double)i / steps + s) / (1.0 + s) * M_PI / 2); return c * c; };
+	double fi = f(0);
+	for (int i = 0; i < steps; i++) {
+		const double fn = f(i + 1), b = 1.0 - fn / fi;
+		out[i] = b < max_beta ? b : max_beta;
+		fi = fn;
+	}
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_create_from_betas(bla_diffusion** out, int steps, const double* betas) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(out && betas, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(steps >= 1 && steps <= (1 << 24), BLA_ERR_INVALID, "steps %d", steps);
+	for (int t = 0; t < steps; t++) BLA_REQUIRE(betas[t] > 0.0 && betas[t] < 1.0, BLA_ERR_INVALID, "beta %g of step %d outside (0, 1)", betas[t], t);   // NaN fails both
+	bla_diffusion* d = new bla_diffusion();
+	d->steps = steps;
+	d->beta.assign(betas, betas + steps);
+	return finish_create(d, out, "bla_diffusion_create_from_betas");
+}
+
+bla_status bla_diffusion_set_objective(bla_diffusion* d, int prediction, double min_snr_gamma) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(d, BLA_ERR_INVALID, "null diffusion object");
+	BLA_REQUIRE(prediction == BLA_PREDICT_EPS || prediction == BLA_PREDICT_X0 || prediction == BLA_PREDICT_V, BLA_ERR_INVALID,
+	            "prediction %d is none of BLA_PREDICT_EPS, BLA_PREDICT_X0, BLA_PREDICT_V", prediction);
+	BLA_REQUIRE(min_snr_gamma >= 0.0 && std::isfinite(min_snr_gamma), BLA_ERR_INVALID, "min_snr_gamma %g is negative or not finite", min_snr_gamma);
+	std::vector<double> w(d->steps);
+	std::vector<float> wf(d->steps);
+	for (int t = 0; t < d->steps; t++) { w[t] = loss_weight(d->alpha_bar[t], prediction, min_snr_gamma); wf[t] = (float)w[t]; }
+	BLA_HIP(hipDeviceSynchronize());   // a launch in flight may still read the old table
+	if (!d->loss_w_dev) BLA_HIP(hipMalloc((void**)&d->loss_w_dev, (size_t)d->steps * sizeof(float)));
+	BLA_HIP(hipMemcpy(d->loss_w_dev, wf.data(), (size_t)d->steps * sizeof(float), hipMemcpyHostToDevice));
+	d->loss_w.swap(w);
+	d->prediction = prediction; d->min_snr_gamma = min_snr_gamma;
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_objective(const bla_diffusion* d, int* prediction, double* min_snr_gamma) {
+	BLA_REQUIRE(d, BLA_ERR_INVALID, "null diffusion object");
+	if (prediction) *prediction = d->prediction;
+	if (min_snr_gamma) *min_snr_gamma = d->min_snr_gamma;
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_loss_weight(const bla_diffusion* d, int t, double* w) {
+	BLA_REQUIRE(d && w && t >= 0 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", t, d ? d->steps : 0);
+	*w = d->loss_w.empty() ? 1.0 : d->loss_w[t];
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_target_f32(const bla_diffusion* d, void* stream, const float* d_x0, const float* d_eps, const int* d_t, int t_const, int batch,
+                                    size_t image_floats, float* d_target, float* d_weight) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, 1))) return st;
+	BLA_REQUIRE(d_target, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(d->prediction == BLA_PREDICT_X0 || d_eps, BLA_ERR_INVALID, "this prediction type needs d_eps");
+	BLA_REQUIRE(d->prediction == BLA_PREDICT_EPS || d_x0, BLA_ERR_INVALID, "this prediction type needs d_x0");
+	BLA_REQUIRE(d_t || (t_const >= 0 && t_const < d->steps), BLA_ERR_INVALID, "timestep %d outside [0, %d)", t_const, d->steps);
+	const float* x0 = d->prediction == BLA_PREDICT_EPS ? nullptr : d_x0;     // the inputs this type does not read are not looked at
+	const float* eps = d->prediction == BLA_PREDICT_X0 ? nullptr : d_eps;
+	const size_t n = (size_t)batch * image_floats;
+	const int vec = ((uintptr_t)x0 | (uintptr_t)eps | (uintptr_t)d_target) % 16 == 0;
+	hipLaunchKernelGGL(target_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), x0, eps, d_t, t_const, batch, image_floats, d->steps,
+	                   d->prediction, d->table, d->loss_w_dev, d_target, d_weight, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_to_eps_f32(const bla_diffusion* d, void* stream, float* d_pred, const float* d_x, const int* d_t, int t_const, int batch,
+                                    size_t image_floats) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, 1))) return st;
+	BLA_REQUIRE(d_pred && d_x, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(d_t || (t_const >= 0 && t_const < d->steps), BLA_ERR_INVALID, "timestep %d outside [0, %d)", t_const, d->steps);
+	if (d->prediction == BLA_PREDICT_EPS) return BLA_OK;
+	const size_t n = (size_t)batch * image_floats;
+	const int vec = ((uintptr_t)d_pred | (uintptr_t)d_x) % 16 == 0;
+	hipLaunchKernelGGL(to_eps_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_pred, d_x, d_t, t_const, batch, image_floats, d->steps,
+	                   d->prediction, d->table, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_diffusion_loss_f32(void* stream, const float* d_out, const float* d_target, const float* d_weight, int batch, size_t image_floats, float* d_g,
+                                  double* d_loss) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(d_out && d_target, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(batch >= 1 && image_floats >= 1, BLA_ERR_INVALID, "batch %d, image_floats %zu", batch, image_floats);
+	if (!d_g && !d_loss) return BLA_OK;
+	const int vec = image_floats % 4 == 0 && ((uintptr_t)d_out | (uintptr_t)d_target | (uintptr_t)d_g) % 16 == 0;
+	hipLaunchKernelGGL(weighted_loss_kernel, dim3(batch), dim3(kThreads), 0, pick_stream(stream), d_out, d_target, d_weight, image_floats, d_g, d_loss, vec);
+	BLA_HIP(hipGetLastError());
 	return BLA_OK;
 }
 
@@ -678,7 +939,7 @@ bla_status bla_diffusion_destroy(bla_diffusion* d) {
 	if (!d) return BLA_OK;
 	(void)hipDeviceSynchronize();
 	(void)hipFree(d->table); (void)hipFree(d->temb); (void)hipFree(d->xg); (void)hipFree(d->rows); (void)hipFree(d->hist);
-	(void)hipFree(d->vlb); (void)hipFree(d->ev); (void)hipFree(d->ev_temb);
+	(void)hipFree(d->vlb); (void)hipFree(d->ev); (void)hipFree(d->ev_temb); (void)hipFree(d->loss_w_dev);
 	delete d;
 	return BLA_OK;
 }
@@ -762,6 +1023,7 @@ bla_status bla_unet_sample_f32(bla_unet* m, const bla_diffusion* d, void* stream
 	BLA_HIP(hipGetLastError());
 	for (int t = T - 1; t >= 0; t--) {
 		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
+		if ((st = output_to_eps(m, d, stream, d_x, B, F, t))) return st;
 		if ((st = bla_diffusion_step_f32(d, stream, d_x, bla_unet_output(m), B, F, t, seed, c.time_dim, dm->temb))) return st;
 	}
 	return BLA_OK;
@@ -835,6 +1097,7 @@ bla_status bla_unet_sample_guided_f32(bla_unet* m, const bla_diffusion* d, void*
 	const float* out = bla_unet_output(m);
 	for (int t = T - 1; t >= 0; t--) {
 		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
+		if ((st = output_to_eps(m, d, stream, xg, B, F, t))) return st;
 		if ((st = bla_diffusion_guided_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, n, F, t, seed, c.time_dim, dm->temb, d_table,
 		                                        classes, dm->rows)))
 			return st;
@@ -892,6 +1155,7 @@ bla_status bla_unet_sample_ddim_f32(bla_unet* m, const bla_diffusion* d, void* s
 	BLA_HIP(hipGetLastError());
 	for (int i = sample_steps - 1; i >= 0; i--) {
 		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
+		if ((st = output_to_eps(m, d, stream, d_x, B, F, ts[i]))) return st;
 		if ((st = bla_diffusion_ddim_step_f32(d, stream, d_x, bla_unet_output(m), B, F, ts[i], i > 0 ? ts[i - 1] : -1, eta, clip, seed, c.time_dim, dm->temb)))
 			return st;
 	}
@@ -952,6 +1216,7 @@ bla_status bla_unet_sample_guided_ddim_f32(bla_unet* m, const bla_diffusion* d, 
 	const float* out = bla_unet_output(m);
 	for (int i = sample_steps - 1; i >= 0; i--) {
 		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
+		if ((st = output_to_eps(m, d, stream, xg, B, F, ts[i]))) return st;
 		if ((st = bla_diffusion_guided_ddim_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, n, F, ts[i], i > 0 ? ts[i - 1] : -1, eta,
 		                                             clip, seed, c.time_dim, dm->temb, d_table, classes, dm->rows)))
 			return st;
@@ -1028,6 +1293,7 @@ bla_status bla_unet_sample_dpmpp_f32(bla_unet* m, const bla_diffusion* d, void* 
 	BLA_HIP(hipGetLastError());
 	for (int i = sample_steps - 1, t_last = -1; i >= 0; t_last = ts[i], i--) {
 		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
+		if ((st = output_to_eps(m, d, stream, d_x, B, F, ts[i]))) return st;
 		if ((st = bla_diffusion_dpmpp_step_f32(d, stream, d_x, bla_unet_output(m), dm->hist, B, F, t_last, ts[i], i > 0 ? ts[i - 1] : -1, clip, c.time_dim, dm->temb)))
 			return st;
 	}
@@ -1069,6 +1335,7 @@ bla_status bla_unet_sample_guided_dpmpp_f32(bla_unet* m, const bla_diffusion* d,
 	const float* out = bla_unet_output(m);
 	for (int i = sample_steps - 1, t_last = -1; i >= 0; t_last = ts[i], i--) {
 		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
+		if ((st = output_to_eps(m, d, stream, xg, B, F, ts[i]))) return st;
 		if ((st = bla_diffusion_guided_dpmpp_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, dm->hist, n, F, t_last, ts[i],
 		                                              i > 0 ? ts[i - 1] : -1, clip, c.time_dim, dm->temb, d_table, classes, dm->rows)))
 			return st;
@@ -1174,6 +1441,7 @@ bla_status bla_unet_evaluate_f32(bla_unet* m, const bla_diffusion* d, void* stre
 			return st;
 		if (d_table && (st = bla_class_embedding_f32(stream, d_table, classes, d_rows, B, c.time_dim, 0.f, seed, 0, dm->rows, dm->ev_temb))) return st;
 		if ((st = bla_unet_forward_f32(m, stream, xt, dm->ev_temb, nullptr))) return st;
+		if ((st = output_to_eps(m, d, stream, xt, B, F, t))) return st;
 		if ((st = bla_diffusion_vlb_terms_f32(d, stream, d_x0, xt, eps, bla_unet_output(m), nullptr, t, B, F, d_terms + (size_t)i * B,
 		                                      d_sqerr ? d_sqerr + (size_t)i * B : nullptr)))
 			return st;

@@ -598,10 +598,11 @@ bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* d_x, con
 
 /* backward(), model/cifar_unet.c:1351-1436 (intended wiring, see the head of this file): fills the gradient bucket for the images, time
  * embeddings and dropout decisions of the last forward pass (summed over the images of a batch). */
-bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float* d_noise) {
+/* the pass behind both entries: seeded with 2 (output - d_noise) by unet_loss_grad_kernel, or (d_noise NULL) with the caller's d_del_y, which is only read */
+static bla_status unet_backward(bla_unet* m, void* stream, const float* d_noise, const float* d_del_y) {
 	bla_status st = require_ready();
 	if (st) return st;
-	BLA_REQUIRE(m && d_noise, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(m && (d_noise || d_del_y), BLA_ERR_INVALID, "null argument");
 	BLA_REQUIRE(m->last_x, BLA_ERR_INVALID, "bla_unet_forward_f32 has not run");
 	const bla_unet_config& c = m->cfg;
 	const int* D = c.dims; const int* H = m->H; const int* W = m->W;
@@ -659,10 +660,14 @@ bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float* d_noise
 	const size_t hw0 = (size_t)H[0] * W[0];
 	const size_t n0 = (size_t)D[0] * hw0, n1 = (size_t)D[1] * H[1] * W[1], n2 = (size_t)D[2] * H[2] * W[2], n3 = (size_t)D[3] * H[3] * W[3];
 	const int nout = (int)(c.in_channels * hw0 * B);
-	hipLaunchKernelGGL(unet_loss_grad_kernel, dim3(grid_of((size_t)nout)), dim3(256), 0, s, m->outc.out, d_noise, F(a), nout);   // :1353-1364
-	BLA_HIP(hipGetLastError());
+	const float* seed = d_del_y;   // the side lane reads it until the join below; the caller's buffer is never written
+	if (d_noise) {
+		hipLaunchKernelGGL(unet_loss_grad_kernel, dim3(grid_of((size_t)nout)), dim3(256), 0, s, m->outc.out, d_noise, F(a), nout);   // :1353-1364
+		BLA_HIP(hipGetLastError());
+		seed = a;
+	}
 	// output processing, :1367-1369: convolution, ReLU gate, group norm
-	TRY(conv(m->outc, a, m->out_relu, F(b)));
+	TRY(conv(m->outc, seed, m->out_relu, F(b)));
 	TRY(bla_group_norm_ddx_gated_batched_f32(stream, B, b, F(a), m->res[17].result, m->out_mu, m->out_sd, D[0], c.group_size, (int)hw0, m->out_relu, nullptr));
 	// fourth up-sampling stage, :1372-1374
 	TRY(res(17, a, m->res[16].result, F(b))); TRY(res(16, b, m->cat[3], F(a)));
@@ -707,6 +712,14 @@ bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float* d_noise
 	return BLA_OK;
 }
 #undef TRY
+
+bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float* d_noise) {
+	return unet_backward(m, stream, d_noise, nullptr);
+}
+
+bla_status bla_unet_backward_from_f32(bla_unet* m, void* stream, const float* d_del_y) {
+	return unet_backward(m, stream, nullptr, d_del_y);
+}
 
 /* d_dtemb [B][time_dim] = dL/dtemb for the loss of the last backward pass: every block's time projection W_k [time_dim][cout] applied to the per-image
  * channel sums it left behind, summed over the 18 blocks -- one launch, nothing of the backward pass re-run or changed */

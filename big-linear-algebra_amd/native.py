@@ -174,6 +174,15 @@ SIGNATURES = {
     "bla_diffusion_vlb_weights": (_I, [_VP, _I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bla_diffusion_eval_timesteps": (_I, [_VP, _I, _VP]),
     "bla_unet_evaluate_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _U64, _U64, _VP, _I, _VP, _VP, _VP]),
+    "bla_diffusion_cosine_betas": (_I, [_I, C.c_double, C.c_double, _VP]),
+    "bla_diffusion_create_from_betas": (_I, [C.POINTER(_VP), _I, _VP]),
+    "bla_diffusion_set_objective": (_I, [_VP, _I, C.c_double]),
+    "bla_diffusion_objective": (_I, [_VP, C.POINTER(_I), C.POINTER(C.c_double)]),
+    "bla_diffusion_loss_weight": (_I, [_VP, _I, C.POINTER(C.c_double)]),
+    "bla_diffusion_target_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _SZ, _VP, _VP]),
+    "bla_diffusion_to_eps_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _SZ]),
+    "bla_diffusion_loss_f32": (_I, [_VP, _VP, _VP, _VP, _I, _SZ, _VP, _VP]),
+    "bla_unet_backward_from_f32": (_I, [_VP, _VP, _VP]),
 }
 
 

@@ -111,6 +111,21 @@
  *                                                      the evaluation file (default one batch; uploaded once), seed BLA_SEED, a fixed K; prints
  *                                                      `Held-out bits/dim: <total>` behind the pass's loss line.  Without it `fit` is unchanged.
  *
+ *   (not in the reference)                             Training objectives beyond Ho et al. 2020, all opt-in.  `fit` with BLA_UNET_SCHEDULE=linear|cosine
+ *                                                      (cosine: Nichol & Dhariwal 2021, bla_diffusion_cosine_betas(T, 0.008, 0.999)),
+ *                                                      BLA_UNET_PREDICT=eps|x0|v (what the network predicts; v: Salimans & Ho 2022) and
+ *                                                      BLA_UNET_MIN_SNR=<gamma> (Min-SNR-gamma loss weights, Hang et al. 2023; 0: none).  With any
+ *                                                      of the three set the pass is noise, bla_diffusion_target_f32, forward,
+ *                                                      bla_diffusion_loss_f32 (the gradient and the per-image losses), bla_unet_backward_from_f32
+ *                                                      and the usual clip / Adam / EMA tail; the printed loss is the mean weighted loss; and fit
+ *                                                      writes the line `schedule=... predict=... min_snr=...` to <weights>/objective.txt (and to
+ *                                                      ema/objective.txt beside the averaged set).  `sample` and `eval` (and `fit` with
+ *                                                      BLA_UNET_RESUME=1) read that file, build the diffusion object from it and call
+ *                                                      bla_diffusion_set_objective; an option in the environment that contradicts the file, or a
+ *                                                      malformed value, stops the program with status 1 before the device is opened.  A fit
+ *                                                      without an objective removes an objective.txt that an earlier fit left beside a set it
+ *                                                      overwrites.  With no option and no file every verb does exactly what it did before.
+ *
  * BLA_UNET_DUMP=<dir> makes train write what it uploaded (params, x, time embedding, noise, dropout decisions) and what came back (prediction,
  * gradient bucket) as raw little-endian files; tests/test_c_unet.py compares those with the oracle.
  *
@@ -656,6 +671,103 @@ static long env_eval_every(void) {
 	if (*end || errno || n < 1) { fprintf(stderr, "fit: BLA_UNET_EVAL_EVERY=%s; the evaluation runs every whole number of passes >= 1\n", v); exit(1); }
 	return n;
 }
+/* ---- the training objective: BLA_UNET_SCHEDULE, BLA_UNET_PREDICT, BLA_UNET_MIN_SNR and <weights>/objective.txt (see the head of this file) --------- */
+typedef struct Objective {
+	int active;              /* an option is set or the file exists: fit takes the objective pass and writes the file */
+	int cosine, predict;     /* predict: BLA_PREDICT_* */
+	double gamma;
+	char gamma_text[32];     /* gamma as it was given, for the file */
+} Objective;
+static int parse_schedule(const char* verb, const char* from, const char* v) {
+	if (strcmp(v, "linear") == 0) return 0;
+	if (strcmp(v, "cosine") == 0) return 1;
+	fprintf(stderr, "%s: %sBLA_UNET_SCHEDULE=%s; the schedules are linear and cosine\n", verb, from, v);
+	exit(1);
+}
+static int parse_predict(const char* verb, const char* from, const char* v) {
+	if (strcmp(v, "eps") == 0) return BLA_PREDICT_EPS;
+	if (strcmp(v, "x0") == 0) return BLA_PREDICT_X0;
+	if (strcmp(v, "v") == 0) return BLA_PREDICT_V;
+	fprintf(stderr, "%s: %sBLA_UNET_PREDICT=%s; the network predicts eps, x0 or v\n", verb, from, v);
+	exit(1);
+}
+static double parse_min_snr(const char* verb, const char* from, const char* v) {
+	char* end = NULL;
+	const double g = strtod(v, &end);
+	if (end == v || *end || !(g >= 0) || !isfinite(g) || strlen(v) >= sizeof ((Objective*)0)->gamma_text || v[0] == ' ' || v[0] == '\t' || v[0] == '\n') {
+		fprintf(stderr, "%s: %sBLA_UNET_MIN_SNR=%s; gamma is a finite number >= 0 (0: no weighting; e.g. 5)\n", verb, from, v);
+		exit(1);
+	}
+	return g;
+}
+static const char* schedule_name(int cosine) { return cosine ? "cosine" : "linear"; }
+static const char* predict_name(int predict) { return predict == BLA_PREDICT_V ? "v" : (predict == BLA_PREDICT_X0 ? "x0" : "eps"); }
+/* The options of the environment, checked; with use_file the line fit wrote to <weights>/objective.txt fills in what the environment leaves open, and an
+ * option that contradicts it stops the program.  Nothing here needs the device. */
+static Objective resolve_objective(const char* verb, int use_file) {
+	Objective o; memset(&o, 0, sizeof o);
+	strcpy(o.gamma_text, "0");
+	const char *se = getenv("BLA_UNET_SCHEDULE"), *pe = getenv("BLA_UNET_PREDICT"), *ge = getenv("BLA_UNET_MIN_SNR");
+	if (se && !*se) se = NULL;
+	if (pe && !*pe) pe = NULL;
+	if (ge && !*ge) ge = NULL;
+	if (se) o.cosine = parse_schedule(verb, "", se);
+	if (pe) o.predict = parse_predict(verb, "", pe);
+	if (ge) { o.gamma = parse_min_snr(verb, "", ge); strcpy(o.gamma_text, ge); }
+	o.active = se || pe || ge;
+	char path[512];
+	data_path(path, sizeof path, "objective.txt");
+	FILE* f = use_file ? fopen(path, "r") : NULL;
+	if (!f) return o;
+	char sv[16], pv[16], gv[64], from[600];
+	const int got = fscanf(f, "schedule=%15s predict=%15s min_snr=%63s", sv, pv, gv);
+	fclose(f);
+	if (got != 3) { fprintf(stderr, "%s: %s does not hold the line `schedule=... predict=... min_snr=...` that fit writes\n", verb, path); exit(1); }
+	snprintf(from, sizeof from, "%s: ", path);
+	const int cosine = parse_schedule(verb, from, sv), predict = parse_predict(verb, from, pv);
+	const double gamma = parse_min_snr(verb, from, gv);
+	if ((se && cosine != o.cosine) || (pe && predict != o.predict) || (ge && gamma != o.gamma)) {
+		fprintf(stderr, "%s: the environment asks for schedule=%s predict=%s min_snr=%s, but the weights were trained with `schedule=%s predict=%s min_snr=%s` (%s)\n",
+		        verb, se ? se : "(unset)", pe ? pe : "(unset)", ge ? ge : "(unset)", sv, pv, gv, path);
+		exit(1);
+	}
+	o.cosine = cosine; o.predict = predict; o.gamma = gamma; strcpy(o.gamma_text, gv);
+	o.active = 1;
+	return o;
+}
+/* beside the parameter set just saved (data_path: the set below ema/ gets its own copy) */
+static void save_objective(const Objective* o) {
+	char path[512];
+	data_path(path, sizeof path, "objective.txt");
+	FILE* f = fopen(path, "w");
+	if (!f || fprintf(f, "schedule=%s predict=%s min_snr=%s\n", schedule_name(o->cosine), predict_name(o->predict), o->gamma_text) < 0 || fclose(f) != 0) {
+		fprintf(stderr, "cannot write %s\n", path);
+		exit(1);
+	}
+}
+/* a set saved by a fit without an objective is an eps model on the linear schedule: a file left beside it by an earlier fit into the same directory
+ * would make sample and eval read it as something else */
+static void remove_objective(void) {
+	char path[512];
+	data_path(path, sizeof path, "objective.txt");
+	if (remove(path) != 0 && errno != ENOENT) { fprintf(stderr, "cannot remove %s: %s\n", path, strerror(errno)); exit(1); }
+}
+/* the diffusion object of an objective: the linear betas 1e-4 .. 0.02 as ever, or the cosine betas (s = 0.008, capped at 0.999); set_objective only where
+ * an objective is in force, so that without one the object is the one this program has always made */
+static bla_diffusion* open_diffusion(const Objective* o, int T) {
+	bla_diffusion* diff;
+	if (o->cosine) {
+		double* betas = malloc((size_t)T * sizeof(double));
+		CHECK(bla_diffusion_cosine_betas(T, 0.008, 0.999, betas));
+		CHECK(bla_diffusion_create_from_betas(&diff, T, betas));
+		free(betas);
+	} else {
+		CHECK(bla_diffusion_create(&diff, T, 1e-4f, 0.02f));
+	}
+	if (o->active) CHECK(bla_diffusion_set_objective(diff, o->predict, o->gamma));
+	return diff;
+}
+
 /* exchanges the host tensors with another set of the same shapes */
 static void swap_sets(float** other) {
 	for (int t = 0; t < g_tensor_count; t++) { float* h = g_tensors[t].host; g_tensors[t].host = other[t]; other[t] = h; }
@@ -777,6 +889,8 @@ static void eval_close(Evaluator* ev) {
 /* `eval [<images>]`: the saved set (BLA_UNET_EVAL_EMA=1: the set below ema/) on the evaluation file's first <images> records (default all), the last partial
  * batch dropped; BLA_UNET_BATCH (default 64), BLA_UNET_EVAL_STEPS, BLA_UNET_CLASSES=1: every image with its own label's row, no label dropout */
 static void eval(const char* images_arg) {
+	if (env_flag("BLA_UNET_EVAL_EMA")) g_set = "ema";
+	const Objective obj = resolve_objective("eval", 1);
 	const int classes = env_flag("BLA_UNET_CLASSES"), T = env_steps(), K = env_eval_steps("eval", T);
 	const int batch = atoi(env_or("BLA_UNET_BATCH", "64"));
 	if (batch < 1) { fprintf(stderr, "eval: BLA_UNET_BATCH must be >= 1\n"); exit(1); }
@@ -792,7 +906,6 @@ static void eval(const char* images_arg) {
 	if (want > 0 && (size_t)want < records) records = (size_t)want;
 	const size_t images = records / batch * batch;
 	if (!images) { fprintf(stderr, "eval: %zu records, fewer than one batch of %d\n", records, batch); exit(1); }
-	if (env_flag("BLA_UNET_EVAL_EMA")) g_set = "ema";
 	float* table = NULL;
 	if (classes) {
 		table = malloc((size_t)(CLASSES + 1) * TIME_EMBED_DIM * sizeof(float));
@@ -808,8 +921,7 @@ static void eval(const char* images_arg) {
 	Inputs in = inputs_alloc(1);
 	Device dv = device_open(batch, in.drop_per_image);
 	device_set_params(&dv);
-	bla_diffusion* diff;
-	CHECK(bla_diffusion_create(&diff, T, 1e-4f, 0.02f));
+	bla_diffusion* diff = open_diffusion(&obj, T);
 	float* d_table = NULL;
 	if (classes) {
 		CHECK(bla_malloc((void**)&d_table, (size_t)(CLASSES + 1) * TIME_EMBED_DIM * sizeof(float)));
@@ -832,6 +944,7 @@ static void eval(const char* images_arg) {
 
 static void fit(int epochs, int batch) {
 	if (batch < 1 || epochs < 1) { fprintf(stderr, "fit: epochs and batch must be >= 1\n"); exit(1); }
+	const Objective obj = resolve_objective("fit", env_flag("BLA_UNET_RESUME"));
 	const double ema_decay = env_ema_decay();
 	const int shuffle = env_fit_flag("BLA_UNET_SHUFFLE"), flip = env_fit_flag("BLA_UNET_FLIP"), gather = shuffle || flip;
 	const double clip_norm = env_clip_norm();
@@ -881,8 +994,7 @@ static void fit(int epochs, int batch) {
 	Inputs in = inputs_alloc(1);                                                                /* only for the dropout layout */
 	Device dv = device_open(batch, in.drop_per_image);
 	device_set_params(&dv);
-	bla_diffusion* diff;
-	CHECK(bla_diffusion_create(&diff, env_steps(), 1e-4f, 0.02f));
+	bla_diffusion* diff = open_diffusion(&obj, env_steps());
 	/* a shuffled epoch draws from every record; otherwise the last partial batch is never seen and is not uploaded */
 	const size_t params = bla_unet_param_count(dv.net), drops = bla_unet_dropout_count(dv.net), used = shuffle ? records : per_epoch * batch;
 	float *d_data, *d_m, *d_v; int* d_t; double* d_loss;
@@ -902,6 +1014,17 @@ static void fit(int epochs, int batch) {
 			CHECK(bla_malloc((void**)&d_ema_table, table_floats * sizeof(float)));
 			CHECK(bla_memcpy_h2d(d_ema_table, ema_table, table_floats * sizeof(float), NULL));
 		}
+	}
+	/* an objective in force: the regression target, the seed of the backward pass, the per-image weights and losses (one row per pass between two logged
+	 * lines, summed on the host in order), and the assembled x0 batch where the noising launch gathers it */
+	float *d_target = NULL, *d_g = NULL, *d_weight = NULL, *d_x0 = NULL; double* d_losses = NULL; double* losses = NULL;
+	if (obj.active) {
+		CHECK(bla_malloc((void**)&d_target, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
+		CHECK(bla_malloc((void**)&d_g, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
+		CHECK(bla_malloc((void**)&d_weight, batch * sizeof(float)));
+		if (gather) CHECK(bla_malloc((void**)&d_x0, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
+		CHECK(bla_malloc((void**)&d_losses, (size_t)log_every * batch * sizeof(double)));
+		losses = malloc((size_t)log_every * batch * sizeof(double));
 	}
 	unsigned int *d_index = NULL, *d_keys = NULL;   /* BLA_UNET_SHUFFLE / BLA_UNET_FLIP: the epoch's record order (0, 1, 2, ... without shuffling) */
 	if (gather) {
@@ -948,12 +1071,14 @@ static void fit(int epochs, int batch) {
 	for (size_t pass = 0; pass < passes; pass++) {
 		const size_t k = pass % per_epoch;
 		const int* pass_labels = classes ? d_labels + k * batch : NULL;
+		const float* x0 = d_data + k * batch * IMAGE_FLOATS;   /* the pass's clean images (read only with an objective in force) */
 		if (gather) {   /* index, flips and labels inside the noising launch; a shuffled epoch starts with its permutation (Philox offsets: bla.h) */
 			if (shuffle && k == 0)
 				CHECK(bla_rand_permutation_u32(NULL, d_index, d_keys, records, seed, ((unsigned long long)(pass / per_epoch) << 32) + (1ull << 31)));
 			CHECK(bla_diffusion_noise_gather_f32(diff, NULL, d_data, used, d_index + k * batch, flip, IMAGE_SIDE, d_labels, d_batch_labels, batch, IMAGE_FLOATS,
-			                                     TIME_EMBED_DIM, seed, pass, d_t, dv.noise, dv.x, dv.temb, NULL));
+			                                     TIME_EMBED_DIM, seed, pass, d_t, dv.noise, dv.x, dv.temb, d_x0));
 			pass_labels = d_batch_labels;
+			x0 = d_x0;
 		} else {
 			CHECK(bla_diffusion_noise_f32(diff, NULL, d_data + k * batch * IMAGE_FLOATS, batch, IMAGE_FLOATS, TIME_EMBED_DIM, seed, pass, d_t, dv.noise, dv.x, dv.temb));
 		}
@@ -961,13 +1086,20 @@ static void fit(int epochs, int batch) {
 			CHECK(bla_class_embedding_f32(NULL, d_table, CLASSES, pass_labels, batch, TIME_EMBED_DIM, (float)p_uncond, seed,
 			                              ((unsigned long long)pass << 32) + (1ull << 31), d_rows, dv.temb));
 		CHECK(bla_rand_bernoulli_u8(NULL, dv.drop, drops, DROPOUT_RATE, seed, (unsigned long long)pass << 32));
-		CHECK(bla_unet_forward_f32(dv.net, NULL, dv.x, dv.temb, dv.drop));
-		CHECK(bla_unet_backward_f32(dv.net, NULL, dv.noise));
+		if (obj.active) {   /* target and weights of the objective, forward, the weighted loss with its gradient, backward from that gradient */
+			CHECK(bla_diffusion_target_f32(diff, NULL, x0, dv.noise, d_t, 0, batch, IMAGE_FLOATS, d_target, d_weight));
+			CHECK(bla_unet_forward_f32(dv.net, NULL, dv.x, dv.temb, dv.drop));
+			CHECK(bla_diffusion_loss_f32(NULL, bla_unet_output(dv.net), d_target, d_weight, batch, IMAGE_FLOATS, d_g, d_losses + (pass - logged) * batch));
+			CHECK(bla_unet_backward_from_f32(dv.net, NULL, d_g));
+		} else {
+			CHECK(bla_unet_forward_f32(dv.net, NULL, dv.x, dv.temb, dv.drop));
+			CHECK(bla_unet_backward_f32(dv.net, NULL, dv.noise));
+		}
 		if (classes) {
 			CHECK(bla_unet_embedding_grad_f32(dv.net, NULL, d_dtemb));
 			CHECK(bla_class_embedding_grad_f32(NULL, d_dtemb, d_rows, batch, CLASSES, TIME_EMBED_DIM, d_gtable));
 		}
-		CHECK(bla_mse_accumulate_f32(NULL, bla_unet_output(dv.net), dv.noise, (size_t)batch * IMAGE_FLOATS, d_loss));
+		if (!obj.active) CHECK(bla_mse_accumulate_f32(NULL, bla_unet_output(dv.net), dv.noise, (size_t)batch * IMAGE_FLOATS, d_loss));
 		const float pass_lr = warmup ? (float)(lr * fmin(1.0, (double)(pass + 1) / (double)warmup)) : (float)lr;
 		if (clip_norm > 0) {   /* the global norm of the mean gradient over both buckets, the clipping coefficient and Adam's grad_scale all stay on the device */
 			CHECK(bla_memset(d_sumsq, 0, sizeof(double), NULL));
@@ -990,10 +1122,12 @@ static void fit(int epochs, int batch) {
 		if ((pass + 1) % log_every == 0 || pass + 1 == passes) {
 			double sum = 0;
 			float norm = 0;
-			CHECK(bla_memcpy_d2h(&sum, d_loss, sizeof sum, NULL));
+			if (obj.active) CHECK(bla_memcpy_d2h(losses, d_losses, (pass + 1 - logged) * batch * sizeof(double), NULL));
+			else CHECK(bla_memcpy_d2h(&sum, d_loss, sizeof sum, NULL));
 			if (clip_norm > 0) CHECK(bla_memcpy_d2h(&norm, d_norm, sizeof norm, NULL));
 			CHECK(bla_memset(d_loss, 0, sizeof(double), NULL));
 			CHECK(bla_stream_sync(NULL));
+			if (obj.active) for (size_t i = 0; i < (pass + 1 - logged) * batch; i++) sum += losses[i];   /* the mean weighted loss */
 			printf("Pass %zu:\tAvg loss: %f\n", pass, sum / ((double)(pass + 1 - logged) * batch * IMAGE_FLOATS));
 			if (clip_norm > 0) printf("Grad norm: %f\n", norm);
 			fflush(stdout);
@@ -1007,11 +1141,13 @@ static void fit(int epochs, int batch) {
 	if (eval_every) eval_close(&ev);
 	device_get_params(&dv);
 	save_parameters();
+	if (obj.active) save_objective(&obj); else remove_objective();
 	if (ema_decay > 0) {   /* the average as a second complete set below ema/: tensors the device model does not use keep the values just written */
 		CHECK(bla_memcpy_d2d(bla_unet_params(dv.net), d_ema, params * sizeof(float), NULL));
 		device_get_params(&dv);
 		g_set = "ema";
 		save_parameters();
+		if (obj.active) save_objective(&obj); else remove_objective();
 		if (classes) {
 			CHECK(bla_memcpy_d2h(ema_table, d_ema_table, table_floats * sizeof(float), NULL));
 			CHECK(bla_stream_sync(NULL));
@@ -1033,6 +1169,7 @@ static void fit(int epochs, int batch) {
 	}
 	if (gather) { CHECK(bla_free(d_index)); CHECK(bla_free(d_keys)); }
 	if (clip_norm > 0) { CHECK(bla_free(d_sumsq)); CHECK(bla_free(d_partials)); CHECK(bla_free(d_scale)); CHECK(bla_free(d_norm)); }
+	if (obj.active) { CHECK(bla_free(d_target)); CHECK(bla_free(d_g)); CHECK(bla_free(d_weight)); CHECK(bla_free(d_x0)); CHECK(bla_free(d_losses)); free(losses); }
 	CHECK(bla_free(d_data)); CHECK(bla_free(d_m)); CHECK(bla_free(d_v)); CHECK(bla_free(d_t)); CHECK(bla_free(d_loss));
 	CHECK(bla_diffusion_destroy(diff));
 	inputs_free(&in); device_close(&dv);
@@ -1042,6 +1179,7 @@ static void sample(int count, const char* dir) {
 	int batch = atoi(env_or("BLA_UNET_BATCH", "16"));
 	if (batch > count) batch = count;
 	if (batch < 1) return;
+	const Objective obj = resolve_objective("sample", 1);
 	/* BLA_UNET_SAMPLE_STEPS=S: DDIM with S steps, BLA_UNET_ETA, BLA_UNET_CLIP; checked before the device is opened */
 	const char* steps_env = getenv("BLA_UNET_SAMPLE_STEPS");
 	const int ddim = steps_env && *steps_env;
@@ -1095,8 +1233,7 @@ static void sample(int count, const char* dir) {
 	Inputs in = inputs_alloc(1);
 	Device dv = device_open(guided ? 2 * batch : batch, in.drop_per_image);   /* guided: n conditioned images + their n null-class copies */
 	device_set_params(&dv);
-	bla_diffusion* diff;
-	CHECK(bla_diffusion_create(&diff, env_steps(), 1e-4f, 0.02f));
+	bla_diffusion* diff = open_diffusion(&obj, env_steps());
 	float* d_table = NULL; int* d_labels = NULL;
 	if (guided) {
 		int* lab = malloc(batch * sizeof(int));

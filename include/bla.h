@@ -447,6 +447,11 @@ BLA_API bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* 
                                         const unsigned char* d_drop);
 /* del_Y = 2 (prediction - noise) (:1353-1364), then every block backwards; uses the activations of the last forward pass */
 BLA_API bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float* d_noise /* [C][H][W] */);
+/* The same pass seeded with the caller's gradient of the loss with respect to the output instead of 2 (prediction - noise): d_del_y has the output's
+ * layout ([B][C][H][W] on a batched model) and is only read (it must stay as it is until the stream has passed this call).  With d_del_y =
+ * 2 (output - noise) in fp32 the gradient bucket is bla_unet_backward_f32's, bit for bit.  Refused like it: a NULL argument, or no forward pass so far.
+ * bla_unet_embedding_grad_f32 works behind either. */
+BLA_API bla_status bla_unet_backward_from_f32(bla_unet* m, void* stream, const float* d_del_y);
 
 /* ---- training the U-Net as a diffusion model (DDPM, Ho et al. 2020) and drawing images from it ----------------------------------------------
  * Not in the reference: its train() allocates Adam's two moment sets and never uses them (:1887-1888), never noises an image at a timestep, never
@@ -714,6 +719,56 @@ BLA_API bla_status bla_diffusion_eval_timesteps(const bla_diffusion* d, int K, i
 BLA_API bla_status bla_unet_evaluate_f32(bla_unet* m, const bla_diffusion* d, void* stream, const float* d_x0, const int* timesteps, int count,
                                          unsigned long long seed, unsigned long long offset_base, const float* d_table, int classes, const int* d_rows,
                                          double* d_terms, double* d_sqerr);
+
+/* ---- training objectives: the schedule, what the network predicts, how a timestep's loss is weighted ---------------------------------------
+ * Not in the reference.  Everything above is Ho et al. 2020: linear betas, the output read as eps_hat, every timestep at weight 1.  The entries below add
+ * the cosine schedule (Nichol & Dhariwal 2021), v- and x0-prediction (Salimans & Ho 2022) and Min-SNR-gamma weighting (Hang et al. 2023).  A diffusion
+ * object that none of them touched behaves exactly as before.
+ *
+ * The cosine betas, host only (no device needed): f(i) = cos^2(((i / steps) + s) / (1 + s) pi / 2), out[i] = min(1 - f(i + 1) / f(i), max_beta) for
+ * i = 0 .. steps-1, in double.  The published values are s = 0.008 and max_beta = 0.999.  steps < 1, s < 0 or not finite, max_beta outside (0, 1):
+ * BLA_ERR_INVALID. */
+BLA_API bla_status bla_diffusion_cosine_betas(int steps, double s, double max_beta, double* out /* [steps] */);
+/* A diffusion object over any betas: alpha_bar_t = prod_{s <= t} (1 - beta_s) in double, then the same fp32 tables and variational-bound weights through the
+ * same code as bla_diffusion_create (whose betas, handed to this entry, give the same object bit for bit).  No kernel assumes a linear schedule: all read
+ * the tables or the doubles of bla_diffusion_schedule.  A beta outside (0, 1) or NaN, steps outside [1, 2^24]: BLA_ERR_INVALID. */
+BLA_API bla_status bla_diffusion_create_from_betas(bla_diffusion** out, int steps, const double* betas /* [steps], host */);
+/* The objective the object carries.  `prediction` says what the network's output is, with a = sqrt(abar_t), c = sqrt(1 - abar_t):
+ *   BLA_PREDICT_EPS  the noise eps (the default);     BLA_PREDICT_X0  the image x0;     BLA_PREDICT_V  v = a eps - c x0.
+ * min_snr_gamma = 0: every timestep weighs 1.  gamma > 0: with SNR_t = abar_t / (1 - abar_t) and m = min(SNR_t, gamma) the weight of timestep t is
+ *   EPS: m / SNR_t (1 where abar_t has underflown to 0, the limit);     X0: m;     V: m / (SNR_t + 1)
+ * -- one weighting of the x0 error expressed in each parametrisation: the three weighted losses of one prediction are equal.  The table w [steps] is
+ * formed in double on the host, rounded to fp32 once and uploaded: this entry may allocate and waits for the device, so it is not for use inside a
+ * capture.  Every sampling loop and bla_unet_evaluate_f32 convert the output to eps_hat by bla_diffusion_to_eps_f32 right behind the forward pass when the
+ * prediction is not EPS (with EPS nothing is launched: their bits are unchanged).  The step kernels always take eps_hat.  Going through eps_hat
+ * amplifies the output's fp32 rounding by sqrt(abar_prev) / sqrt(abar_t) where the SNR is near zero.
+ * A prediction other than the three, gamma negative, infinite or NaN: BLA_ERR_INVALID, nothing changed.  A fresh object: EPS, gamma 0. */
+enum { BLA_PREDICT_EPS = 0, BLA_PREDICT_X0 = 1, BLA_PREDICT_V = 2 };
+BLA_API bla_status bla_diffusion_set_objective(bla_diffusion* d, int prediction, double min_snr_gamma);
+BLA_API bla_status bla_diffusion_objective(const bla_diffusion* d, int* prediction, double* min_snr_gamma);   /* either pointer may be NULL */
+BLA_API bla_status bla_diffusion_loss_weight(const bla_diffusion* d, int t, double* w);   /* the host double of w_t; t outside [0, steps): BLA_ERR_INVALID */
+/* The regression target of d's prediction type, one launch: d_target [batch][image_floats] = eps (EPS), x0 (X0: both bit-equal copies) or
+ * fmaf(a, eps, -(c x0)) (V) with a, c the fp32 table values of each image's timestep, and d_weight [batch] (may be NULL) = the fp32 w of that timestep.
+ * Timesteps as for bla_diffusion_noise_at_f32: d_t [batch] on the device, NULL = every image at t_const (outside [0, steps): BLA_ERR_INVALID); an image
+ * whose device-side t lies outside [0, steps) gets a zero target and weight 0.  Only the inputs the type reads are looked at (d_x0 may be NULL for EPS,
+ * d_eps for X0).  16-byte loads and stores when the pointers read and d_target are 16-byte aligned (a tail of batch * image_floats % 4 elements one by
+ * one; image_floats need not be a multiple of 4), one element per lane otherwise. */
+BLA_API bla_status bla_diffusion_target_f32(const bla_diffusion* d, void* stream, const float* d_x0, const float* d_eps, const int* d_t /* may be NULL */,
+                                            int t_const, int batch, size_t image_floats, float* d_target, float* d_weight /* [batch], may be NULL */);
+/* The model's output turned into eps_hat in place, given the x_t the model saw (d_x, not written; it must not overlap d_pred):
+ *   V:  eps_hat = fmaf(a, v, c x);      X0:  eps_hat = fmaf(-a, x0_hat, x) / c, a correctly rounded division by the table's c (no reciprocal);
+ *   EPS: BLA_OK without a launch.
+ * Timesteps, alignment rule and arguments refused as for bla_diffusion_target_f32; an image whose device-side t lies outside [0, steps) is left as it is. */
+BLA_API bla_status bla_diffusion_to_eps_f32(const bla_diffusion* d, void* stream, float* d_pred, const float* d_x, const int* d_t /* may be NULL */, int t_const,
+                                            int batch, size_t image_floats);
+/* The weighted squared error and its gradient, one launch, one workgroup per image (batch <= 2^31 - 1 workgroups):
+ *   d_g [batch][image_floats] (may be NULL) = (2 w_b) (out - target) in fp32: 2 w_b is exact, the difference is rounded once and the product once.
+ *   d_loss [batch] (may be NULL)           = w_b sum_i ((double)out_i - (double)target_i)^2, summed in double in a fixed order: bit-reproducible.
+ * d_weight [batch] on the device, NULL = 1: then d_g is 2 (out - target), what bla_unet_backward_f32 seeds its pass with, bit for bit.  Hand d_g to
+ * bla_unet_backward_from_f32.  16-byte accesses when image_floats % 4 == 0 and d_out, d_target, d_g are 16-byte aligned.  Both outputs NULL: nothing
+ * is launched. */
+BLA_API bla_status bla_diffusion_loss_f32(void* stream, const float* d_out, const float* d_target, const float* d_weight /* [batch], may be NULL */, int batch,
+                                          size_t image_floats, float* d_g, double* d_loss);
 
 /* ---- device-resident MNIST-NN trainer: the hot loop of model/mnist_nn.c:218-315 with everything in HBM -------
  * sizes = {n0, n1, n2, n3} (784, 256, 128, 10 in the reference, model/mnist_nn.c:25-28); samples are columns.
