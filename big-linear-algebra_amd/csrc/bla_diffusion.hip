@@ -1,6 +1,7 @@
 // bla_diffusion.hip -- what turns the U-Net of model/cifar_unet.c into a DDPM (Ho, Jain, Abbeel 2020): the linear beta schedule, the forward noising
-// of a training batch, the sinusoidal time embedding, the ancestral sampler step and the sampling loop around bla_unet_forward_f32, and the held-out
-// evaluation of the trained model (the variational bound, per image).
+// of a training batch, the sinusoidal time embedding, the samplers (ancestral, DDIM, DPM-Solver++(2M), each unguided and classifier-free guided) around
+// bla_unet_forward_f32, and the held-out evaluation of the trained model (the variational bound, per image).  The six samplers share one walk over the timesteps
+// (sample_loop), the guided ones one set-up (guided_start); a new sampler adds a step kernel with its bla_diffusion_*_step_f32 and a choice of timesteps.
 //
 // The reference has the network (time embedding input, noise prediction, MSE against the noise) but never writes the embedding (:535), never noises
 // an image at a timestep and leaves run() empty (:1936).  Random draws come from the Philox streams of bla_philox.h (see include/bla.h), so every
@@ -34,7 +35,7 @@ struct bla_diffusion {
 	float* xg = nullptr;           // the guided sampler's model input [2n][C][H][W] and class rows [2n] (grow on first use)
 	size_t xg_floats = 0;
 	int* rows = nullptr;
-	int rows_count = 0;
+	size_t rows_count = 0;
 	float* hist = nullptr;         // the DPM-Solver++ samplers' previous x0 prediction, [B][C][H][W] (grows on first use)
 	size_t hist_floats = 0;
 	double* vlb = nullptr;         // device, 2 x steps: c_t, w_t of bla_diffusion_vlb_weights (0 at t = 0)
@@ -160,64 +161,65 @@ __global__ void __launch_bounds__(kThreads) noise_kernel(const float* __restrict
 	}
 }
 
-__global__ void __launch_bounds__(kThreads) step_kernel(float* __restrict__ x, const float* __restrict__ eps_hat, size_t n, int t, int steps, unsigned long long seed,
-                                                        const float* __restrict__ table, int batch, int dim, float* __restrict__ temb_next, int vec) {
-	const float k = table[TAB_EPS_COEF * steps + t], inv = table[TAB_INV_SQRT_A * steps + t], sig = table[TAB_SIGMA * steps + t];
-	const unsigned long long offset = (unsigned long long)(t + 1) << 32;
-	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-	if (temb_next && t > 0) {
-		const size_t ne = (size_t)batch * dim;
-		for (size_t i = tid; i < ne; i += stride) temb_next[i] = temb_value(t - 1, (int)(i % dim), dim);
-	}
-	const size_t n4 = vec ? n / 4 : 0;
-	for (size_t q = tid; q < n4; q += stride) {
-		const float4 z = t > 0 ? philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL)) : make_float4(0.f, 0.f, 0.f, 0.f);
-		const float4 e = reinterpret_cast<const float4*>(eps_hat)[q];
-		float4 v = reinterpret_cast<float4*>(x)[q];
-		v.x = (v.x - k * e.x) * inv + sig * z.x; v.y = (v.y - k * e.y) * inv + sig * z.y;
-		v.z = (v.z - k * e.z) * inv + sig * z.z; v.w = (v.w - k * e.w) * inv + sig * z.w;
-		reinterpret_cast<float4*>(x)[q] = v;
-	}
-	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
-		const float z = t > 0 ? normal_at(seed, offset, i) : 0.f;
-		x[i] = (x[i] - k * eps_hat[i]) * inv + sig * z;
+// What the three step kernels below share.  A GUIDED instance serves the classifier-free guided samplers (Ho & Salimans 2022): the model ran on [2 batch] images, the
+// conditioned ones and their null-class copies, eps_c and eps_u are the halves of its output, and x_copy (may be NULL) receives the new x too: the second half of the
+// model's next input.  An unguided instance reads eps_u as eps_hat and looks at none of x_copy, eps_c, s, ctable, classes and rows.
+
+// temb_next [(GUIDED ? 2 : 1) batch][dim] = the embedding of t, plus ctable[rows[b]] when GUIDED (nothing added where ctable is NULL or a row is outside [0, classes])
+template <bool GUIDED>
+__device__ __forceinline__ void next_embedding(float* __restrict__ temb_next, int t, int batch, int dim, const float* __restrict__ ctable, int classes,
+                                               const int* __restrict__ rows, size_t tid, size_t stride) {
+	const size_t ne = (size_t)(GUIDED ? 2 : 1) * batch * dim;
+	for (size_t i = tid; i < ne; i += stride) {
+		const float e = temb_value(t, (int)(i % dim), dim);
+		const int r = GUIDED && ctable ? rows[i / dim] : -1;
+		temb_next[i] = r >= 0 && r <= classes ? e + ctable[(size_t)r * dim + i % dim] : e;
 	}
 }
 
-// the classifier-free guided step (Ho & Salimans 2022): eps~ = eps_u + s (eps_c - eps_u), then step_kernel's update word for word (the same z stream; at s = 0
-// eps~ is eps_u bit for bit, and so is the result).  x_copy (may be NULL) receives the new x too: the second, null-class half of the model's input.
-// temb_next [2 batch][dim] (may be NULL): the embedding of t - 1 plus table[rows[b]] (nothing added where table is NULL or a row is outside [0, classes])
-__global__ void __launch_bounds__(kThreads) guided_step_kernel(float* __restrict__ x, float* __restrict__ x_copy, const float* __restrict__ eps_c,
-                                                               const float* __restrict__ eps_u, float s, size_t n, int t, int steps, unsigned long long seed,
-                                                               const float* __restrict__ table, int batch, int dim, float* __restrict__ temb_next,
-                                                               const float* __restrict__ ctable, int classes, const int* __restrict__ rows, int vec) {
+// eps~ = eps_u + s (eps_c - eps_u) in one explicit fmaf: at s = 0 it is eps_u bit for bit, and so is every guided step its unguided one
+__device__ __forceinline__ float guided_mix(float s, float c, float u) { return fmaf(s, c - u, u); }
+
+template <bool GUIDED>
+__device__ __forceinline__ float eps_at(const float* __restrict__ eps_c, const float* __restrict__ eps_u, float s, size_t i) {
+	return GUIDED ? guided_mix(s, eps_c[i], eps_u[i]) : eps_u[i];
+}
+template <bool GUIDED>
+__device__ __forceinline__ float4 eps4_at(const float* __restrict__ eps_c, const float* __restrict__ eps_u, float s, size_t q) {
+	float4 e = reinterpret_cast<const float4*>(eps_u)[q];
+	if constexpr (GUIDED) {
+		const float4 c = reinterpret_cast<const float4*>(eps_c)[q];
+		e = make_float4(guided_mix(s, c.x, e.x), guided_mix(s, c.y, e.y), guided_mix(s, c.z, e.z), guided_mix(s, c.w, e.w));
+	}
+	return e;
+}
+
+// One ancestral step at t in place: x <- (x - k eps) inv + sig z with z from the stream (seed, (t + 1) << 32), 0 at t = 0.  temb_next (may be NULL) receives the
+// embedding of t - 1, nothing at t = 0.
+template <bool GUIDED>
+__global__ void __launch_bounds__(kThreads) step_kernel(float* __restrict__ x, float* __restrict__ x_copy, const float* __restrict__ eps_c,
+                                                        const float* __restrict__ eps_u, float s, size_t n, int t, int steps, unsigned long long seed,
+                                                        const float* __restrict__ table, int batch, int dim, float* __restrict__ temb_next,
+                                                        const float* __restrict__ ctable, int classes, const int* __restrict__ rows, int vec) {
 	const float k = table[TAB_EPS_COEF * steps + t], inv = table[TAB_INV_SQRT_A * steps + t], sig = table[TAB_SIGMA * steps + t];
 	const unsigned long long offset = (unsigned long long)(t + 1) << 32;
 	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-	if (temb_next && t > 0) {
-		const size_t ne = (size_t)2 * batch * dim;
-		for (size_t i = tid; i < ne; i += stride) {
-			const float e = temb_value(t - 1, (int)(i % dim), dim);
-			const int r = ctable ? rows[i / dim] : -1;
-			temb_next[i] = r >= 0 && r <= classes ? e + ctable[(size_t)r * dim + i % dim] : e;
-		}
-	}
+	if (temb_next && t > 0) next_embedding<GUIDED>(temb_next, t - 1, batch, dim, ctable, classes, rows, tid, stride);
 	const size_t n4 = vec ? n / 4 : 0;
 	for (size_t q = tid; q < n4; q += stride) {
 		const float4 z = t > 0 ? philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL)) : make_float4(0.f, 0.f, 0.f, 0.f);
-		const float4 c = reinterpret_cast<const float4*>(eps_c)[q], u = reinterpret_cast<const float4*>(eps_u)[q];
-		const float4 e = make_float4(fmaf(s, c.x - u.x, u.x), fmaf(s, c.y - u.y, u.y), fmaf(s, c.z - u.z, u.z), fmaf(s, c.w - u.w, u.w));
+		const float4 e = eps4_at<GUIDED>(eps_c, eps_u, s, q);
 		float4 v = reinterpret_cast<float4*>(x)[q];
 		v.x = (v.x - k * e.x) * inv + sig * z.x; v.y = (v.y - k * e.y) * inv + sig * z.y;
 		v.z = (v.z - k * e.z) * inv + sig * z.z; v.w = (v.w - k * e.w) * inv + sig * z.w;
 		reinterpret_cast<float4*>(x)[q] = v;
-		if (x_copy) reinterpret_cast<float4*>(x_copy)[q] = v;
+		if (GUIDED && x_copy) reinterpret_cast<float4*>(x_copy)[q] = v;
 	}
 	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
 		const float z = t > 0 ? normal_at(seed, offset, i) : 0.f;
-		const float e = fmaf(s, eps_c[i] - eps_u[i], eps_u[i]);
+		const float e = eps_at<GUIDED>(eps_c, eps_u, s, i);
 		x[i] = (x[i] - k * e) * inv + sig * z;
-		if (x_copy) x_copy[i] = x[i];
+		if (GUIDED && x_copy) x_copy[i] = x[i];
 	}
 }
 
@@ -437,9 +439,7 @@ __device__ __forceinline__ float ddim1(float x, float e, float z, const DdimArgs
 	return fmaf(a.sab_prev, x0, fmaf(a.dir, e, a.sigma * z));
 }
 
-// One DDIM step from t to t_prev in place.  GUIDED = false: eps_u is eps_hat.  GUIDED = true: eps~ = eps_u + s (eps_c - eps_u) by guided_step_kernel's
-// single fmaf (at s = 0 eps~ is eps_u bit for bit, and so is the step), x_copy (may be NULL) receives the new x, temb_next is [2 batch][dim] with the
-// class rows added as guided_step_kernel adds them.  z is step_kernel's stream (seed, (t + 1) << 32), drawn only when sigma > 0; temb_next (may be
+// One DDIM step from t to t_prev in place; step_kernel's structure.  z is step_kernel's stream (seed, (t + 1) << 32), drawn only when sigma > 0; temb_next (may be
 // NULL) receives the embedding of t_prev, nothing at t_prev = -1.
 template <bool GUIDED>
 __global__ void __launch_bounds__(kThreads) ddim_step_kernel(float* __restrict__ x, float* __restrict__ x_copy, const float* __restrict__ eps_c,
@@ -449,22 +449,11 @@ __global__ void __launch_bounds__(kThreads) ddim_step_kernel(float* __restrict__
 	const unsigned long long offset = (unsigned long long)(t + 1) << 32;
 	const bool noise = a.sigma > 0.f;
 	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-	if (temb_next && t_prev >= 0) {
-		const size_t ne = (size_t)(GUIDED ? 2 : 1) * batch * dim;
-		for (size_t i = tid; i < ne; i += stride) {
-			const float e = temb_value(t_prev, (int)(i % dim), dim);
-			const int r = GUIDED && ctable ? rows[i / dim] : -1;
-			temb_next[i] = r >= 0 && r <= classes ? e + ctable[(size_t)r * dim + i % dim] : e;
-		}
-	}
+	if (temb_next && t_prev >= 0) next_embedding<GUIDED>(temb_next, t_prev, batch, dim, ctable, classes, rows, tid, stride);
 	const size_t n4 = vec ? n / 4 : 0;
 	for (size_t q = tid; q < n4; q += stride) {
 		const float4 z = noise ? philox_normal4(philox_block(seed, offset + q, PHILOX_TAG_NORMAL)) : make_float4(0.f, 0.f, 0.f, 0.f);
-		float4 e = reinterpret_cast<const float4*>(eps_u)[q];
-		if constexpr (GUIDED) {
-			const float4 c = reinterpret_cast<const float4*>(eps_c)[q];
-			e = make_float4(fmaf(s, c.x - e.x, e.x), fmaf(s, c.y - e.y, e.y), fmaf(s, c.z - e.z, e.z), fmaf(s, c.w - e.w, e.w));
-		}
+		const float4 e = eps4_at<GUIDED>(eps_c, eps_u, s, q);
 		float4 v = reinterpret_cast<float4*>(x)[q];
 		v = make_float4(ddim1(v.x, e.x, z.x, a), ddim1(v.y, e.y, z.y, a), ddim1(v.z, e.z, z.z, a), ddim1(v.w, e.w, z.w, a));
 		reinterpret_cast<float4*>(x)[q] = v;
@@ -472,7 +461,7 @@ __global__ void __launch_bounds__(kThreads) ddim_step_kernel(float* __restrict__
 	}
 	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
 		const float z = noise ? normal_at(seed, offset, i) : 0.f;
-		const float e = GUIDED ? fmaf(s, eps_c[i] - eps_u[i], eps_u[i]) : eps_u[i];
+		const float e = eps_at<GUIDED>(eps_c, eps_u, s, i);
 		const float v = ddim1(x[i], e, z, a);
 		x[i] = v;
 		if (GUIDED && x_copy) x_copy[i] = v;
@@ -493,31 +482,15 @@ std::vector<int> ddim_timesteps(int T, int S) {
 	return ts;
 }
 
-// the samplers' workspaces of the diffusion object (scratch, not part of the schedule), grown to at least the sizes given; waits for the stream when
-// it has to grow one, so the first call is not capturable
-bla_status grow_workspaces(bla_diffusion* dm, hipStream_t s, size_t temb_floats, size_t xg_floats, int rows, size_t hist_floats = 0) {
-	if (dm->temb_floats >= temb_floats && dm->xg_floats >= xg_floats && dm->rows_count >= rows && dm->hist_floats >= hist_floats) return BLA_OK;
+// One scratch buffer of the diffusion object grown to at least `count` elements (what it held is lost).  It waits for the stream only when it has to grow, so a
+// first call is not capturable and a second with the same shapes neither waits nor allocates.
+template <typename T>
+bla_status grow(hipStream_t s, T** buf, size_t* have, size_t count) {
+	if (*have >= count) return BLA_OK;
 	BLA_HIP(hipStreamSynchronize(s));
-	if (dm->temb_floats < temb_floats) {
-		(void)hipFree(dm->temb); dm->temb = nullptr; dm->temb_floats = 0;
-		BLA_HIP(hipMalloc((void**)&dm->temb, temb_floats * sizeof(float)));
-		dm->temb_floats = temb_floats;
-	}
-	if (dm->xg_floats < xg_floats) {
-		(void)hipFree(dm->xg); dm->xg = nullptr; dm->xg_floats = 0;
-		BLA_HIP(hipMalloc((void**)&dm->xg, xg_floats * sizeof(float)));
-		dm->xg_floats = xg_floats;
-	}
-	if (dm->rows_count < rows) {
-		(void)hipFree(dm->rows); dm->rows = nullptr; dm->rows_count = 0;
-		BLA_HIP(hipMalloc((void**)&dm->rows, (size_t)rows * sizeof(int)));
-		dm->rows_count = rows;
-	}
-	if (dm->hist_floats < hist_floats) {
-		(void)hipFree(dm->hist); dm->hist = nullptr; dm->hist_floats = 0;
-		BLA_HIP(hipMalloc((void**)&dm->hist, hist_floats * sizeof(float)));
-		dm->hist_floats = hist_floats;
-	}
+	(void)hipFree(*buf); *buf = nullptr; *have = 0;
+	BLA_HIP(hipMalloc((void**)buf, count * sizeof(T)));
+	*have = count;
 	return BLA_OK;
 }
 
@@ -602,7 +575,7 @@ __device__ __forceinline__ float dpmpp1(float x, float e, float hist, const Dpmp
 	return fmaf(a.c_x, x, a.c_d * D);
 }
 
-// One DPM-Solver++(2M) step from t to t_prev in place; ddim_step_kernel's structure (the GUIDED mix, x_copy, temb_next and the class rows are its).
+// One DPM-Solver++(2M) step from t to t_prev in place; step_kernel's structure.
 // hist [n] holds the previous step's x0 prediction: read only when a.second, always written with this step's.  No noise.
 template <bool GUIDED>
 __global__ void __launch_bounds__(kThreads) dpmpp_step_kernel(float* __restrict__ x, float* __restrict__ x_copy, const float* __restrict__ eps_c,
@@ -610,21 +583,10 @@ __global__ void __launch_bounds__(kThreads) dpmpp_step_kernel(float* __restrict_
                                                               int t_prev, int batch, int dim, float* __restrict__ temb_next,
                                                               const float* __restrict__ ctable, int classes, const int* __restrict__ rows, int vec) {
 	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-	if (temb_next && t_prev >= 0) {
-		const size_t ne = (size_t)(GUIDED ? 2 : 1) * batch * dim;
-		for (size_t i = tid; i < ne; i += stride) {
-			const float e = temb_value(t_prev, (int)(i % dim), dim);
-			const int r = GUIDED && ctable ? rows[i / dim] : -1;
-			temb_next[i] = r >= 0 && r <= classes ? e + ctable[(size_t)r * dim + i % dim] : e;
-		}
-	}
+	if (temb_next && t_prev >= 0) next_embedding<GUIDED>(temb_next, t_prev, batch, dim, ctable, classes, rows, tid, stride);
 	const size_t n4 = vec ? n / 4 : 0;
 	for (size_t q = tid; q < n4; q += stride) {
-		float4 e = reinterpret_cast<const float4*>(eps_u)[q];
-		if constexpr (GUIDED) {
-			const float4 c = reinterpret_cast<const float4*>(eps_c)[q];
-			e = make_float4(fmaf(s, c.x - e.x, e.x), fmaf(s, c.y - e.y, e.y), fmaf(s, c.z - e.z, e.z), fmaf(s, c.w - e.w, e.w));
-		}
+		const float4 e = eps4_at<GUIDED>(eps_c, eps_u, s, q);
 		const float4 h = a.second ? reinterpret_cast<const float4*>(hist)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
 		float4 v = reinterpret_cast<float4*>(x)[q], p;
 		v = make_float4(dpmpp1(v.x, e.x, h.x, a, &p.x), dpmpp1(v.y, e.y, h.y, a, &p.y), dpmpp1(v.z, e.z, h.z, a, &p.z), dpmpp1(v.w, e.w, h.w, a, &p.w));
@@ -633,7 +595,7 @@ __global__ void __launch_bounds__(kThreads) dpmpp_step_kernel(float* __restrict_
 		if (GUIDED && x_copy) reinterpret_cast<float4*>(x_copy)[q] = v;
 	}
 	for (size_t i = 4 * n4 + tid; i < n; i += stride) {
-		const float e = GUIDED ? fmaf(s, eps_c[i] - eps_u[i], eps_u[i]) : eps_u[i];
+		const float e = eps_at<GUIDED>(eps_c, eps_u, s, i);
 		float p;
 		const float v = dpmpp1(x[i], e, a.second ? hist[i] : 0.f, a, &p);
 		x[i] = v;
@@ -809,6 +771,106 @@ bla_status finish_create(bla_diffusion* d, bla_diffusion** out, const char* who)
 bla_status output_to_eps(bla_unet* m, const bla_diffusion* d, void* stream, const float* d_x, int batch, size_t image_floats, int t) {
 	if (d->prediction == BLA_PREDICT_EPS) return BLA_OK;
 	return bla_diffusion_to_eps_f32(d, stream, bla_unet_output(m), d_x, nullptr, t, batch, image_floats);
+}
+
+// ---- the samplers: one walk, one guided set-up.  A sampler is a step function (one of the six bla_diffusion_*_step_f32) and a choice of timesteps -----------------
+
+// what a sampler needs to know of its model: the batch, the embedding's width, one image's floats
+struct ModelShape { int B, dim; size_t F; };
+
+ModelShape shape_of(bla_unet* m) {
+	const bla_unet_config& c = *unet_config(m);
+	return {bla_unet_batch(m), c.time_dim, (size_t)c.in_channels * c.image_h * c.image_w};
+}
+
+// The walk down the timesteps ts[S-1] > ... > ts[0] (ts NULL: ts[i] = i, every timestep without a list of them): the model on x with the embedding workspace, its
+// output read as eps_hat, then step(t_last, t, t_prev), which moves x to t_prev and writes the next embedding.  t_last is the timestep before t (-1 at the first),
+// t_prev the one behind it (-1 at the last).
+template <typename Step>
+bla_status sample_loop(bla_unet* m, const bla_diffusion* d, void* stream, const float* x, const ModelShape& g, const int* ts, int S, Step step) {
+	const auto at = [ts](int i) { return ts ? ts[i] : i; };
+	bla_status st;
+	for (int i = S - 1, t_last = -1; i >= 0; t_last = at(i), i--) {
+		if ((st = bla_unet_forward_f32(m, stream, x, d->temb, nullptr))) return st;
+		if ((st = output_to_eps(m, d, stream, x, g.B, g.F, at(i)))) return st;
+		if ((st = step(t_last, at(i), i > 0 ? at(i - 1) : -1))) return st;
+	}
+	return BLA_OK;
+}
+
+// an unguided sampler's set-up: the embedding workspace and hist_floats of history grown, the embedding of the first timestep written
+bla_status sample_start(const bla_diffusion* d, hipStream_t s, const ModelShape& g, int t_first, size_t hist_floats) {
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);   // the workspaces are scratch, not part of the schedule
+	const size_t ne = (size_t)g.B * g.dim;
+	bla_status st;
+	if ((st = grow(s, &dm->temb, &dm->temb_floats, ne))) return st;
+	if ((st = grow(s, &dm->hist, &dm->hist_floats, hist_floats))) return st;
+	hipLaunchKernelGGL(time_embedding_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, s, (const int*)nullptr, t_first, g.B, g.dim, dm->temb);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+// what the three guided samplers check before their own arguments
+bla_status check_guided_sampler(bla_unet* m, const bla_diffusion* d, const float* d_x, const float* d_table, int classes, const int* labels, float guidance) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_REQUIRE(m && d && d_x && d_table && labels, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(classes >= 1, BLA_ERR_INVALID, "classes %d", classes);
+	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
+	return BLA_OK;
+}
+
+// A guided sampler's set-up, n = B / 2 images: the workspaces grown, the model's input xg = [x; x], the rows [labels; classes ...] and the embedding of the first
+// timestep plus the class rows.  Device labels go to guided_start_kernel with no host round trip (one outside [0, classes] gets no class row).  Host labels are
+// checked here and the rows uploaded: the one wait for the stream that makes such a call not capturable.
+bla_status guided_start(const bla_diffusion* d, hipStream_t s, const ModelShape& g, const float* d_x, const float* d_table, int classes, const int* labels, int t_first,
+                        size_t hist_floats) {
+	const int B = g.B, n = B / 2;
+	BLA_REQUIRE(B % 2 == 0, BLA_ERR_INVALID, "the guided sampler needs an even model batch (n conditioned images + their n null-class copies), not %d", B);
+	bla_diffusion* dm = const_cast<bla_diffusion*>(d);   // the workspaces are scratch, not part of the schedule
+	const size_t ne = (size_t)B * g.dim, half = (size_t)n * g.F;
+	bla_status st;
+	if ((st = grow(s, &dm->temb, &dm->temb_floats, ne))) return st;
+	if ((st = grow(s, &dm->xg, &dm->xg_floats, 2 * half))) return st;
+	if ((st = grow(s, &dm->rows, &dm->rows_count, (size_t)B))) return st;
+	if ((st = grow(s, &dm->hist, &dm->hist_floats, hist_floats))) return st;
+	const int* dev_labels = labels;
+	if (host_pointer(labels)) {
+		std::vector<int> rows(B);
+		for (int b = 0; b < n; b++) {
+			BLA_REQUIRE(labels[b] >= 0 && labels[b] <= classes, BLA_ERR_INVALID, "label %d of image %d outside [0, %d]", labels[b], b, classes);
+			rows[b] = labels[b]; rows[n + b] = classes;
+		}
+		BLA_HIP(hipMemcpyAsync(dm->rows, rows.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+		BLA_HIP(hipStreamSynchronize(s));
+		dev_labels = nullptr;
+	}
+	BLA_HIP(hipMemcpyAsync(dm->xg, d_x, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+	BLA_HIP(hipMemcpyAsync(dm->xg + half, d_x, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+	hipLaunchKernelGGL(guided_start_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, s, dev_labels, n, classes, dm->rows, d_table, t_first, g.dim, dm->temb);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+// the tear-down: the first half of xg is the sample
+bla_status guided_finish(const bla_diffusion* d, hipStream_t s, const ModelShape& g, float* d_x) {
+	BLA_HIP(hipMemcpyAsync(d_x, d->xg, (size_t)(g.B / 2) * g.F * sizeof(float), hipMemcpyDeviceToDevice, s));
+	return BLA_OK;
+}
+
+// what the six *_step_f32 check before their own timesteps (have: the pointers each of them needs), and what the three guided ones check behind them
+bla_status check_step(const bla_diffusion* d, int batch, size_t image_floats, int time_dim, bool have) {
+	bla_status st = require_ready();
+	if (st) return st;
+	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
+	BLA_REQUIRE(have, BLA_ERR_INVALID, "null argument");
+	return BLA_OK;
+}
+
+bla_status check_guidance(float guidance, const float* d_table, int classes, const int* d_rows) {
+	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
+	BLA_REQUIRE(!d_table || (d_rows && classes >= 1), BLA_ERR_INVALID, "a class table needs the rows [2 batch] and classes >= 1");
+	return BLA_OK;
 }
 
 }  // namespace
@@ -992,118 +1054,59 @@ bla_status bla_diffusion_noise_f32(const bla_diffusion* d, void* stream, const f
 
 bla_status bla_diffusion_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, int batch, size_t image_floats, int t,
                                   unsigned long long seed, int time_dim, float* d_temb_next) {
-	bla_status st = require_ready();
+	bla_status st = check_step(d, batch, image_floats, time_dim, d_x && d_eps_hat);
 	if (st) return st;
-	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
-	BLA_REQUIRE(d_x && d_eps_hat, BLA_ERR_INVALID, "null argument");
 	BLA_REQUIRE(t >= 0 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", t, d->steps);
 	const size_t n = (size_t)batch * image_floats;
 	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_hat) % 16 == 0;
-	hipLaunchKernelGGL(step_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_eps_hat, n, t, d->steps, seed, d->table, batch,
-	                   time_dim, d_temb_next, vec);
+	hipLaunchKernelGGL((step_kernel<false>), dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, (float*)nullptr, (const float*)nullptr,
+	                   d_eps_hat, 0.f, n, t, d->steps, seed, d->table, batch, time_dim, d_temb_next, (const float*)nullptr, 0, (const int*)nullptr, vec);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
 }
 
+// the ancestral sampler: every timestep, T - 1 down to 0
 bla_status bla_unet_sample_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, unsigned long long seed) {
 	bla_status st = require_ready();
 	if (st) return st;
 	BLA_REQUIRE(m && d && d_x, BLA_ERR_INVALID, "null argument");
-	const bla_unet_config& c = *unet_config(m);
-	const int B = bla_unet_batch(m), T = d->steps;
-	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
-	bla_diffusion* dm = const_cast<bla_diffusion*>(d);   // the embedding workspace is scratch, not part of the schedule
-	if (dm->temb_floats < ne) {
-		BLA_HIP(hipStreamSynchronize(pick_stream(stream)));
-		(void)hipFree(dm->temb); dm->temb = nullptr; dm->temb_floats = 0;
-		BLA_HIP(hipMalloc((void**)&dm->temb, ne * sizeof(float)));
-		dm->temb_floats = ne;
-	}
-	hipLaunchKernelGGL(time_embedding_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, pick_stream(stream), (const int*)nullptr, T - 1, B, c.time_dim, dm->temb);
-	BLA_HIP(hipGetLastError());
-	for (int t = T - 1; t >= 0; t--) {
-		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
-		if ((st = output_to_eps(m, d, stream, d_x, B, F, t))) return st;
-		if ((st = bla_diffusion_step_f32(d, stream, d_x, bla_unet_output(m), B, F, t, seed, c.time_dim, dm->temb))) return st;
-	}
-	return BLA_OK;
+	const ModelShape g = shape_of(m);
+	if ((st = sample_start(d, pick_stream(stream), g, d->steps - 1, 0))) return st;
+	return sample_loop(m, d, stream, d_x, g, nullptr, d->steps, [&](int, int t, int) {
+		return bla_diffusion_step_f32(d, stream, d_x, bla_unet_output(m), g.B, g.F, t, seed, g.dim, d->temb);
+	});
 }
 
 bla_status bla_diffusion_guided_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond, const float* d_eps_uncond,
                                          float guidance, int batch, size_t image_floats, int t, unsigned long long seed, int time_dim, float* d_temb_next,
                                          const float* d_table, int classes, const int* d_rows) {
-	bla_status st = require_ready();
+	bla_status st = check_step(d, batch, image_floats, time_dim, d_x && d_eps_cond && d_eps_uncond);
 	if (st) return st;
-	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
-	BLA_REQUIRE(d_x && d_eps_cond && d_eps_uncond, BLA_ERR_INVALID, "null argument");
 	BLA_REQUIRE(t >= 0 && t < d->steps, BLA_ERR_INVALID, "timestep %d outside [0, %d)", t, d->steps);
-	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
-	BLA_REQUIRE(!d_table || (d_rows && classes >= 1), BLA_ERR_INVALID, "a class table needs the rows [2 batch] and classes >= 1");
+	if ((st = check_guidance(guidance, d_table, classes, d_rows))) return st;
 	const size_t n = (size_t)batch * image_floats;
 	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_cond | (uintptr_t)d_eps_uncond | (uintptr_t)d_x_copy) % 16 == 0;
-	hipLaunchKernelGGL(guided_step_kernel, dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_x_copy, d_eps_cond, d_eps_uncond, guidance, n, t,
-	                   d->steps, seed, d->table, batch, time_dim, d_temb_next, d_table, classes, d_rows, vec);
+	hipLaunchKernelGGL((step_kernel<true>), dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_x_copy, d_eps_cond, d_eps_uncond, guidance, n,
+	                   t, d->steps, seed, d->table, batch, time_dim, d_temb_next, d_table, classes, d_rows, vec);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
 }
 
 bla_status bla_unet_sample_guided_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes, const int* labels, float guidance,
                                       unsigned long long seed) {
-	bla_status st = require_ready();
+	bla_status st = check_guided_sampler(m, d, d_x, d_table, classes, labels, guidance);
 	if (st) return st;
-	BLA_REQUIRE(m && d && d_x && d_table && labels, BLA_ERR_INVALID, "null argument");
-	BLA_REQUIRE(classes >= 1, BLA_ERR_INVALID, "classes %d", classes);
-	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
-	const bla_unet_config& c = *unet_config(m);
-	const int B = bla_unet_batch(m), n = B / 2, T = d->steps;
-	BLA_REQUIRE(B % 2 == 0, BLA_ERR_INVALID, "the guided sampler needs an even model batch (n conditioned images + their n null-class copies), not %d", B);
-	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim, nx = (size_t)B * F;
+	const ModelShape g = shape_of(m);
 	hipStream_t s = pick_stream(stream);
-	bla_diffusion* dm = const_cast<bla_diffusion*>(d);   // workspaces, not part of the schedule
-	if (dm->temb_floats < ne || dm->xg_floats < nx || dm->rows_count < B) {
-		BLA_HIP(hipStreamSynchronize(s));
-		if (dm->temb_floats < ne) {
-			(void)hipFree(dm->temb); dm->temb = nullptr; dm->temb_floats = 0;
-			BLA_HIP(hipMalloc((void**)&dm->temb, ne * sizeof(float)));
-			dm->temb_floats = ne;
-		}
-		if (dm->xg_floats < nx) {
-			(void)hipFree(dm->xg); dm->xg = nullptr; dm->xg_floats = 0;
-			BLA_HIP(hipMalloc((void**)&dm->xg, nx * sizeof(float)));
-			dm->xg_floats = nx;
-		}
-		if (dm->rows_count < B) {
-			(void)hipFree(dm->rows); dm->rows = nullptr; dm->rows_count = 0;
-			BLA_HIP(hipMalloc((void**)&dm->rows, (size_t)B * sizeof(int)));
-			dm->rows_count = B;
-		}
-	}
-	const int* dev_labels = labels;
-	if (host_pointer(labels)) {   // host labels: checked here, the rows uploaded (not capturable: the copy waits for the host)
-		std::vector<int> rows(B);
-		for (int b = 0; b < n; b++) {
-			BLA_REQUIRE(labels[b] >= 0 && labels[b] <= classes, BLA_ERR_INVALID, "label %d of image %d outside [0, %d]", labels[b], b, classes);
-			rows[b] = labels[b]; rows[n + b] = classes;
-		}
-		BLA_HIP(hipMemcpyAsync(dm->rows, rows.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-		BLA_HIP(hipStreamSynchronize(s));
-		dev_labels = nullptr;
-	}
-	float* xg = dm->xg;
-	BLA_HIP(hipMemcpyAsync(xg, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	BLA_HIP(hipMemcpyAsync(xg + (size_t)n * F, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	hipLaunchKernelGGL(guided_start_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, s, dev_labels, n, classes, dm->rows, d_table, T - 1, c.time_dim, dm->temb);
-	BLA_HIP(hipGetLastError());
+	if ((st = guided_start(d, s, g, d_x, d_table, classes, labels, d->steps - 1, 0))) return st;
+	const int n = g.B / 2;
+	float* xg = d->xg;
 	const float* out = bla_unet_output(m);
-	for (int t = T - 1; t >= 0; t--) {
-		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
-		if ((st = output_to_eps(m, d, stream, xg, B, F, t))) return st;
-		if ((st = bla_diffusion_guided_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, n, F, t, seed, c.time_dim, dm->temb, d_table,
-		                                        classes, dm->rows)))
-			return st;
-	}
-	BLA_HIP(hipMemcpyAsync(d_x, xg, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	return BLA_OK;
+	if ((st = sample_loop(m, d, stream, xg, g, nullptr, d->steps, [&](int, int t, int) {
+		    return bla_diffusion_guided_step_f32(d, stream, xg, xg + n * g.F, out, out + n * g.F, guidance, n, g.F, t, seed, g.dim, d->temb, d_table, classes, d->rows);
+	    })))
+		return st;
+	return guided_finish(d, s, g, d_x);
 }
 
 bla_status bla_mse_accumulate_f32(void* stream, const float* d_a, const float* d_b, size_t n, double* d_acc) {
@@ -1125,10 +1128,8 @@ bla_status bla_diffusion_ddim_timesteps(const bla_diffusion* d, int sample_steps
 
 bla_status bla_diffusion_ddim_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, int batch, size_t image_floats, int t, int t_prev,
                                        float eta, int clip, unsigned long long seed, int time_dim, float* d_temb_next) {
-	bla_status st = require_ready();
+	bla_status st = check_step(d, batch, image_floats, time_dim, d_x && d_eps_hat);
 	if (st) return st;
-	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
-	BLA_REQUIRE(d_x && d_eps_hat, BLA_ERR_INVALID, "null argument");
 	if ((st = check_ddim(d, t, t_prev, eta))) return st;
 	const size_t n = (size_t)batch * image_floats;
 	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_hat) % 16 == 0;
@@ -1145,33 +1146,21 @@ bla_status bla_unet_sample_ddim_f32(bla_unet* m, const bla_diffusion* d, void* s
 	BLA_REQUIRE(m && d && d_x, BLA_ERR_INVALID, "null argument");
 	BLA_REQUIRE(sample_steps >= 1 && sample_steps <= d->steps, BLA_ERR_INVALID, "sample_steps %d outside [1, %d]", sample_steps, d->steps);
 	BLA_REQUIRE(eta >= 0.f && eta <= 1.f, BLA_ERR_INVALID, "eta %g outside [0, 1]", eta);
-	const bla_unet_config& c = *unet_config(m);
-	const int B = bla_unet_batch(m);
-	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
-	bla_diffusion* dm = const_cast<bla_diffusion*>(d);
-	if ((st = grow_workspaces(dm, pick_stream(stream), ne, 0, 0))) return st;
 	const std::vector<int> ts = ddim_timesteps(d->steps, sample_steps);
-	hipLaunchKernelGGL(time_embedding_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, pick_stream(stream), (const int*)nullptr, ts.back(), B, c.time_dim, dm->temb);
-	BLA_HIP(hipGetLastError());
-	for (int i = sample_steps - 1; i >= 0; i--) {
-		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
-		if ((st = output_to_eps(m, d, stream, d_x, B, F, ts[i]))) return st;
-		if ((st = bla_diffusion_ddim_step_f32(d, stream, d_x, bla_unet_output(m), B, F, ts[i], i > 0 ? ts[i - 1] : -1, eta, clip, seed, c.time_dim, dm->temb)))
-			return st;
-	}
-	return BLA_OK;
+	const ModelShape g = shape_of(m);
+	if ((st = sample_start(d, pick_stream(stream), g, ts.back(), 0))) return st;
+	return sample_loop(m, d, stream, d_x, g, ts.data(), sample_steps, [&](int, int t, int t_prev) {
+		return bla_diffusion_ddim_step_f32(d, stream, d_x, bla_unet_output(m), g.B, g.F, t, t_prev, eta, clip, seed, g.dim, d->temb);
+	});
 }
 
 bla_status bla_diffusion_guided_ddim_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond, const float* d_eps_uncond,
                                               float guidance, int batch, size_t image_floats, int t, int t_prev, float eta, int clip, unsigned long long seed,
                                               int time_dim, float* d_temb_next, const float* d_table, int classes, const int* d_rows) {
-	bla_status st = require_ready();
+	bla_status st = check_step(d, batch, image_floats, time_dim, d_x && d_eps_cond && d_eps_uncond);
 	if (st) return st;
-	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
-	BLA_REQUIRE(d_x && d_eps_cond && d_eps_uncond, BLA_ERR_INVALID, "null argument");
 	if ((st = check_ddim(d, t, t_prev, eta))) return st;
-	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
-	BLA_REQUIRE(!d_table || (d_rows && classes >= 1), BLA_ERR_INVALID, "a class table needs the rows [2 batch] and classes >= 1");
+	if ((st = check_guidance(guidance, d_table, classes, d_rows))) return st;
 	const size_t n = (size_t)batch * image_floats;
 	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_cond | (uintptr_t)d_eps_uncond | (uintptr_t)d_x_copy) % 16 == 0;
 	hipLaunchKernelGGL((ddim_step_kernel<true>), dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_x_copy, d_eps_cond, d_eps_uncond,
@@ -1182,47 +1171,23 @@ bla_status bla_diffusion_guided_ddim_step_f32(const bla_diffusion* d, void* stre
 
 bla_status bla_unet_sample_guided_ddim_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes, const int* labels,
                                            float guidance, int sample_steps, float eta, int clip, unsigned long long seed) {
-	bla_status st = require_ready();
+	bla_status st = check_guided_sampler(m, d, d_x, d_table, classes, labels, guidance);
 	if (st) return st;
-	BLA_REQUIRE(m && d && d_x && d_table && labels, BLA_ERR_INVALID, "null argument");
-	BLA_REQUIRE(classes >= 1, BLA_ERR_INVALID, "classes %d", classes);
-	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
 	BLA_REQUIRE(sample_steps >= 1 && sample_steps <= d->steps, BLA_ERR_INVALID, "sample_steps %d outside [1, %d]", sample_steps, d->steps);
 	BLA_REQUIRE(eta >= 0.f && eta <= 1.f, BLA_ERR_INVALID, "eta %g outside [0, 1]", eta);
-	const bla_unet_config& c = *unet_config(m);
-	const int B = bla_unet_batch(m), n = B / 2;
-	BLA_REQUIRE(B % 2 == 0, BLA_ERR_INVALID, "the guided sampler needs an even model batch (n conditioned images + their n null-class copies), not %d", B);
-	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
-	hipStream_t s = pick_stream(stream);
-	bla_diffusion* dm = const_cast<bla_diffusion*>(d);
-	if ((st = grow_workspaces(dm, s, ne, (size_t)B * F, B))) return st;
-	const int* dev_labels = labels;
-	if (host_pointer(labels)) {   // host labels: checked here, the rows uploaded (not capturable: the copy waits for the host)
-		std::vector<int> rows(B);
-		for (int b = 0; b < n; b++) {
-			BLA_REQUIRE(labels[b] >= 0 && labels[b] <= classes, BLA_ERR_INVALID, "label %d of image %d outside [0, %d]", labels[b], b, classes);
-			rows[b] = labels[b]; rows[n + b] = classes;
-		}
-		BLA_HIP(hipMemcpyAsync(dm->rows, rows.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-		BLA_HIP(hipStreamSynchronize(s));
-		dev_labels = nullptr;
-	}
 	const std::vector<int> ts = ddim_timesteps(d->steps, sample_steps);
-	float* xg = dm->xg;
-	BLA_HIP(hipMemcpyAsync(xg, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	BLA_HIP(hipMemcpyAsync(xg + (size_t)n * F, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	hipLaunchKernelGGL(guided_start_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, s, dev_labels, n, classes, dm->rows, d_table, ts.back(), c.time_dim, dm->temb);
-	BLA_HIP(hipGetLastError());
+	const ModelShape g = shape_of(m);
+	hipStream_t s = pick_stream(stream);
+	if ((st = guided_start(d, s, g, d_x, d_table, classes, labels, ts.back(), 0))) return st;
+	const int n = g.B / 2;
+	float* xg = d->xg;
 	const float* out = bla_unet_output(m);
-	for (int i = sample_steps - 1; i >= 0; i--) {
-		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
-		if ((st = output_to_eps(m, d, stream, xg, B, F, ts[i]))) return st;
-		if ((st = bla_diffusion_guided_ddim_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, n, F, ts[i], i > 0 ? ts[i - 1] : -1, eta,
-		                                             clip, seed, c.time_dim, dm->temb, d_table, classes, dm->rows)))
-			return st;
-	}
-	BLA_HIP(hipMemcpyAsync(d_x, xg, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	return BLA_OK;
+	if ((st = sample_loop(m, d, stream, xg, g, ts.data(), sample_steps, [&](int, int t, int t_prev) {
+		    return bla_diffusion_guided_ddim_step_f32(d, stream, xg, xg + n * g.F, out, out + n * g.F, guidance, n, g.F, t, t_prev, eta, clip, seed, g.dim, d->temb,
+		                                              d_table, classes, d->rows);
+	    })))
+		return st;
+	return guided_finish(d, s, g, d_x);
 }
 
 // ---- DPM-Solver++(2M) ---------------------------------------------------------------------------------------------------------------------------
@@ -1246,10 +1211,8 @@ bla_status bla_diffusion_dpmpp_coefficients(const bla_diffusion* d, int t_last, 
 
 bla_status bla_diffusion_dpmpp_step_f32(const bla_diffusion* d, void* stream, float* d_x, const float* d_eps_hat, float* d_x0_hist, int batch, size_t image_floats,
                                         int t_last, int t, int t_prev, int clip, int time_dim, float* d_temb_next) {
-	bla_status st = require_ready();
+	bla_status st = check_step(d, batch, image_floats, time_dim, d_x && d_eps_hat && d_x0_hist);
 	if (st) return st;
-	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
-	BLA_REQUIRE(d_x && d_eps_hat && d_x0_hist, BLA_ERR_INVALID, "null argument");
 	if ((st = check_dpmpp(d, t_last, t, t_prev))) return st;
 	const size_t n = (size_t)batch * image_floats;
 	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_hat | (uintptr_t)d_x0_hist) % 16 == 0;
@@ -1263,13 +1226,10 @@ bla_status bla_diffusion_dpmpp_step_f32(const bla_diffusion* d, void* stream, fl
 bla_status bla_diffusion_guided_dpmpp_step_f32(const bla_diffusion* d, void* stream, float* d_x, float* d_x_copy, const float* d_eps_cond, const float* d_eps_uncond,
                                                float guidance, float* d_x0_hist, int batch, size_t image_floats, int t_last, int t, int t_prev, int clip,
                                                int time_dim, float* d_temb_next, const float* d_table, int classes, const int* d_rows) {
-	bla_status st = require_ready();
+	bla_status st = check_step(d, batch, image_floats, time_dim, d_x && d_eps_cond && d_eps_uncond && d_x0_hist);
 	if (st) return st;
-	if ((st = check_images(d, batch, image_floats, time_dim))) return st;
-	BLA_REQUIRE(d_x && d_eps_cond && d_eps_uncond && d_x0_hist, BLA_ERR_INVALID, "null argument");
 	if ((st = check_dpmpp(d, t_last, t, t_prev))) return st;
-	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
-	BLA_REQUIRE(!d_table || (d_rows && classes >= 1), BLA_ERR_INVALID, "a class table needs the rows [2 batch] and classes >= 1");
+	if ((st = check_guidance(guidance, d_table, classes, d_rows))) return st;
 	const size_t n = (size_t)batch * image_floats;
 	const int vec = ((uintptr_t)d_x | (uintptr_t)d_eps_cond | (uintptr_t)d_eps_uncond | (uintptr_t)d_x_copy | (uintptr_t)d_x0_hist) % 16 == 0;
 	hipLaunchKernelGGL((dpmpp_step_kernel<true>), dim3(grid_for(vec ? n / 4 : n)), dim3(kThreads), 0, pick_stream(stream), d_x, d_x_copy, d_eps_cond, d_eps_uncond,
@@ -1284,64 +1244,31 @@ bla_status bla_unet_sample_dpmpp_f32(bla_unet* m, const bla_diffusion* d, void* 
 	BLA_REQUIRE(m && d && d_x, BLA_ERR_INVALID, "null argument");
 	std::vector<int> ts;
 	if ((st = sample_timesteps(d, sample_steps, spacing, &ts))) return st;
-	const bla_unet_config& c = *unet_config(m);
-	const int B = bla_unet_batch(m);
-	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
-	bla_diffusion* dm = const_cast<bla_diffusion*>(d);
-	if ((st = grow_workspaces(dm, pick_stream(stream), ne, 0, 0, (size_t)B * F))) return st;
-	hipLaunchKernelGGL(time_embedding_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, pick_stream(stream), (const int*)nullptr, ts.back(), B, c.time_dim, dm->temb);
-	BLA_HIP(hipGetLastError());
-	for (int i = sample_steps - 1, t_last = -1; i >= 0; t_last = ts[i], i--) {
-		if ((st = bla_unet_forward_f32(m, stream, d_x, dm->temb, nullptr))) return st;
-		if ((st = output_to_eps(m, d, stream, d_x, B, F, ts[i]))) return st;
-		if ((st = bla_diffusion_dpmpp_step_f32(d, stream, d_x, bla_unet_output(m), dm->hist, B, F, t_last, ts[i], i > 0 ? ts[i - 1] : -1, clip, c.time_dim, dm->temb)))
-			return st;
-	}
-	return BLA_OK;
+	const ModelShape g = shape_of(m);
+	if ((st = sample_start(d, pick_stream(stream), g, ts.back(), (size_t)g.B * g.F))) return st;
+	return sample_loop(m, d, stream, d_x, g, ts.data(), sample_steps, [&](int t_last, int t, int t_prev) {
+		return bla_diffusion_dpmpp_step_f32(d, stream, d_x, bla_unet_output(m), d->hist, g.B, g.F, t_last, t, t_prev, clip, g.dim, d->temb);
+	});
 }
 
 bla_status bla_unet_sample_guided_dpmpp_f32(bla_unet* m, const bla_diffusion* d, void* stream, float* d_x, const float* d_table, int classes, const int* labels,
                                             float guidance, int sample_steps, int spacing, int clip) {
-	bla_status st = require_ready();
+	bla_status st = check_guided_sampler(m, d, d_x, d_table, classes, labels, guidance);
 	if (st) return st;
-	BLA_REQUIRE(m && d && d_x && d_table && labels, BLA_ERR_INVALID, "null argument");
-	BLA_REQUIRE(classes >= 1, BLA_ERR_INVALID, "classes %d", classes);
-	BLA_REQUIRE(std::isfinite(guidance), BLA_ERR_INVALID, "guidance %g", guidance);
 	std::vector<int> ts;
 	if ((st = sample_timesteps(d, sample_steps, spacing, &ts))) return st;
-	const bla_unet_config& c = *unet_config(m);
-	const int B = bla_unet_batch(m), n = B / 2;
-	BLA_REQUIRE(B % 2 == 0, BLA_ERR_INVALID, "the guided sampler needs an even model batch (n conditioned images + their n null-class copies), not %d", B);
-	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim;
+	const ModelShape g = shape_of(m);
 	hipStream_t s = pick_stream(stream);
-	bla_diffusion* dm = const_cast<bla_diffusion*>(d);
-	if ((st = grow_workspaces(dm, s, ne, (size_t)B * F, B, (size_t)n * F))) return st;
-	const int* dev_labels = labels;
-	if (host_pointer(labels)) {   // host labels: checked here, the rows uploaded (not capturable: the copy waits for the host)
-		std::vector<int> rows(B);
-		for (int b = 0; b < n; b++) {
-			BLA_REQUIRE(labels[b] >= 0 && labels[b] <= classes, BLA_ERR_INVALID, "label %d of image %d outside [0, %d]", labels[b], b, classes);
-			rows[b] = labels[b]; rows[n + b] = classes;
-		}
-		BLA_HIP(hipMemcpyAsync(dm->rows, rows.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-		BLA_HIP(hipStreamSynchronize(s));
-		dev_labels = nullptr;
-	}
-	float* xg = dm->xg;
-	BLA_HIP(hipMemcpyAsync(xg, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	BLA_HIP(hipMemcpyAsync(xg + (size_t)n * F, d_x, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	hipLaunchKernelGGL(guided_start_kernel, dim3(grid_for(ne)), dim3(kThreads), 0, s, dev_labels, n, classes, dm->rows, d_table, ts.back(), c.time_dim, dm->temb);
-	BLA_HIP(hipGetLastError());
+	const int n = g.B / 2;
+	if ((st = guided_start(d, s, g, d_x, d_table, classes, labels, ts.back(), n * g.F))) return st;
+	float* xg = d->xg;
 	const float* out = bla_unet_output(m);
-	for (int i = sample_steps - 1, t_last = -1; i >= 0; t_last = ts[i], i--) {
-		if ((st = bla_unet_forward_f32(m, stream, xg, dm->temb, nullptr))) return st;
-		if ((st = output_to_eps(m, d, stream, xg, B, F, ts[i]))) return st;
-		if ((st = bla_diffusion_guided_dpmpp_step_f32(d, stream, xg, xg + (size_t)n * F, out, out + (size_t)n * F, guidance, dm->hist, n, F, t_last, ts[i],
-		                                              i > 0 ? ts[i - 1] : -1, clip, c.time_dim, dm->temb, d_table, classes, dm->rows)))
-			return st;
-	}
-	BLA_HIP(hipMemcpyAsync(d_x, xg, (size_t)n * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-	return BLA_OK;
+	if ((st = sample_loop(m, d, stream, xg, g, ts.data(), sample_steps, [&](int t_last, int t, int t_prev) {
+		    return bla_diffusion_guided_dpmpp_step_f32(d, stream, xg, xg + n * g.F, out, out + n * g.F, guidance, d->hist, n, g.F, t_last, t, t_prev, clip, g.dim,
+		                                               d->temb, d_table, classes, d->rows);
+	    })))
+		return st;
+	return guided_finish(d, s, g, d_x);
 }
 
 // ---- held-out evaluation ------------------------------------------------------------------------------------------------------------------------
@@ -1420,20 +1347,9 @@ bla_status bla_unet_evaluate_f32(bla_unet* m, const bla_diffusion* d, void* stre
 	const size_t F = (size_t)c.in_channels * c.image_h * c.image_w, ne = (size_t)B * c.time_dim, nx = (size_t)B * F;
 	hipStream_t s = pick_stream(stream);
 	bla_diffusion* dm = const_cast<bla_diffusion*>(d);   // workspaces, not part of the schedule
-	if (dm->ev_floats < 2 * nx || dm->ev_temb_floats < ne) {
-		BLA_HIP(hipStreamSynchronize(s));
-		if (dm->ev_floats < 2 * nx) {
-			(void)hipFree(dm->ev); dm->ev = nullptr; dm->ev_floats = 0;
-			BLA_HIP(hipMalloc((void**)&dm->ev, 2 * nx * sizeof(float)));
-			dm->ev_floats = 2 * nx;
-		}
-		if (dm->ev_temb_floats < ne) {
-			(void)hipFree(dm->ev_temb); dm->ev_temb = nullptr; dm->ev_temb_floats = 0;
-			BLA_HIP(hipMalloc((void**)&dm->ev_temb, ne * sizeof(float)));
-			dm->ev_temb_floats = ne;
-		}
-	}
-	if (d_table && (st = grow_workspaces(dm, s, 0, 0, B))) return st;   // the rows bla_class_embedding_f32 writes
+	if ((st = grow(s, &dm->ev, &dm->ev_floats, 2 * nx))) return st;
+	if ((st = grow(s, &dm->ev_temb, &dm->ev_temb_floats, ne))) return st;
+	if (d_table && (st = grow(s, &dm->rows, &dm->rows_count, (size_t)B))) return st;   // the rows bla_class_embedding_f32 writes
 	float *eps = dm->ev, *xt = dm->ev + nx;
 	for (int i = 0; i < count; i++) {
 		const int t = timesteps[i];

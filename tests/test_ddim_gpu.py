@@ -328,6 +328,26 @@ def test_guided_ddim_sampler(pkg, L):
     assert np.array_equal(x2.numpy()[:n], got)
     print(f"guided DDIM sampler steps vs numpy on the same x and outputs: worst {worst:.2f} of step_error's bound")
     assert worst <= 1, worst
+    # a device label outside [0, classes] cannot be refused without a round trip: its image is sampled with no class row -- the composed loop at row -1
+    want = sample(5, [3, CLASSES + 5], 0.5)
+    chk(pkg, L.bla_rand_normal_f32(None, x2.ptr, n * F, 0.0, 1.0, 5, 0))
+    chk(pkg, L.bla_rand_normal_f32(None, x2.ptr + 4 * n * F, n * F, 0.0, 1.0, 5, 0))
+    chk(pkg, L.bla_time_embedding_f32(None, dts.ptr, 2 * n, dim, temb.ptr))
+    dl2 = pkg.to_device(np.array([3, CLASSES + 5, CLASSES, CLASSES], np.int32), np.int32)
+    chk(pkg, L.bla_class_embedding_f32(None, dtab.ptr, CLASSES, dl2.ptr, 2 * n, dim, 0.0, 0, 0, rows.ptr, temb.ptr))
+    assert rows.numpy().tolist() == [3, -1, CLASSES, CLASSES]
+    for i in range(S - 1, -1, -1):
+        chk(pkg, L.bla_unet_forward_f32(h, None, x2.ptr, temb.ptr, None))
+        chk(pkg, L.bla_diffusion_guided_ddim_step_f32(d, None, x2.ptr, x2.ptr + 4 * n * F, out, out + 4 * n * F, s, n, F, ts[i], ts[i - 1] if i else -1, 0.5, 1, 5, dim,
+                                                      temb.ptr, dtab.ptr, CLASSES, rows.ptr))
+    assert np.array_equal(x2.numpy()[:n], want)
+    # a host label outside [0, classes] is refused before anything touches x
+    chk(pkg, L.bla_rand_normal_f32(None, x.ptr, n * F, 0.0, 1.0, 5, 0))
+    before = x.numpy()
+    for bad in ([3, CLASSES + 1], [-1, 7]):
+        lab = np.array(bad, np.int32)
+        assert L.bla_unet_sample_guided_ddim_f32(h, d, None, x.ptr, dtab.ptr, CLASSES, lab.ctypes.data, s, S, 0.5, 1, 5) == BLA_ERR_INVALID, bad
+        assert np.array_equal(x.numpy(), before), bad
     for s_bad in (0, T + 1):
         assert L.bla_unet_sample_guided_ddim_f32(h, d, None, x.ptr, dtab.ptr, CLASSES, pkg.to_device(np.array([1, 2], np.int32), np.int32).ptr, s, s_bad, 0.0, 0,
                                                  5) == BLA_ERR_INVALID

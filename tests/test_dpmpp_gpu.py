@@ -302,23 +302,32 @@ def test_guided_dpmpp_sampler(pkg, L):
     dlab = pkg.to_device(lab, np.int32)
     x2, temb, rows, hist = pkg.empty((2 * n, UNET_F)), pkg.empty((2 * n, dim)), pkg.empty((2 * n,), np.int32), pkg.empty((n, UNET_F))
     out = L.bla_unet_output(h)
-    for spacing in (LOGSNR, TRAILING):
+    # the third case: a device label outside [0, classes] cannot be refused without a round trip, so its image is sampled with no class row (row -1 in the
+    # composed loop); the same label on the host is refused before anything touches x
+    for spacing, lb in ((LOGSNR, lab), (TRAILING, lab), (LOGSNR, np.array([3, CLASSES + 5], np.int32))):
+        dlb = pkg.to_device(lb, np.int32)
         chk(pkg, L.bla_rand_normal_f32(None, x.ptr, n * UNET_F, 0.0, 1.0, 5, 0))
-        chk(pkg, L.bla_unet_sample_guided_dpmpp_f32(h, d, None, x.ptr, dtab.ptr, CLASSES, dlab.ptr, s, S, spacing, 1))
+        noise = x.numpy()
+        chk(pkg, L.bla_unet_sample_guided_dpmpp_f32(h, d, None, x.ptr, dtab.ptr, CLASSES, dlb.ptr, s, S, spacing, 1))
         want = x.numpy()
         assert np.isfinite(want).all()
-        for labels in (dlab.ptr, lab.ctypes.data):                                     # again (workspaces grown), and with host labels
+        for labels in (dlb.ptr, lb.ctypes.data):                                     # again (workspaces grown), and with host labels
             chk(pkg, L.bla_rand_normal_f32(None, x.ptr, n * UNET_F, 0.0, 1.0, 5, 0))
-            chk(pkg, L.bla_unet_sample_guided_dpmpp_f32(h, d, None, x.ptr, dtab.ptr, CLASSES, labels, s, S, spacing, 1))
-            assert np.array_equal(x.numpy(), want), spacing
+            status = L.bla_unet_sample_guided_dpmpp_f32(h, d, None, x.ptr, dtab.ptr, CLASSES, labels, s, S, spacing, 1)
+            if labels == lb.ctypes.data and lb.max() > CLASSES:
+                assert status == BLA_ERR_INVALID and np.array_equal(x.numpy(), noise)
+            else:
+                chk(pkg, status)
+                assert np.array_equal(x.numpy(), want), spacing
         # composed from the public pieces as in test_guided_ddim_sampler
         ts = sample_ts(sched, S, spacing)
         chk(pkg, L.bla_rand_normal_f32(None, x2.ptr, n * UNET_F, 0.0, 1.0, 5, 0))
         chk(pkg, L.bla_rand_normal_f32(None, x2.ptr + 4 * n * UNET_F, n * UNET_F, 0.0, 1.0, 5, 0))
         upload(pkg, hist.ptr, np.full((n, UNET_F), np.nan, np.float32))
-        dts, dl2 = pkg.to_device(np.full(2 * n, ts[-1], np.int32), np.int32), pkg.to_device(np.array([3, 7, CLASSES, CLASSES], np.int32), np.int32)
+        dts, dl2 = pkg.to_device(np.full(2 * n, ts[-1], np.int32), np.int32), pkg.to_device(np.array(list(lb) + [CLASSES, CLASSES], np.int32), np.int32)
         chk(pkg, L.bla_time_embedding_f32(None, dts.ptr, 2 * n, dim, temb.ptr))
         chk(pkg, L.bla_class_embedding_f32(None, dtab.ptr, CLASSES, dl2.ptr, 2 * n, dim, 0.0, 0, 0, rows.ptr, temb.ptr))
+        assert rows.numpy().tolist() == [int(r) if r <= CLASSES else -1 for r in lb] + [CLASSES, CLASSES]
         t_last = -1
         for i in range(S - 1, -1, -1):
             t, t_prev = ts[i], ts[i - 1] if i else -1

@@ -315,18 +315,28 @@ def test_guided_sampler(pkg, L):
     assert np.array_equal(sample(5, [3, 7], host=True), got)
     assert not np.array_equal(sample(6, [3, 7]), got)
     assert not np.array_equal(sample(5, [5, 7])[0], got[0])
-    # the same loop composed from the public pieces: one batch-2n forward pass and the guided step per timestep -- bit-equal
+    # a host label outside [0, classes] is refused before anything touches x
+    chk(pkg, L.bla_rand_normal_f32(None, x.ptr, n * F, 0.0, 1.0, 5, 0))
+    before = x.numpy()
+    for bad in ([3, CLASSES + 1], [-1, 7]):
+        lab = np.array(bad, np.int32)
+        assert L.bla_unet_sample_guided_f32(h, d, None, x.ptr, dtab.ptr, CLASSES, lab.ctypes.data, s, 5) == BLA_ERR_INVALID, bad
+        assert np.array_equal(x.numpy(), before), bad
+    # the same loop composed from the public pieces: one batch-2n forward pass and the guided step per timestep -- bit-equal.  A device label outside
+    # [0, classes] cannot be refused without a round trip: its image is sampled with no class row (row -1)
     x2, temb, rows = pkg.empty((2 * n, F)), pkg.empty((2 * n, dim)), pkg.empty((2 * n,), np.int32)
-    chk(pkg, L.bla_rand_normal_f32(None, x2.ptr, n * F, 0.0, 1.0, 5, 0))
-    chk(pkg, L.bla_rand_normal_f32(None, x2.ptr + 4 * n * F, n * F, 0.0, 1.0, 5, 0))
-    dts, dl2 = pkg.to_device(np.full(2 * n, T - 1, np.int32), np.int32), pkg.to_device(np.array([3, 7, CLASSES, CLASSES], np.int32), np.int32)
-    chk(pkg, L.bla_time_embedding_f32(None, dts.ptr, 2 * n, dim, temb.ptr))
-    chk(pkg, L.bla_class_embedding_f32(None, dtab.ptr, CLASSES, dl2.ptr, 2 * n, dim, 0.0, 0, 0, rows.ptr, temb.ptr))
     out = L.bla_unet_output(h)
-    for t in range(T - 1, -1, -1):
-        chk(pkg, L.bla_unet_forward_f32(h, None, x2.ptr, temb.ptr, None))
-        chk(pkg, L.bla_diffusion_guided_step_f32(d, None, x2.ptr, x2.ptr + 4 * n * F, out, out + 4 * n * F, s, n, F, t, 5, dim, temb.ptr, dtab.ptr, CLASSES, rows.ptr))
-    assert np.array_equal(x2.numpy()[:n], got)
+    for labels, want in (([3, 7], got), ([3, CLASSES + 5], sample(5, [3, CLASSES + 5]))):
+        chk(pkg, L.bla_rand_normal_f32(None, x2.ptr, n * F, 0.0, 1.0, 5, 0))
+        chk(pkg, L.bla_rand_normal_f32(None, x2.ptr + 4 * n * F, n * F, 0.0, 1.0, 5, 0))
+        dts, dl2 = pkg.to_device(np.full(2 * n, T - 1, np.int32), np.int32), pkg.to_device(np.array(labels + [CLASSES, CLASSES], np.int32), np.int32)
+        chk(pkg, L.bla_time_embedding_f32(None, dts.ptr, 2 * n, dim, temb.ptr))
+        chk(pkg, L.bla_class_embedding_f32(None, dtab.ptr, CLASSES, dl2.ptr, 2 * n, dim, 0.0, 0, 0, rows.ptr, temb.ptr))
+        assert rows.numpy().tolist() == [r if r <= CLASSES else -1 for r in labels] + [CLASSES, CLASSES]
+        for t in range(T - 1, -1, -1):
+            chk(pkg, L.bla_unet_forward_f32(h, None, x2.ptr, temb.ptr, None))
+            chk(pkg, L.bla_diffusion_guided_step_f32(d, None, x2.ptr, x2.ptr + 4 * n * F, out, out + 4 * n * F, s, n, F, t, 5, dim, temb.ptr, dtab.ptr, CLASSES, rows.ptr))
+        assert np.array_equal(x2.numpy()[:n], want), labels
     chk(pkg, L.bla_diffusion_destroy(d)); chk(pkg, L.bla_unet_destroy(h))
     # an odd model batch has no halves
     h3, _ = unet_build(pkg, CFG, 3)
