@@ -682,6 +682,19 @@ const char* bla_gemm_last_kernel(void) { return g_last_kernel; }
 
 namespace {
 struct WskPlan { GemmArgs a; bool akc, bkc, valid; };
+
+void name_wsk_launch(const GemmArgs& a, bool akc, bool bkc, bool avec, bool bvec) {
+	snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_f32_wsk%dx%d_%c%c_%s%s_ksplit%d", a.wsk_tile, a.wsk_tile, akc ? 'n' : 't', bkc ? 't' : 'n',
+	         avec ? "v" : "s", bvec ? "v" : "s", a.splits);
+}
+
+// A planned product (un-split, 16-byte loads on both operands) that ends up with no partner for a shared launch: launched by itself, and named
+// exactly as bla_gemm_f32 would have named it -- bla_gemm_last_kernel() then speaks of this call, not of an earlier one or of a sibling product.
+hipError_t launch_planned(const WskPlan& pl, hipStream_t s) {
+	hipError_t e = launch_wsk(pl.a, pl.akc, pl.bkc, true, true, dim3((unsigned)(pl.a.tiles_m * pl.a.tiles_n), 1), s);
+	if (e == hipSuccess) name_wsk_launch(pl.a, pl.akc, pl.bkc, true, true);
+	return e;
+}
 }
 
 // plan != nullptr: a product that resolves to the un-split, fully vectorised wave-split-K kernel is NOT launched but handed
@@ -820,8 +833,7 @@ static bla_status gemm_impl(void* stream, int transa, int transb, int m, int n, 
 		if (plan && ksplit == 1 && avec && bvec) { plan->a = a; plan->akc = akc; plan->bkc = bkc; plan->valid = true; return BLA_OK; }
 		hipError_t e = launch_wsk(a, akc, bkc, avec, bvec, grid, s);
 		if (e != hipSuccess) return hip_fail(e, "gemm_f32_wsk_kernel launch");
-		snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_f32_wsk%dx%d_%c%c_%s%s_ksplit%d", tile, tile, transa ? 't' : 'n', transb ? 't' : 'n',
-		         avec ? "v" : "s", bvec ? "v" : "s", ksplit);
+		name_wsk_launch(a, akc, bkc, avec, bvec);
 		return BLA_OK;
 	}
 	BLA_REQUIRE(!a.softmax_grad || cfg == 6, BLA_ERR_INVALID, "fused softmax is only available on the wave-split-K config (6)");
@@ -956,8 +968,8 @@ bla_status bla::gemm_pair_with_hook(void* stream, const bla_gemm_desc* p, const 
 		snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_f32_wsk_pair_%c%c+%c%c_%dx%d+%dx%d", pp.akc ? 'n' : 't', pp.bkc ? 't' : 'n', pq.akc ? 'n' : 't',
 		         pq.bkc ? 't' : 'n', tp, pp.a.wsk_tile, tq, pq.a.wsk_tile);
 	} else {
-		if (pp.valid) e = launch_wsk(pp.a, pp.akc, pp.bkc, true, true, dim3((unsigned)tp, 1), s);
-		if (e == hipSuccess && pq.valid) e = launch_wsk(pq.a, pq.akc, pq.bkc, true, true, dim3((unsigned)tq, 1), s);
+		if (pp.valid) e = launch_planned(pp, s);
+		if (e == hipSuccess && pq.valid) e = launch_planned(pq, s);
 	}
 	if (e != hipSuccess) return hip_fail(e, "gemm_f32_wsk pair launch");
 	return BLA_OK;
@@ -1040,7 +1052,7 @@ bla_status bla_gemm_group_f32(void* stream, const bla_gemm_desc* d, int count) {
 		snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_f32_wsk_triple_nt_%dx%d+%dx%d+%dx%d", t1, pl[0].a.wsk_tile, t2 - t1, pl[1].a.wsk_tile, t3 - t2, pl[2].a.wsk_tile);
 	} else {
 		for (int i = 0; i < 3 && e == hipSuccess; i++)
-			if (pl[i].valid) e = launch_wsk(pl[i].a, pl[i].akc, pl[i].bkc, true, true, dim3((unsigned)(pl[i].a.tiles_m * pl[i].a.tiles_n), 1), s);
+			if (pl[i].valid) e = launch_planned(pl[i], s);
 	}
 	if (e != hipSuccess) return hip_fail(e, "gemm_f32_wsk group launch");
 	return BLA_OK;

@@ -309,9 +309,24 @@ def gemm_pair(p, q, stream=None):
     check(lib().bla_gemm_pair_f32(stream, C.byref(p), C.byref(q)))
 
 
+def gemm_group(descs, stream=None):
+    """bla_gemm_group_f32 on a sequence of GemmDesc (their epilogues are kept alive by the caller)."""
+    arr = (GemmDesc * max(len(descs), 1))(*descs)
+    check(lib().bla_gemm_group_f32(stream, arr, len(descs)))
+
+
+def gemm_batched(a, b, c, batch, m, n, k, lda, stride_a, ldb, stride_b, ldc, stride_c, transa=False, transb=False,
+                 epilogue=None, stride_pre=0, stream=None):
+    """bla_gemm_batched_f32: `batch` products op(A_i) op(B_i) -> C_i, set i at base + i * stride (in elements; 0 = shared operand)."""
+    check(lib().bla_gemm_batched_f32(stream, int(transa), int(transb), m, n, k, _ptr(a), lda, stride_a, _ptr(b), ldb, stride_b,
+                                     _ptr(c), ldc, stride_c, batch, C.byref(epilogue) if epilogue is not None else None, stride_pre))
+    return c
+
+
 def gemm(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, bias_row=None, bias_col=None, pre_act=None,
          act=ACT_NONE, relu_mask=None, stream=None, m=None, n=None, k=None, lda=None, ldb=None, ldc=None,
-         row_sum_a=None, softmax_y=None, softmax_scale=0.0, softmax_grad=None, row_sum_alpha=0.0, row_sum_beta=0.0):
+         row_sum_a=None, softmax_y=None, softmax_scale=0.0, softmax_grad=None, row_sum_alpha=0.0, row_sum_beta=0.0,
+         softmax_loss_acc=None, softmax_correct_acc=None):
     """C = epilogue(alpha * op(A) op(B)) on device arrays; shapes default to the arrays' own."""
     if m is None:
         m = a.shape[1] if transa else a.shape[0]
@@ -324,7 +339,7 @@ def gemm(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, bias_row=None
         raise BlaError(2, f"inner dimensions differ: {k} vs {kb}")
     ep = Epilogue(alpha, beta, _ptr(bias_row), _ptr(bias_col), _ptr(pre_act), pre_act.ld if pre_act is not None else 0,
                   act, _ptr(relu_mask), relu_mask.ld if relu_mask is not None else 0, _ptr(row_sum_a), _ptr(softmax_y),
-                  softmax_scale, _ptr(softmax_grad), row_sum_alpha, row_sum_beta)
+                  softmax_scale, _ptr(softmax_grad), row_sum_alpha, row_sum_beta, _ptr(softmax_loss_acc), _ptr(softmax_correct_acc))
     check(lib().bla_gemm_f32(stream, int(transa), int(transb), m, n, k, _ptr(a), lda or a.ld, _ptr(b), ldb or b.ld,
                              _ptr(c), ldc or c.ld, C.byref(ep)))
     return c

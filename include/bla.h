@@ -182,7 +182,8 @@ BLA_API bla_status bla_gemm_group_f32(void* stream, const bla_gemm_desc* descs, 
  * per CU).  A forced configuration that cannot take the call fails with
  * BLA_ERR_INVALID; the automatic choice never does. */
 BLA_API bla_status bla_gemm_set_config(int config, int split_k);
-/* Name of the kernel variant the last bla_gemm_f32 call launched (for profiles/). */
+/* Name of the kernel variant the last bla_gemm_f32 / _pair / _group / _batched call launched (for profiles/); where such a call made several
+ * launches, the last one it issued (products of a pair or group that wait for a shared launch and then go alone are issued after the others). */
 BLA_API const char* bla_gemm_last_kernel(void);
 
 /* ---- elementwise / broadcast / transpose / reductions: lib/matrix.c:59-205, lib/util.c:7-55 -------------
