@@ -680,6 +680,8 @@ const char* bla_gemm_last_kernel(void) { return g_last_kernel; }
 
 }  // extern "C"
 
+void bla::gemm_note_last_kernel(const char* name) { snprintf(g_last_kernel, sizeof(g_last_kernel), "%s", name); }
+
 namespace {
 struct WskPlan { GemmArgs a; bool akc, bkc, valid; };
 

@@ -1,0 +1,412 @@
+// bla_gemm_bf16.hip -- bf16 operands, fp32 accumulation (include/bla.h, "mixed precision"): the conversions, the 16-bit transpose, the product.
+//
+// The fast kernel (gemm_bf16_nt_kernel) is the plain LDS-DMA structure: a 128 x 128 output tile per 256-thread workgroup, 64-deep K slabs, one 32 KiB
+// LDS image, two barriers per slab (stage, wait, barrier, multiply, barrier); several workgroups per CU overlap one another's staging.
+//   * Both operands K-contiguous (A [m][k], B [n][k]).  A slab of an operand is 128 rows x 128 bytes; wave w's i-th global_load_lds_dwordx4 fills the 1 KiB
+//     piece (4w + i) = 8 rows, lane l -> row l >> 3, 16-byte chunk l & 7.  The LDS image stays lane-linear (the DMA writes base + 16 * lane); the swizzle is
+//     on the SOURCE address: LDS chunk c of row r holds global chunk c ^ ((r >> 1) & 7), and the fragment reads apply the same XOR.  With 128-byte rows two
+//     rows share a 256-byte bank row, so the 16 rows a ds_read_b128 lane group reads land on 16 different 16-byte slots.
+//   * Edges: a lane whose row is past m (n) or whose chunk is past k fetches from 256 bytes of zeros the context keeps (zero_word()); no address outside
+//     the operands is ever formed into a load.  k % 8 == 0 makes every chunk wholly inside or wholly outside.  Stores are bounds-checked.
+//   * v_mfma_f32_32x32x16_bf16: lane l holds A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][col l & 31], j < 8 -- one 16-byte chunk each;
+//     C/D: col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).  Each wave owns 64 x 64 = 2 x 2 such tiles.
+//   * Workgroup -> tile: XCD-aware (the 8 XCDs take contiguous chunks of the tile order), then groups of 8 tile rows walked column by column.
+#include "bla_internal.h"
+
+namespace bla {
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
+
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
+	uint32_t u = __float_as_uint(f);
+	if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // NaN stays NaN
+	return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
+
+struct Bf16Args {
+	const uint16_t* A; const uint16_t* B; void* C; const void* zero;
+	int m, n, k, lda, ldb, ldc, tiles_m, tiles_n;
+	float alpha, beta;
+	const float* bias_row; const float* bias_col;
+	int relu;
+	long sa_r, sa_k, sb_k, sb_c;   // general kernel: element strides of op(A)[r][kk] and op(B)[kk][c]
+};
+
+template <bool C_BF16>
+__device__ __forceinline__ void epilogue_store(const Bf16Args& p, int r, int c, float acc) {
+	float v = p.alpha * acc;
+	if (p.bias_row) v += p.bias_row[r];
+	if (p.bias_col) v += p.bias_col[c];
+	if (p.relu) v = v < 0.f ? 0.f : v;
+	const size_t at = (size_t)r * p.ldc + c;
+	if (C_BF16) {
+		uint16_t* C = (uint16_t*)p.C;
+		if (p.beta != 0.f) v += p.beta * bf16_to_f32(C[at]);
+		C[at] = f32_to_bf16_rne(v);
+	} else {
+		float* C = (float*)p.C;
+		if (p.beta != 0.f) v += p.beta * C[at];
+		C[at] = v;
+	}
+}
+
+__device__ __forceinline__ int xcd_tile(int bid, int nwg) {   // bijective for any count
+	int q = nwg >> 3, r = nwg & 7, x = bid & 7, i = bid >> 3;
+	return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
+}
+
+constexpr int BM = 128, BN = 128, BK = 64, SLAB_BYTES = BM * BK * 2;
+
+template <bool C_BF16>
+__global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(Bf16Args p) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // [A slab 16 KiB][B slab 16 KiB]
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	int pid = xcd_tile(blockIdx.x, p.tiles_m * p.tiles_n);
+	const int gsz = 8 * p.tiles_n, grp = pid / gsz, first = grp * 8, gm = min(p.tiles_m - first, 8);
+	const int tm = first + (pid % gsz) % gm, tn = (pid % gsz) / gm;
+	const int row0 = tm * BM, col0 = tn * BN;
+
+	const uint16_t* pa[4]; const uint16_t* pb[4];
+	int kc[4];   // first k of the chunk this lane fetches for piece i (the same for A and B)
+	bool oka[4], okb[4];
+#pragma unroll
+	for (int i = 0; i < 4; ++i) {
+		const int row = (wave * 4 + i) * 8 + (lane >> 3);
+		const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+		kc[i] = chunk * 8;
+		oka[i] = row0 + row < p.m;
+		okb[i] = col0 + row < p.n;
+		pa[i] = p.A + (size_t)(oka[i] ? row0 + row : 0) * p.lda + kc[i];
+		pb[i] = p.B + (size_t)(okb[i] ? col0 + row : 0) * p.ldb + kc[i];
+	}
+	f32x16 acc[2][2];
+#pragma unroll
+	for (int i = 0; i < 2; ++i)
+#pragma unroll
+		for (int j = 0; j < 2; ++j)
+#pragma unroll
+			for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+	const int wm = wave >> 1, wn = wave & 1, fr = lane & 31, fh = lane >> 5;
+	for (int kb = 0; kb < p.k; kb += BK) {
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			const bool in = kb + kc[i] < p.k;
+			const void* sa = (oka[i] && in) ? (const void*)(pa[i] + kb) : p.zero;
+			const void* sb = (okb[i] && in) ? (const void*)(pb[i] + kb) : p.zero;
+			__builtin_amdgcn_global_load_lds((gbl_ptr_t)sa, (lds_ptr_t)(lds + (wave * 4 + i) * 1024), 16, 0, 0);
+			__builtin_amdgcn_global_load_lds((gbl_ptr_t)sb, (lds_ptr_t)(lds + SLAB_BYTES + (wave * 4 + i) * 1024), 16, 0, 0);
+		}
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		__syncthreads();
+#pragma unroll
+		for (int s = 0; s < BK / 16; ++s) {
+			bf16x8 fa[2], fb[2];
+			const int g = 2 * s + fh;
+#pragma unroll
+			for (int i = 0; i < 2; ++i) {
+				const int ra = wm * 64 + i * 32 + fr, rb = wn * 64 + i * 32 + fr;
+				fa[i] = *(const bf16x8*)(lds + ra * 128 + ((g ^ ((ra >> 1) & 7)) << 4));
+				fb[i] = *(const bf16x8*)(lds + SLAB_BYTES + rb * 128 + ((g ^ ((rb >> 1) & 7)) << 4));
+			}
+#pragma unroll
+			for (int i = 0; i < 2; ++i)
+#pragma unroll
+				for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+		}
+		__syncthreads();
+	}
+#pragma unroll
+	for (int i = 0; i < 2; ++i)
+#pragma unroll
+		for (int j = 0; j < 2; ++j) {
+			const int c = col0 + wn * 64 + j * 32 + fr;
+#pragma unroll
+			for (int r = 0; r < 16; ++r) {
+				const int row = row0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+				if (row < p.m && c < p.n) epilogue_store<C_BF16>(p, row, c, acc[i][j][r]);
+			}
+		}
+}
+
+// Any shape, pitch, alignment and layout: one output element per thread, 2-byte loads, a k-ascending fp32 fma chain (products of bf16 values are exact).
+template <bool C_BF16>
+__global__ __launch_bounds__(256) void gemm_bf16_general_kernel(Bf16Args p) {
+	const int c = blockIdx.x * 16 + (threadIdx.x & 15), r = blockIdx.y * 16 + (threadIdx.x >> 4);
+	if (r >= p.m || c >= p.n) return;
+	const uint16_t* a = p.A + (size_t)r * p.sa_r;
+	const uint16_t* b = p.B + (size_t)c * p.sb_c;
+	float acc = 0.f;
+	for (int kk = 0; kk < p.k; ++kk) acc = fmaf(bf16_to_f32(a[(size_t)kk * p.sa_k]), bf16_to_f32(b[(size_t)kk * p.sb_k]), acc);
+	epilogue_store<C_BF16>(p, r, c, acc);
+}
+
+// ---- conversions: one thread per 8 consecutive elements of a row -----------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* src, long ld_src, uint16_t* dst, long ld_dst, int rows, int cols, int vec) {
+	const int chunks = (cols + 7) >> 3;
+	const long id = (long)blockIdx.x * 256 + threadIdx.x;
+	if (id >= (long)rows * chunks) return;
+	const int r = (int)(id / chunks), c0 = (int)(id % chunks) * 8;
+	const float* s = src + r * ld_src + c0;
+	uint16_t* d = dst + r * ld_dst + c0;
+	if (vec && c0 + 8 <= cols) {
+		const float4 x = *(const float4*)s, y = *(const float4*)(s + 4);
+		uint4 o;
+		o.x = f32_to_bf16_rne(x.x) | ((uint32_t)f32_to_bf16_rne(x.y) << 16);
+		o.y = f32_to_bf16_rne(x.z) | ((uint32_t)f32_to_bf16_rne(x.w) << 16);
+		o.z = f32_to_bf16_rne(y.x) | ((uint32_t)f32_to_bf16_rne(y.y) << 16);
+		o.w = f32_to_bf16_rne(y.z) | ((uint32_t)f32_to_bf16_rne(y.w) << 16);
+		*(uint4*)d = o;
+	} else {
+		for (int j = 0; j < 8 && c0 + j < cols; ++j) d[j] = f32_to_bf16_rne(s[j]);
+	}
+}
+
+__global__ __launch_bounds__(256) void bf16_to_f32_kernel(const uint16_t* src, long ld_src, float* dst, long ld_dst, int rows, int cols, int vec) {
+	const int chunks = (cols + 7) >> 3;
+	const long id = (long)blockIdx.x * 256 + threadIdx.x;
+	if (id >= (long)rows * chunks) return;
+	const int r = (int)(id / chunks), c0 = (int)(id % chunks) * 8;
+	const uint16_t* s = src + r * ld_src + c0;
+	float* d = dst + r * ld_dst + c0;
+	if (vec && c0 + 8 <= cols) {
+		const uint4 x = *(const uint4*)s;
+		*(float4*)d = make_float4(__uint_as_float(x.x << 16), __uint_as_float(x.x & 0xffff0000u), __uint_as_float(x.y << 16), __uint_as_float(x.y & 0xffff0000u));
+		*(float4*)(d + 4) = make_float4(__uint_as_float(x.z << 16), __uint_as_float(x.z & 0xffff0000u), __uint_as_float(x.w << 16), __uint_as_float(x.w & 0xffff0000u));
+	} else {
+		for (int j = 0; j < 8 && c0 + j < cols; ++j) d[j] = bf16_to_f32(s[j]);
+	}
+}
+
+// ---- 16-bit transpose: 64 x 64 tiles through LDS; a thread moves two 8-element chunks in, two out -------------------------------------------------
+constexpr int TT = 64, TP = TT + 8;   // rows of 144 bytes: 16-byte aligned chunks, and a column walk that moves 36 banks per row
+__global__ __launch_bounds__(256) void transpose_b16_kernel(const uint16_t* src, long ld_src, uint16_t* dst, long ld_dst, int rows, int cols, int vec_src, int vec_dst) {
+	__shared__ __attribute__((aligned(16))) uint16_t tile[TT][TP];
+	const int r0 = blockIdx.y * TT, c0 = blockIdx.x * TT;
+#pragma unroll
+	for (int q = 0; q < 2; ++q) {
+		const int id = threadIdx.x + q * 256, tr = id >> 3, tc = (id & 7) * 8;
+		const int r = r0 + tr, c = c0 + tc;
+		if (r < rows && c < cols) {
+			const uint16_t* s = src + r * ld_src + c;
+			if (vec_src && c + 8 <= cols) *(uint4*)&tile[tr][tc] = *(const uint4*)s;
+			else for (int j = 0; j < 8 && c + j < cols; ++j) tile[tr][tc + j] = s[j];
+		}
+	}
+	__syncthreads();
+#pragma unroll
+	for (int q = 0; q < 2; ++q) {
+		const int id = threadIdx.x + q * 256, tc = id >> 3, tr = (id & 7) * 8;   // output row = source column c0 + tc, output columns = source rows r0 + tr ...
+		const int c = c0 + tc, r = r0 + tr;
+		if (c < cols && r < rows) {
+			uint16_t* d = dst + c * ld_dst + r;
+			if (vec_dst && r + 8 <= rows) {
+				uint4 o;
+				o.x = tile[tr + 0][tc] | ((uint32_t)tile[tr + 1][tc] << 16);
+				o.y = tile[tr + 2][tc] | ((uint32_t)tile[tr + 3][tc] << 16);
+				o.z = tile[tr + 4][tc] | ((uint32_t)tile[tr + 5][tc] << 16);
+				o.w = tile[tr + 6][tc] | ((uint32_t)tile[tr + 7][tc] << 16);
+				*(uint4*)d = o;
+			} else for (int j = 0; j < 8 && r + j < rows; ++j) d[j] = tile[tr + j][tc];
+		}
+	}
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline size_t round_up(size_t x, size_t to) { return (x + to - 1) / to * to; }
+
+bla_status window_args(const void* src, long ld_src, const void* dst, long ld_dst, int rows, int cols, const char* who) {
+	BLA_REQUIRE(rows >= 0 && cols >= 0, BLA_ERR_INVALID, "%s: negative extent %d x %d", who, rows, cols);
+	if (rows == 0 || cols == 0) return BLA_OK;
+	BLA_REQUIRE(src && dst, BLA_ERR_INVALID, "%s: NULL pointer", who);
+	BLA_REQUIRE(ld_src >= cols, BLA_ERR_INVALID, "%s: ld_src %ld < cols %d", who, ld_src, cols);
+	return BLA_OK;
+}
+
+bla_status launch_f32_to_bf16(hipStream_t s, const float* src, int ld_src, uint16_t* dst, int ld_dst, int rows, int cols) {
+	const long n = (long)rows * ((cols + 7) / 8);
+	if (n == 0) return BLA_OK;
+	const int vec = aligned16(src) && ld_src % 4 == 0 && aligned16(dst) && ld_dst % 8 == 0;
+	hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, (long)ld_src, dst, (long)ld_dst, rows, cols, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status launch_transpose(hipStream_t s, const uint16_t* src, int ld_src, uint16_t* dst, int ld_dst, int rows, int cols) {
+	if (rows == 0 || cols == 0) return BLA_OK;
+	const int vs = aligned16(src) && ld_src % 8 == 0, vd = aligned16(dst) && ld_dst % 8 == 0;
+	BLA_REQUIRE((rows + TT - 1) / TT <= 65535, BLA_ERR_INVALID, "bla_transpose_b16: %d rows exceed the grid", rows);
+	hipLaunchKernelGGL(transpose_b16_kernel, dim3((cols + TT - 1) / TT, (rows + TT - 1) / TT), dim3(256), 0, s, src, (long)ld_src, dst, (long)ld_dst, rows, cols, vs, vd);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+// the fields of the epilogue a bf16 product honours; everything else must be off.  A pure argument check: it runs before the device is asked for.
+bla_status check_epilogue(const bla_gemm_epilogue* ep) {
+	if (!ep) return BLA_OK;
+	BLA_REQUIRE(!ep->pre_act && ep->ld_pre == 0 && !ep->relu_mask && ep->ld_mask == 0 && !ep->row_sum_a && !ep->softmax_y && ep->softmax_scale == 0.f &&
+	            !ep->softmax_grad && ep->row_sum_alpha == 0.f && ep->row_sum_beta == 0.f && !ep->softmax_loss_acc && !ep->softmax_correct_acc,
+	            BLA_ERR_INVALID, "bla_gemm_bf16: the epilogue sets a field other than alpha, beta, bias_row, bias_col, act");
+	BLA_REQUIRE(ep->act == BLA_ACT_NONE || ep->act == BLA_ACT_RELU, BLA_ERR_INVALID, "bla_gemm_bf16: act %d", ep->act);
+	return BLA_OK;
+}
+
+bla_status check_product(int m, int n, int k, const void* A, int lda, int transa, const void* B, int ldb, int transb, const void* C, int ldc) {
+	BLA_REQUIRE(m >= 0 && n >= 0 && k >= 0, BLA_ERR_INVALID, "bla_gemm_bf16: negative extent m %d n %d k %d", m, n, k);
+	if (m == 0 || n == 0) return BLA_OK;
+	BLA_REQUIRE(C && (k == 0 || (A && B)), BLA_ERR_INVALID, "bla_gemm_bf16: NULL operand");
+	BLA_REQUIRE(lda >= (transa ? m : k) && ldb >= (transb ? k : n) && ldc >= n, BLA_ERR_INVALID, "bla_gemm_bf16: pitch too small (lda %d ldb %d ldc %d)", lda, ldb, ldc);
+	return BLA_OK;
+}
+
+bool fast_path(int k, const void* A, int lda, const void* B, int ldb) {
+	return k > 0 && k % 8 == 0 && aligned16(A) && aligned16(B) && lda % 8 == 0 && ldb % 8 == 0;
+}
+// bytes of the transposed copies a fast-path product puts into the workspace
+size_t tcopy_bytes(bool fast, int transa, int transb, int m, int n, int k) {
+	if (m == 0 || n == 0 || !fast) return 0;
+	return (transa ? round_up((size_t)m * k * 2, 256) : 0) + (!transb ? round_up((size_t)n * k * 2, 256) : 0);
+}
+
+// the product itself; ws holds tcopy_bytes() bytes (16-byte aligned)
+bla_status gemm_bf16_launch(hipStream_t s, int transa, int transb, int m, int n, int k, const uint16_t* A, int lda, const uint16_t* B, int ldb, void* C, int ldc,
+                            int c_type, const bla_gemm_epilogue* ep, unsigned char* ws) {
+	if (m == 0 || n == 0) return BLA_OK;
+	Bf16Args a{};
+	a.C = C; a.m = m; a.n = n; a.k = k; a.ldc = ldc;
+	a.alpha = ep ? ep->alpha : 1.f; a.beta = ep ? ep->beta : 0.f;
+	a.bias_row = ep ? ep->bias_row : nullptr; a.bias_col = ep ? ep->bias_col : nullptr;
+	a.relu = ep && ep->act == BLA_ACT_RELU;
+	char name[96];
+	const char* lay = transa ? (transb ? "tt" : "tn") : (transb ? "nt" : "nn");
+	const char* ct = c_type == BLA_C_BF16 ? "bf16" : "f32";
+	if (fast_path(k, A, lda, B, ldb)) {
+		if (transa) {   // A stored k x m -> m x k
+			BLA_REQUIRE(ws, BLA_ERR_INVALID, "bla_gemm_bf16: no workspace");
+			bla_status st = launch_transpose(s, A, lda, (uint16_t*)ws, k, k, m);
+			if (st != BLA_OK) return st;
+			A = (const uint16_t*)ws; lda = k; ws += round_up((size_t)m * k * 2, 256);
+		}
+		if (!transb) {  // B stored k x n -> n x k
+			BLA_REQUIRE(ws, BLA_ERR_INVALID, "bla_gemm_bf16: no workspace");
+			bla_status st = launch_transpose(s, B, ldb, (uint16_t*)ws, k, k, n);
+			if (st != BLA_OK) return st;
+			B = (const uint16_t*)ws; ldb = k;
+		}
+		a.A = A; a.B = B; a.lda = lda; a.ldb = ldb; a.zero = zero_word();
+		a.tiles_m = (m + BM - 1) / BM; a.tiles_n = (n + BN - 1) / BN;
+		const dim3 grid((unsigned)((long)a.tiles_m * a.tiles_n));
+		if (c_type == BLA_C_BF16) hipLaunchKernelGGL(gemm_bf16_nt_kernel<true>, grid, dim3(256), 2 * SLAB_BYTES, s, a);
+		else hipLaunchKernelGGL(gemm_bf16_nt_kernel<false>, grid, dim3(256), 2 * SLAB_BYTES, s, a);
+		BLA_HIP(hipGetLastError());
+		snprintf(name, sizeof name, "gemm_bf16_mfma128x128x64_%s_%s%s%s", lay, ct, transa ? "_tcopyA" : "", !transb ? "_tcopyB" : "");
+	} else {
+		a.A = A; a.B = B;
+		a.sa_r = transa ? 1 : lda; a.sa_k = transa ? lda : 1;
+		a.sb_k = transb ? 1 : ldb; a.sb_c = transb ? ldb : 1;
+		BLA_REQUIRE((m + 15) / 16 <= 65535, BLA_ERR_INVALID, "bla_gemm_bf16: m %d exceeds the general kernel's grid", m);
+		const dim3 grid((n + 15) / 16, (m + 15) / 16);
+		if (c_type == BLA_C_BF16) hipLaunchKernelGGL(gemm_bf16_general_kernel<true>, grid, dim3(256), 0, s, a);
+		else hipLaunchKernelGGL(gemm_bf16_general_kernel<false>, grid, dim3(256), 0, s, a);
+		BLA_HIP(hipGetLastError());
+		snprintf(name, sizeof name, "gemm_bf16_general_%s_%s", lay, ct);
+	}
+	gemm_note_last_kernel(name);
+	return BLA_OK;
+}
+
+}  // namespace
+}  // namespace bla
+
+using namespace bla;
+
+extern "C" {
+
+bla_status bla_f32_to_bf16(void* stream, const float* d_src, int ld_src, uint16_t* d_dst, int ld_dst, int rows, int cols) {
+	bla_status st = require_ready();
+	if (st != BLA_OK) return st;
+	st = window_args(d_src, ld_src, d_dst, ld_dst, rows, cols, "bla_f32_to_bf16");
+	if (st != BLA_OK) return st;
+	BLA_REQUIRE(ld_dst >= cols, BLA_ERR_INVALID, "bla_f32_to_bf16: ld_dst %d < cols %d", ld_dst, cols);
+	return launch_f32_to_bf16(pick_stream(stream), d_src, ld_src, d_dst, ld_dst, rows, cols);
+}
+
+bla_status bla_bf16_to_f32(void* stream, const uint16_t* d_src, int ld_src, float* d_dst, int ld_dst, int rows, int cols) {
+	bla_status st = require_ready();
+	if (st != BLA_OK) return st;
+	st = window_args(d_src, ld_src, d_dst, ld_dst, rows, cols, "bla_bf16_to_f32");
+	if (st != BLA_OK) return st;
+	BLA_REQUIRE(ld_dst >= cols, BLA_ERR_INVALID, "bla_bf16_to_f32: ld_dst %d < cols %d", ld_dst, cols);
+	const long n = (long)rows * ((cols + 7) / 8);
+	if (n == 0) return BLA_OK;
+	const int vec = aligned16(d_src) && ld_src % 8 == 0 && aligned16(d_dst) && ld_dst % 4 == 0;
+	hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, pick_stream(stream), d_src, (long)ld_src, d_dst, (long)ld_dst, rows, cols, vec);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status bla_transpose_b16(void* stream, const uint16_t* d_src, int ld_src, uint16_t* d_dst, int ld_dst, int rows, int cols) {
+	bla_status st = require_ready();
+	if (st != BLA_OK) return st;
+	st = window_args(d_src, ld_src, d_dst, ld_dst, rows, cols, "bla_transpose_b16");
+	if (st != BLA_OK) return st;
+	BLA_REQUIRE(ld_dst >= rows, BLA_ERR_INVALID, "bla_transpose_b16: ld_dst %d < rows %d", ld_dst, rows);
+	return launch_transpose(pick_stream(stream), d_src, ld_src, d_dst, ld_dst, rows, cols);
+}
+
+bla_status bla_gemm_bf16(void* stream, int transa, int transb, int m, int n, int k, const uint16_t* d_a, int lda, const uint16_t* d_b, int ldb,
+                         void* d_c, int ldc, int c_type, const bla_gemm_epilogue* ep) {
+	bla_status st = check_epilogue(ep);
+	if (st != BLA_OK) return st;
+	BLA_REQUIRE(c_type == BLA_C_F32 || c_type == BLA_C_BF16, BLA_ERR_INVALID, "bla_gemm_bf16: c_type %d", c_type);
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	transa = transa != 0; transb = transb != 0;
+	st = check_product(m, n, k, d_a, lda, transa, d_b, ldb, transb, d_c, ldc);
+	if (st != BLA_OK) return st;
+	void* ws = nullptr;
+	const size_t need = tcopy_bytes(fast_path(k, d_a, lda, d_b, ldb), transa, transb, m, n, k);
+	if (need) {
+		st = ensure_workspace(need, &ws);
+		if (st != BLA_OK) return st;
+	}
+	return gemm_bf16_launch(pick_stream(stream), transa, transb, m, n, k, d_a, lda, d_b, ldb, d_c, ldc, c_type, ep, (unsigned char*)ws);
+}
+
+bla_status bla_gemm_f32_as_bf16(void* stream, int transa, int transb, int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb,
+                                float* d_c, int ldc, const bla_gemm_epilogue* ep) {
+	bla_status st = check_epilogue(ep);
+	if (st != BLA_OK) return st;
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	transa = transa != 0; transb = transb != 0;
+	st = check_product(m, n, k, d_a, lda, transa, d_b, ldb, transb, d_c, ldc);
+	if (st != BLA_OK) return st;
+	if (m == 0 || n == 0) return BLA_OK;
+	// the bf16 operands keep their layout, at a pitch rounded up to 8 elements, in front of the transposed copies the product may add
+	const int ar = transa ? k : m, ac = transa ? m : k, br = transb ? n : k, bc = transb ? k : n;
+	const int la = (int)round_up((size_t)ac, 8), lb = (int)round_up((size_t)bc, 8);
+	const size_t a_bytes = round_up((size_t)ar * la * 2, 256), b_bytes = round_up((size_t)br * lb * 2, 256);
+	// the workspace is 256-byte aligned and both pitches are multiples of 8: the product takes the fast path whenever k allows it
+	void* ws = nullptr;
+	st = ensure_workspace(a_bytes + b_bytes + tcopy_bytes(k > 0 && k % 8 == 0, transa, transb, m, n, k), &ws);
+	if (st != BLA_OK) return st;
+	unsigned char* base = (unsigned char*)ws;
+	uint16_t* a16 = (uint16_t*)base;
+	uint16_t* b16 = (uint16_t*)(base + a_bytes);
+	hipStream_t s = pick_stream(stream);
+	if (k > 0) {
+		st = launch_f32_to_bf16(s, d_a, lda, a16, la, ar, ac);
+		if (st != BLA_OK) return st;
+		st = launch_f32_to_bf16(s, d_b, ldb, b16, lb, br, bc);
+		if (st != BLA_OK) return st;
+	}
+	return gemm_bf16_launch(s, transa, transb, m, n, k, a16, la, b16, lb, d_c, ldc, BLA_C_F32, ep, base + a_bytes + b_bytes);
+}
+
+}  // extern "C"

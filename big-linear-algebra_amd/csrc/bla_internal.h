@@ -109,6 +109,9 @@ bla_status thin_conv_forward(hipStream_t s, const float* x, const float* kern, f
                              const float* ep_bias, int ep_bias_stride, const float* ep_add, float* ep_out2);
 bla_status thin_conv_wgrad(hipStream_t s, const float* del_y, const float* x, float* del_kern, int batch, int h, int w, int k, int c_in, int f_n, int pt, int pl);
 
+// bla_gemm.hip: what bla_gemm_last_kernel() answers; the bf16 products (bla_gemm_bf16.hip) record their variant here
+void gemm_note_last_kernel(const char* name);
+
 // bla_gemm_thin.hip: batched products with a short contraction (k <= 64, a multiple of 8; m, n multiples of 32) and a large output, one wave per
 // 32 x (32..128) block straight from global memory; up to three (A, B) pairs accumulate before the one store.  Strides in floats per batch index.
 struct ThinPart { const float* A; const float* B; long sa, sb; int lda, ldb; };

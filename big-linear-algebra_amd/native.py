@@ -9,6 +9,7 @@ _SO = os.path.join(_HERE, "csrc", "libbla_hip.so")
 _lib = None
 
 ACT_NONE, ACT_RELU = 0, 1
+C_F32, C_BF16 = 0, 1   # bla_gemm_bf16's c_type
 
 
 class BlaError(RuntimeError):
@@ -62,6 +63,10 @@ SIGNATURES = {
     "bla_event_elapsed_ms": (_I, [_VP, _VP, C.POINTER(_F)]),
     "bla_gemm_f32": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, C.POINTER(Epilogue)]),
     "bla_gemm_set_config": (_I, [_I, _I]), "bla_gemm_last_kernel": (C.c_char_p, []),
+    "bla_f32_to_bf16": (_I, [_VP, _VP, _I, _VP, _I, _I, _I]), "bla_bf16_to_f32": (_I, [_VP, _VP, _I, _VP, _I, _I, _I]),
+    "bla_transpose_b16": (_I, [_VP, _VP, _I, _VP, _I, _I, _I]),
+    "bla_gemm_bf16": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, C.POINTER(Epilogue)]),
+    "bla_gemm_f32_as_bf16": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, C.POINTER(Epilogue)]),
     "bla_scale_f32": (_I, [_VP, _VP, _SZ, _F]), "bla_add_f32": (_I, [_VP, _VP, _VP, _SZ]),
     "bla_hadamard_f32": (_I, [_VP, _VP, _VP, _SZ]), "bla_axpy_f32": (_I, [_VP, _VP, _VP, _F, _SZ]),
     "bla_relu_f32": (_I, [_VP, _VP, _SZ]), "bla_relu_ddx_f32": (_I, [_VP, _VP, _SZ]),
@@ -342,4 +347,33 @@ def gemm(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, bias_row=None
                   softmax_scale, _ptr(softmax_grad), row_sum_alpha, row_sum_beta, _ptr(softmax_loss_acc), _ptr(softmax_correct_acc))
     check(lib().bla_gemm_f32(stream, int(transa), int(transb), m, n, k, _ptr(a), lda or a.ld, _ptr(b), ldb or b.ld,
                              _ptr(c), ldc or c.ld, C.byref(ep)))
+    return c
+
+
+def to_bf16(a):
+    """fp32 -> bf16 bit patterns (np.uint16) on the host, round to nearest even: what bla_f32_to_bf16 computes, bit for bit."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    rne = (u.astype(np.uint64) + 0x7FFF + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint64(16)
+    return np.where(nan, (u >> np.uint32(16)) | np.uint32(0x40), rne).astype(np.uint16)
+
+
+def from_bf16(h):
+    """bf16 bit patterns -> fp32, the exact widening."""
+    return (np.ascontiguousarray(h, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def gemm_bf16(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, bias_row=None, bias_col=None, act=ACT_NONE, stream=None,
+              m=None, n=None, k=None, lda=None, ldb=None, ldc=None):
+    """C = epilogue(alpha * op(A) op(B)) with bf16 operands (np.uint16 device arrays) and fp32 accumulation; C is fp32 or bf16 by c's dtype."""
+    if m is None:
+        m = a.shape[1] if transa else a.shape[0]
+    if k is None:
+        k = a.shape[0] if transa else a.shape[1]
+    if n is None:
+        n = b.shape[0] if transb else b.shape[1]
+    ep = Epilogue(alpha=alpha, beta=beta, bias_row=_ptr(bias_row), bias_col=_ptr(bias_col), act=act)
+    c_type = C_BF16 if c.dtype == np.uint16 else C_F32
+    check(lib().bla_gemm_bf16(stream, int(transa), int(transb), m, n, k, _ptr(a), lda or a.ld, _ptr(b), ldb or b.ld, _ptr(c), ldc or c.ld,
+                              c_type, C.byref(ep)))
     return c

@@ -24,6 +24,7 @@
 #define BLA_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #if defined(BLA_BUILDING)
 #define BLA_API __attribute__((visibility("default")))
@@ -185,6 +186,45 @@ BLA_API bla_status bla_gemm_set_config(int config, int split_k);
 /* Name of the kernel variant the last bla_gemm_f32 / _pair / _group / _batched call launched (for profiles/); where such a call made several
  * launches, the last one it issued (products of a pair or group that wait for a shared launch and then go alone are issued after the others). */
 BLA_API const char* bla_gemm_last_kernel(void);
+
+/* ---- mixed precision: bf16 operands, fp32 accumulation, on the bf16 matrix instructions (csrc/bla_gemm_bf16.hip) ------------------------------
+ * A bf16 value is its 16-bit pattern in a uint16_t: the upper half of the IEEE fp32 encoding.
+ *
+ * Conversions over a 2-D window (rows x cols, pitches in elements; rows = 1 is the flat form).  fp32 -> bf16 rounds to nearest even: a NaN gives a NaN
+ * (pattern (u >> 16) | 0x40), +-inf, +-0 and subnormals keep their value (nothing is flushed), a finite value above the largest bf16 rounds to inf, and
+ * everything else is (u + 0x7FFF + ((u >> 16) & 1)) >> 16 on the fp32 bit pattern u.  bf16 -> fp32 is the exact widening u16 << 16.  Only the window is
+ * written.  16-byte accesses when bases and pitches allow them (fp32 side: 16-byte base, pitch % 4 == 0; bf16 side: 16-byte base, pitch % 8 == 0). */
+BLA_API bla_status bla_f32_to_bf16(void* stream, const float* d_src, int ld_src, uint16_t* d_dst, int ld_dst, int rows, int cols);
+BLA_API bla_status bla_bf16_to_f32(void* stream, const uint16_t* d_src, int ld_src, float* d_dst, int ld_dst, int rows, int cols);
+/* dst (cols x rows, ld_dst >= rows) = src^T for src (rows x cols, ld_src >= cols) of 16-bit elements, out of place, bit-exact: 64 x 64 tiles through
+ * LDS, 16-byte accesses on either side whose base is 16-byte aligned with a pitch that is a multiple of 8 (2-byte accesses otherwise and at the edges). */
+BLA_API bla_status bla_transpose_b16(void* stream, const uint16_t* d_src, int ld_src, uint16_t* d_dst, int ld_dst, int rows, int cols);
+
+/*   C[m x n] = epilogue( alpha * op(A)[m x k] . op(B)[k x n] ),  A and B bf16, accumulation and epilogue in fp32
+ * op(), the pitches, transa and transb mean exactly what they mean for bla_gemm_f32.  C is fp32 (BLA_C_F32: d_c is a float*) or bf16 (BLA_C_BF16: d_c is a
+ * uint16_t*, rounded to nearest even ONCE, after the whole epilogue); ldc in elements of C's type.  Of the epilogue, alpha, beta, bias_row, bias_col and act
+ * are honoured, in bla_gemm_f32's order; with beta != 0, C is read in its own type.  Any other field non-NULL or non-zero: BLA_ERR_INVALID, nothing is
+ * launched.  NULL = a plain product.  Products of two bf16 values are exact in fp32, so the only error is that of the fp32 accumulation.
+ *
+ * Dispatch.  The fast path is a 128 x 128 x 64 tile kernel on v_mfma_f32_32x32x16_bf16 that reads both operands K-contiguous (the nt form: A stored m x k,
+ * B stored n x k); it takes any m and n, and a k that is not a whole number of 64-deep slabs, when
+ *     both bases are 16-byte aligned, lda and ldb are multiples of 8, and k is a multiple of 8 (k > 0).
+ * For nn, tn and tt the operand that is not K-contiguous is first copied transposed (bla_transpose_b16) into the context workspace.  Every other call
+ * (odd k, an operand off alignment, an odd pitch) goes to a bounds-checked kernel with 2-byte loads that is correct, not fast.
+ * bla_gemm_last_kernel() names what the last call launched:
+ *     gemm_bf16_mfma128x128x64_<nn|nt|tn|tt>_<f32|bf16>[_tcopyA][_tcopyB]     the fast path (tcopyX: operand X went through the transposed copy)
+ *     gemm_bf16_general_<nn|nt|tn|tt>_<f32|bf16>                              the general path
+ * Workspace: the transposed copies (and bla_gemm_f32_as_bf16's bf16 operands) live in the context workspace, which grows on demand.  As for every entry of
+ * this library that may grow a workspace, a call must have run once eagerly, with shapes at least as large, before it is captured into a graph. */
+enum { BLA_C_F32 = 0, BLA_C_BF16 = 1 };
+BLA_API bla_status bla_gemm_bf16(void* stream, int transa, int transb, int m, int n, int k, const uint16_t* d_a, int lda, const uint16_t* d_b, int ldb,
+                                 void* d_c, int ldc, int c_type, const bla_gemm_epilogue* ep /* NULL = plain product */);
+/* bla_gemm_f32's own argument list, fp32 A, B and C in memory: both operands are rounded to bf16 (bla_f32_to_bf16) into the context workspace and
+ * multiplied by bla_gemm_bf16 with BLA_C_F32 -- exactly that composition, bit for bit, with the bf16 operands in their fp32 layout at 16-byte aligned
+ * bases and pitches rounded up to a multiple of 8 (so the product is on the fast path whenever k % 8 == 0).  The entry for a caller with fp32 data who
+ * trades 16 mantissa bits of the operands for the bf16 matrix rate.  Epilogue and workspace rules: bla_gemm_bf16's. */
+BLA_API bla_status bla_gemm_f32_as_bf16(void* stream, int transa, int transb, int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb,
+                                        float* d_c, int ldc, const bla_gemm_epilogue* ep);
 
 /* ---- elementwise / broadcast / transpose / reductions: lib/matrix.c:59-205, lib/util.c:7-55 -------------
  * All operate in place on device memory exactly like their reference counterparts operate on host
