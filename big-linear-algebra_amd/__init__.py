@@ -6,10 +6,14 @@ if libbla_hip.so or a gfx950 device is missing, calls raise.
 """
 from . import build as _build  # noqa: F401
 from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilogue,  # noqa: F401
-                     to_device, empty, zeros, sync, ACT_NONE, ACT_RELU, gemm_bf16, to_bf16, from_bf16, C_F32, C_BF16)
+                     to_device, empty, zeros, sync, ACT_NONE, ACT_RELU, gemm_bf16, to_bf16, from_bf16, C_F32, C_BF16,
+                     conv_bf16_layout, conv_bf16_pad, conv_bf16_prepare_kernels, conv2d_gathered_bf16, conv2d_forward_as_bf16,
+                     conv2d_backward_as_bf16)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
 build_native = _build.build_native
 __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Epilogue", "to_device", "empty",
-           "zeros", "sync", "build_native", "ACT_NONE", "ACT_RELU", "gemm_bf16", "to_bf16", "from_bf16", "C_F32", "C_BF16"]
+           "zeros", "sync", "build_native", "ACT_NONE", "ACT_RELU", "gemm_bf16", "to_bf16", "from_bf16", "C_F32", "C_BF16",
+           "conv_bf16_layout", "conv_bf16_pad", "conv_bf16_prepare_kernels", "conv2d_gathered_bf16", "conv2d_forward_as_bf16",
+           "conv2d_backward_as_bf16"]

@@ -1,0 +1,471 @@
+// bla_conv_bf16.hip -- batched convolution with bf16 operands and fp32 accumulation (include/bla.h, "mixed-precision convolution").
+//
+// The product (conv_bf16_gather_kernel) is gemm_bf16_nt_kernel (bla_gemm_bf16.hip) with a gathered B operand: the same 128 x 128 x 64 tile, the same
+// v_mfma_f32_32x32x16_bf16 fragments, the same 16-byte global_load_lds pieces with the XOR swizzle on the source address, the same XCD-aware tile order and
+// the same zero-word source for lanes outside m, n or K.  What differs:
+//   * B row n is the output pixel (image b, i, j) of the padded channel-last copy P [B][Hp][Wp][Cp]; its k-th element is
+//         P[pixel_base(n) + (p Wp + q) Cp + c],   pixel_base(n) = ((b Hp + i s) Wp + j s) Cp,   k = (p kk + q) Cp + c   (tap-major, channel-minor).
+//     Cp % 8 == 0 makes every 8-element chunk of k one tap's 8 consecutive channels = 16 aligned bytes of P, whatever the stride, kernel and map size; the
+//     halo is part of P, so the gather has no bounds checks.  A 64-deep slab may cross tap boundaries (Cp = 24) and the last one may end short (K = 72).
+//   * pixel_base is a per-lane loop constant (four 64-bit pointers, one per piece).  A lane's chunk has only TWO distinct k offsets (pieces i and i + 2
+//     share the swizzle), so per slab a lane derives two tap offsets from kb + kc by two multiply-high divisions (by Cp, by kk; the magic constants come
+//     from the host) -- registers and VALU only, no table load in front of a DMA (a vector load there drains every DMA in flight).
+//   * the store maps (row, n) to out [b][row][pix]: lanes run along n, so a wave's store instruction writes runs of consecutive floats, also in a tile that
+//     straddles two images.
+// Around it: the pad copy (fp32 [B][C][H][W] -> P, a convert-and-transpose through an LDS tile that writes EVERY element of P), the tap-major kernel
+// matrices, and the materialised weight gradient (a bf16 im2col and a bf16 copy of del_y in front of the existing fast nt product).
+#include "bla_internal.h"
+#include <cmath>
+
+namespace bla {
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
+
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {   // bla_f32_to_bf16's rounding
+	uint32_t u = __float_as_uint(f);
+	if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+	return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ uint32_t pack2(float a, float b) { return f32_to_bf16_rne(a) | ((uint32_t)f32_to_bf16_rne(b) << 16); }
+
+__device__ __forceinline__ int xcd_tile(int bid, int nwg) {   // as in bla_gemm_bf16.hip
+	int q = nwg >> 3, r = nwg & 7, x = bid & 7, i = bid >> 3;
+	return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
+}
+
+constexpr int BM = 128, BN = 128, BK = 64, SLAB_BYTES = BM * BK * 2;
+
+struct GatherArgs {
+	const uint16_t* A; const uint16_t* P; float* out; const void* zero;
+	int rows, n, K, tiles_m, tiles_n;     // n = batch * ho * wo, K = kk * kk * cp
+	int hp, wp, cp, kk, stride, wo, howo;
+	uint32_t magic_cp, magic_kk;          // ceil(2^32 / cp); ceil(2^32 / kk), 0 for kk = 1 (every valid chunk is tap 0)
+	const float* bias; int bias_stride;
+};
+
+__global__ __launch_bounds__(256) void conv_bf16_gather_kernel(GatherArgs p) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // [A slab 16 KiB][B slab 16 KiB]
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	int pid = xcd_tile(blockIdx.x, p.tiles_m * p.tiles_n);
+	const int gsz = 8 * p.tiles_n, grp = pid / gsz, first = grp * 8, gm = min(p.tiles_m - first, 8);
+	const int tm = first + (pid % gsz) % gm, tn = (pid % gsz) / gm;
+	const int row0 = tm * BM, col0 = tn * BN;
+
+	const uint16_t* pa[4]; const uint16_t* pb[4];
+	bool oka[4], okb[4];
+	int kc[2];   // first k of the chunk this lane fetches: piece i takes kc[i & 1] (the swizzle term (row >> 1) & 7 is 4 (i & 1) + (lane >> 4))
+#pragma unroll
+	for (int i = 0; i < 4; ++i) {
+		const int row = (wave * 4 + i) * 8 + (lane >> 3);
+		const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+		if (i < 2) kc[i] = chunk * 8;
+		oka[i] = row0 + row < p.rows;
+		okb[i] = col0 + row < p.n;
+		pa[i] = p.A + (size_t)(oka[i] ? row0 + row : 0) * p.K + chunk * 8;
+		const int n = okb[i] ? col0 + row : 0;
+		const int b = n / p.howo, pix = n - b * p.howo, oi = pix / p.wo, oj = pix - oi * p.wo;
+		pb[i] = p.P + (((size_t)b * p.hp + (size_t)oi * p.stride) * p.wp + (size_t)oj * p.stride) * p.cp;
+	}
+	f32x16 acc[2][2];
+#pragma unroll
+	for (int i = 0; i < 2; ++i)
+#pragma unroll
+		for (int j = 0; j < 2; ++j)
+#pragma unroll
+			for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+	const int wm = wave >> 1, wn = wave & 1, fr = lane & 31, fh = lane >> 5;
+	for (int kb = 0; kb < p.K; kb += BK) {
+		int off[2]; bool in[2];
+#pragma unroll
+		for (int e = 0; e < 2; ++e) {
+			const uint32_t k0 = (uint32_t)(kb + kc[e]);
+			const uint32_t tap = __umulhi(k0, p.magic_cp), c = k0 - tap * p.cp;
+			const uint32_t tp = __umulhi(tap, p.magic_kk), tq = tap - tp * p.kk;
+			off[e] = (int)((tp * p.wp + tq) * p.cp + c);
+			in[e] = k0 < (uint32_t)p.K;   // a lane past K has a meaningless offset and never uses it
+		}
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			const void* sa = (oka[i] && in[i & 1]) ? (const void*)(pa[i] + kb) : p.zero;
+			const void* sb = (okb[i] && in[i & 1]) ? (const void*)(pb[i] + off[i & 1]) : p.zero;
+			__builtin_amdgcn_global_load_lds((gbl_ptr_t)sa, (lds_ptr_t)(lds + (wave * 4 + i) * 1024), 16, 0, 0);
+			__builtin_amdgcn_global_load_lds((gbl_ptr_t)sb, (lds_ptr_t)(lds + SLAB_BYTES + (wave * 4 + i) * 1024), 16, 0, 0);
+		}
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		__syncthreads();
+#pragma unroll
+		for (int s = 0; s < BK / 16; ++s) {
+			bf16x8 fa[2], fb[2];
+			const int g = 2 * s + fh;
+#pragma unroll
+			for (int i = 0; i < 2; ++i) {
+				const int ra = wm * 64 + i * 32 + fr, rb = wn * 64 + i * 32 + fr;
+				fa[i] = *(const bf16x8*)(lds + ra * 128 + ((g ^ ((ra >> 1) & 7)) << 4));
+				fb[i] = *(const bf16x8*)(lds + SLAB_BYTES + rb * 128 + ((g ^ ((rb >> 1) & 7)) << 4));
+			}
+#pragma unroll
+			for (int i = 0; i < 2; ++i)
+#pragma unroll
+				for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+		}
+		__syncthreads();
+	}
+#pragma unroll
+	for (int j = 0; j < 2; ++j) {
+		const int n = col0 + wn * 64 + j * 32 + fr;
+		if (n >= p.n) continue;
+		const int b = n / p.howo, pix = n - b * p.howo;
+		float* o = p.out + (size_t)b * p.rows * p.howo + pix;
+		const float* bias = p.bias ? p.bias + (size_t)b * p.bias_stride : nullptr;
+#pragma unroll
+		for (int i = 0; i < 2; ++i)
+#pragma unroll
+			for (int r = 0; r < 16; ++r) {
+				const int row = row0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+				if (row < p.rows) o[(size_t)row * p.howo] = bias ? acc[i][j][r] + bias[row] : acc[i][j][r];
+			}
+	}
+}
+
+// ---- the pad copy: fp32 [B][C][H][W] -> bf16 [B][Hp][Wp][Cp], every element of the destination written -----------------------------------------------
+// One workgroup: one destination row of one image, 64 channels, 64 source pixels of that row.  A row that holds source pixels ((r - top) % d == 0, inside
+// the map) is read [c][x] into an fp32 LDS tile (pitch 65: the 8-channel column walk of the write phase and the 4-pixel row writes of the read phase both
+// touch 64 different banks) and written [x][c] as 16-byte chunks of 8 channels; every other destination position of the tile's span -- halo, holes of a
+// dilation, channels from C up -- gets +0 from the same store.  The x tiles share the row's destination span between them: tile 0 starts at column 0, the
+// last tile ends at Wp.
+struct PadArgs16 { const float* src; uint16_t* dst; int c, h, w, hp, wp, cp, top, left, d, xtiles, vec; };
+
+__global__ __launch_bounds__(256) void conv_bf16_pad_kernel(PadArgs16 a) {
+	__shared__ float tile[64][65];
+	const int xt = blockIdx.x % a.xtiles, ct = blockIdx.x / a.xtiles, r = blockIdx.y, b = blockIdx.z;
+	const int c0 = ct * 64, x0 = xt * 64, xn = min(64, a.w - x0);
+	const int ry = r - a.top, y = ry / a.d;
+	const bool source_row = ry >= 0 && ry % a.d == 0 && y < a.h;   // uniform over the workgroup
+	if (source_row) {
+		const float* s = a.src + (((size_t)b * a.c + c0) * a.h + y) * a.w + x0;
+		for (int id = threadIdx.x; id < 64 * 16; id += 256) {
+			const int c = id >> 4, x = (id & 15) * 4;
+			if (x >= xn) continue;
+			float v[4] = {0.f, 0.f, 0.f, 0.f};
+			if (c0 + c < a.c) {
+				const float* sp = s + (size_t)c * a.h * a.w + x;
+				if (a.vec && x + 4 <= xn) { const float4 q = *(const float4*)sp; v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+				else for (int j = 0; j < 4 && x + j < xn; ++j) v[j] = sp[j];
+			}
+#pragma unroll
+			for (int j = 0; j < 4; ++j) tile[c][x + j] = v[j];   // x + j <= 63; columns from xn up are never read
+		}
+		__syncthreads();
+	}
+	const int lo = xt == 0 ? 0 : a.left + x0 * a.d, hi = xt == a.xtiles - 1 ? a.wp : a.left + (x0 + 64) * a.d;
+	const int cq = threadIdx.x & 7, c = c0 + cq * 8;
+	if (c >= a.cp) return;
+	uint16_t* drow = a.dst + ((size_t)b * a.hp + r) * a.wp * a.cp + c;
+	for (int t = lo + (threadIdx.x >> 3); t < hi; t += 32) {
+		uint4 o = make_uint4(0u, 0u, 0u, 0u);
+		const int sx = t - a.left, x = sx / a.d - x0;
+		if (source_row && sx >= 0 && sx % a.d == 0 && x >= 0 && x < xn) {
+			o.x = pack2(tile[cq * 8 + 0][x], tile[cq * 8 + 1][x]);
+			o.y = pack2(tile[cq * 8 + 2][x], tile[cq * 8 + 3][x]);
+			o.z = pack2(tile[cq * 8 + 4][x], tile[cq * 8 + 5][x]);
+			o.w = pack2(tile[cq * 8 + 6][x], tile[cq * 8 + 7][x]);
+		}
+		*(uint4*)(drow + (size_t)t * a.cp) = o;
+	}
+}
+
+// ---- kernel matrices, tap-major: one thread per 8-element chunk of a destination row ------------------------------------------------------------------
+//   forward:        dst [f][(p k + q) Cp + c]                 = kern[f][c][p][q]          rows = F, inner = C
+//   data gradient:  dst [c][((k-1-p) k + (k-1-q)) Fp + f]     = kern[f][c][p][q]          rows = C, inner = F
+__global__ __launch_bounds__(256) void conv_bf16_kernels_kernel(const float* __restrict__ kern, uint16_t* __restrict__ dst, int f_n, int c_n, int k, int dgrad) {
+	const int inner = dgrad ? f_n : c_n, rows = dgrad ? c_n : f_n, ip = (inner + 7) & ~7, chunks = k * k * (ip >> 3);
+	const long id = (long)blockIdx.x * 256 + threadIdx.x;
+	if (id >= (long)rows * chunks) return;
+	const int row = (int)(id / chunks), ch = (int)(id % chunks), tap = ch / (ip >> 3), i0 = (ch % (ip >> 3)) * 8;
+	const int tp = dgrad ? k - 1 - tap / k : tap / k, tq = dgrad ? k - 1 - tap % k : tap % k;
+	float v[8];
+#pragma unroll
+	for (int j = 0; j < 8; ++j) {
+		const int in = i0 + j, f = dgrad ? in : row, c = dgrad ? row : in;
+		v[j] = in < inner ? kern[(((size_t)f * c_n + c) * k + tp) * k + tq] : 0.f;
+	}
+	*(uint4*)(dst + (size_t)row * k * k * ip + (size_t)ch * 8) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+}
+
+// ---- the weight gradient's operands, both [row][n] with n = (image, i, j) at a pitch np = B Ho Wo rounded up to 8, the tail zero ----------------------
+//   G [(c, p, q)][n] = x[b][c][i s + p - pt][j s + q - pl] (0 outside the map);   dY16 [f][n] = del_y[b][f][i][j]
+struct WgradArgs { const float* src; uint16_t* dst; int rows, n, np, c, h, w, k, s, wo, howo, pt, pl; };
+
+template <bool IM2COL>
+__global__ __launch_bounds__(256) void conv_bf16_wgrad_operand_kernel(WgradArgs a) {
+	const int chunks = a.np >> 3;
+	const long id = (long)blockIdx.x * 256 + threadIdx.x;
+	if (id >= (long)a.rows * chunks) return;
+	const int row = (int)(id / chunks), n0 = (int)(id % chunks) * 8;
+	int c = row, tp = 0, tq = 0;
+	if (IM2COL) { const int kk = a.k * a.k, t = row % kk; c = row / kk; tp = t / a.k; tq = t % a.k; }
+	float v[8];
+#pragma unroll
+	for (int j = 0; j < 8; ++j) {
+		const int n = n0 + j;
+		v[j] = 0.f;
+		if (n < a.n) {
+			const int b = n / a.howo, pix = n - b * a.howo;
+			if (IM2COL) {
+				const int oi = pix / a.wo, oj = pix - oi * a.wo, y = oi * a.s + tp - a.pt, x = oj * a.s + tq - a.pl;
+				if (y >= 0 && y < a.h && x >= 0 && x < a.w) v[j] = a.src[(((size_t)b * a.c + c) * a.h + y) * a.w + x];
+			} else {
+				v[j] = a.src[((size_t)b * a.rows + row) * a.howo + pix];
+			}
+		}
+	}
+	*(uint4*)(a.dst + (size_t)row * a.np + n0) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline size_t round_up(size_t x, size_t to) { return (x + to - 1) / to * to; }
+inline int round8(int x) { return (x + 7) & ~7; }
+
+struct Same { int ho, wo, pt, pl, vpad, hpad; };
+// TF "SAME" geometry exactly as lib/conv.c:13-28,55-56 computes it (ceil on a float quotient)
+Same same_geometry(int h, int w, int k, int s) {
+	Same g;
+	g.vpad = (int)((ceil(((float)h) / s) - 1) * s + k - h);
+	if (g.vpad < 0) g.vpad = 0;
+	g.hpad = (int)((ceil(((float)w) / s) - 1) * s + k - w);
+	if (g.hpad < 0) g.hpad = 0;
+	g.pt = g.vpad / 2; g.pl = g.hpad / 2;
+	g.ho = (int)ceil((float)h / s); g.wo = (int)ceil((float)w / s);
+	return g;
+}
+
+struct Layout16 { int hp, wp, top, left, dilate; };
+Layout16 layout16(int h, int w, int k, int stride, bool dgrad) {
+	const Same g = same_geometry(h, w, k, stride);
+	if (dgrad) return {h + k - 1, w + k - 1, k - 1 - g.pt, k - 1 - g.pl, stride};
+	return {h + g.vpad, w + g.hpad, g.pt, g.pl, 1};
+}
+
+bool strict_reference() {
+	static const bool v = [] { const char* e = getenv("BLA_STRICT_REFERENCE"); return e && e[0] == '1'; }();
+	return v;
+}
+
+// ---- pure argument checks (no device is asked for) ---------------------------------------------------------------------------------------------------
+// (the shape checks stand apart from the pointer checks: the _as_bf16 entries run them before they have a workspace)
+bla_status check_pad_shape(int batch, int c, int h, int w, int hp, int wp, int top, int left, int dilate) {
+	BLA_REQUIRE(batch > 0 && c > 0 && h > 0 && w > 0 && hp > 0 && wp > 0, BLA_ERR_INVALID, "bla_conv_bf16_pad: extent <= 0 (batch %d c %d h %d w %d hp %d wp %d)", batch, c, h, w, hp, wp);
+	BLA_REQUIRE(top >= 0 && left >= 0 && dilate >= 1, BLA_ERR_INVALID, "bla_conv_bf16_pad: top %d left %d dilate %d", top, left, dilate);
+	BLA_REQUIRE((long)top + (long)(h - 1) * dilate < hp && (long)left + (long)(w - 1) * dilate < wp, BLA_ERR_INVALID,
+	            "bla_conv_bf16_pad: the %d x %d map at (%d, %d), dilation %d, does not fit %d x %d", h, w, top, left, dilate, hp, wp);
+	BLA_REQUIRE(batch <= 65535 && hp <= 65535 && (long)left + ((long)w + 64) * dilate < (1L << 31), BLA_ERR_INVALID, "bla_conv_bf16_pad: batch %d or hp %d exceeds the grid", batch, hp);
+	return BLA_OK;
+}
+
+bla_status check_kernels(const void* kern, const void* dst, int f_n, int c_n, int k) {
+	BLA_REQUIRE(kern && dst, BLA_ERR_INVALID, "bla_conv_bf16_prepare_kernels: NULL pointer");
+	BLA_REQUIRE(f_n > 0 && c_n > 0 && k > 0, BLA_ERR_INVALID, "bla_conv_bf16_prepare_kernels: extent <= 0 (f %d c %d k %d)", f_n, c_n, k);
+	BLA_REQUIRE(aligned16(dst), BLA_ERR_INVALID, "bla_conv_bf16_prepare_kernels: the destination is not 16-byte aligned");
+	return BLA_OK;
+}
+
+bla_status check_gathered_shape(int rows, int batch, int hp, int wp, int cp, int k, int stride, int ho, int wo, int ep_bias_stride) {
+	BLA_REQUIRE(rows > 0 && batch > 0 && hp > 0 && wp > 0 && cp > 0 && k > 0 && ho > 0 && wo > 0, BLA_ERR_INVALID,
+	            "bla_conv2d_gathered_bf16: extent <= 0 (rows %d batch %d hp %d wp %d cp %d k %d ho %d wo %d)", rows, batch, hp, wp, cp, k, ho, wo);
+	BLA_REQUIRE(stride >= 1, BLA_ERR_INVALID, "bla_conv2d_gathered_bf16: stride %d", stride);
+	BLA_REQUIRE(cp % 8 == 0, BLA_ERR_INVALID, "bla_conv2d_gathered_bf16: cp %d is not a multiple of 8", cp);
+	BLA_REQUIRE(ep_bias_stride >= 0, BLA_ERR_INVALID, "bla_conv2d_gathered_bf16: ep_bias_stride %d", ep_bias_stride);
+	// every tap of every output pixel lies inside the padded copy: the gather itself checks nothing
+	BLA_REQUIRE((long)(ho - 1) * stride + k <= hp && (long)(wo - 1) * stride + k <= wp, BLA_ERR_INVALID,
+	            "bla_conv2d_gathered_bf16: a %d x %d output at stride %d, k %d reads past the %d x %d padded map", ho, wo, stride, k, hp, wp);
+	const long K = (long)k * k * cp, n = (long)batch * ho * wo;
+	BLA_REQUIRE((long)hp * wp * cp < (1L << 31) && (K + 128) * cp < (1L << 31) && n < (1L << 31) - 128 && ((rows + 127L) / 128) * ((n + 127) / 128) < (1L << 31), BLA_ERR_INVALID,
+	            "bla_conv2d_gathered_bf16: the product exceeds 32-bit indexing (padded image %ld elements, K %ld, columns %ld)", (long)hp * wp * cp, K, n);
+	return BLA_OK;
+}
+
+bla_status check_conv(const char* who, int batch, int h, int w, int k, int c_in, int f_n, int stride) {
+	BLA_REQUIRE(batch > 0 && h > 0 && w > 0 && k > 0 && c_in > 0 && f_n > 0, BLA_ERR_INVALID, "%s: extent <= 0 (batch %d h %d w %d k %d c %d f %d)", who, batch, h, w, k, c_in, f_n);
+	BLA_REQUIRE(stride >= 1, BLA_ERR_INVALID, "%s: stride %d", who, stride);
+	return BLA_OK;
+}
+
+// ---- launches -------------------------------------------------------------------------------------------------------------------------------------------
+bla_status launch_pad(hipStream_t s, const float* src, uint16_t* dst, int batch, int c, int h, int w, int hp, int wp, int top, int left, int dilate) {
+	PadArgs16 a{src, dst, c, h, w, hp, wp, round8(c), top, left, dilate, (w + 63) / 64, aligned16(src) && w % 4 == 0};
+	const long gx = (long)a.xtiles * ((a.cp + 63) / 64);
+	BLA_REQUIRE(gx < (1L << 31), BLA_ERR_INVALID, "bla_conv_bf16_pad: %d channels x %d columns exceed the grid", c, w);
+	hipLaunchKernelGGL(conv_bf16_pad_kernel, dim3((unsigned)gx, hp, batch), dim3(256), 0, s, a);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status launch_kernels(hipStream_t s, const float* kern, uint16_t* dst, int f_n, int c_n, int k, int dgrad) {
+	const long n = (long)(dgrad ? c_n : f_n) * k * k * (round8(dgrad ? f_n : c_n) / 8);
+	BLA_REQUIRE((n + 255) / 256 < (1L << 31), BLA_ERR_INVALID, "bla_conv_bf16_prepare_kernels: %ld chunks exceed the grid", n);
+	hipLaunchKernelGGL(conv_bf16_kernels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kern, dst, f_n, c_n, k, dgrad);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status launch_gathered(hipStream_t s, const uint16_t* A, int rows, const uint16_t* P, int batch, int hp, int wp, int cp, int k, int stride, int ho, int wo, float* out,
+                           const float* ep_bias, int ep_bias_stride) {
+	GatherArgs a{};
+	a.A = A; a.P = P; a.out = out; a.zero = zero_word();
+	a.rows = rows; a.n = batch * ho * wo; a.K = k * k * cp;
+	a.tiles_m = (rows + BM - 1) / BM; a.tiles_n = (a.n + BN - 1) / BN;
+	a.hp = hp; a.wp = wp; a.cp = cp; a.kk = k; a.stride = stride; a.wo = wo; a.howo = ho * wo;
+	// floor(x / d) = (x * ceil(2^32 / d)) >> 32 whenever x * d < 2^32 (check_gathered_shape: (K + 128) cp < 2^31; taps * kk is far below)
+	a.magic_cp = (uint32_t)(((1ull << 32) + cp - 1) / cp);
+	a.magic_kk = k == 1 ? 0u : (uint32_t)(((1ull << 32) + k - 1) / k);
+	a.bias = ep_bias; a.bias_stride = ep_bias_stride;
+	hipLaunchKernelGGL(conv_bf16_gather_kernel, dim3((unsigned)((long)a.tiles_m * a.tiles_n)), dim3(256), 2 * SLAB_BYTES, s, a);
+	BLA_HIP(hipGetLastError());
+	char name[64];
+	snprintf(name, sizeof name, "conv_bf16_gather128x128x64_s%d", stride);
+	gemm_note_last_kernel(name);
+	return BLA_OK;
+}
+
+template <bool IM2COL>
+bla_status launch_wgrad_operand(hipStream_t s, const WgradArgs& a) {
+	const long n = (long)a.rows * (a.np / 8);
+	BLA_REQUIRE((n + 255) / 256 < (1L << 31), BLA_ERR_INVALID, "bla_conv2d_backward_batched_f32_as_bf16: %ld chunks exceed the grid", n);
+	hipLaunchKernelGGL(conv_bf16_wgrad_operand_kernel<IM2COL>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+size_t padded_bytes(int batch, int hp, int wp, int cp) { return round_up((size_t)batch * hp * wp * cp * 2, 256); }
+size_t kernels_bytes(int rows, int k, int inner_p) { return round_up((size_t)rows * k * k * inner_p * 2, 256); }
+
+}  // namespace
+}  // namespace bla
+
+using namespace bla;
+
+extern "C" {
+
+bla_status bla_conv_bf16_layout(int h, int w, int k, int stride, int data_gradient, int* hp, int* wp, int* top, int* left, int* dilate) {
+	BLA_REQUIRE(h > 0 && w > 0 && k > 0 && stride >= 1 && hp && wp && top && left && dilate, BLA_ERR_INVALID, "bla_conv_bf16_layout: bad query (h %d w %d k %d stride %d)", h, w, k, stride);
+	const Layout16 L = layout16(h, w, k, stride, data_gradient != 0);
+	*hp = L.hp; *wp = L.wp; *top = L.top; *left = L.left; *dilate = L.dilate;
+	return BLA_OK;
+}
+
+bla_status bla_conv_bf16_pad(void* stream, const float* d_src, uint16_t* d_dst, int batch, int c, int h, int w, int hp, int wp, int top, int left, int dilate) {
+	BLA_REQUIRE(d_src && d_dst, BLA_ERR_INVALID, "bla_conv_bf16_pad: NULL pointer");
+	BLA_REQUIRE(aligned16(d_dst), BLA_ERR_INVALID, "bla_conv_bf16_pad: the destination is not 16-byte aligned");
+	bla_status st = check_pad_shape(batch, c, h, w, hp, wp, top, left, dilate);
+	if (st != BLA_OK) return st;
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	return launch_pad(pick_stream(stream), d_src, d_dst, batch, c, h, w, hp, wp, top, left, dilate);
+}
+
+bla_status bla_conv_bf16_prepare_kernels(void* stream, const float* d_kern, uint16_t* d_dst, int f_n, int c_n, int k, int data_gradient) {
+	bla_status st = check_kernels(d_kern, d_dst, f_n, c_n, k);
+	if (st != BLA_OK) return st;
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	return launch_kernels(pick_stream(stream), d_kern, d_dst, f_n, c_n, k, data_gradient != 0);
+}
+
+bla_status bla_conv2d_gathered_bf16(void* stream, const uint16_t* d_a, int rows, const uint16_t* d_p, int batch, int hp, int wp, int cp, int k, int stride, int ho, int wo,
+                                    float* d_out, const float* ep_bias, int ep_bias_stride) {
+	BLA_REQUIRE(d_a && d_p && d_out, BLA_ERR_INVALID, "bla_conv2d_gathered_bf16: NULL pointer");
+	BLA_REQUIRE(aligned16(d_a) && aligned16(d_p), BLA_ERR_INVALID, "bla_conv2d_gathered_bf16: an operand is not 16-byte aligned");
+	bla_status st = check_gathered_shape(rows, batch, hp, wp, cp, k, stride, ho, wo, ep_bias_stride);
+	if (st != BLA_OK) return st;
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	return launch_gathered(pick_stream(stream), d_a, rows, d_p, batch, hp, wp, cp, k, stride, ho, wo, d_out, ep_bias, ep_bias_stride);
+}
+
+bla_status bla_conv2d_forward_batched_f32_as_bf16(void* stream, const float* d_x, const float* d_kern, float* d_out, int batch, int h, int w, int k, int c_in, int f_n,
+                                                  int stride, const float* ep_bias, int ep_bias_stride) {
+	const char* who = "bla_conv2d_forward_batched_f32_as_bf16";
+	BLA_REQUIRE(d_x && d_kern && d_out, BLA_ERR_INVALID, "%s: NULL pointer", who);
+	bla_status st = check_conv(who, batch, h, w, k, c_in, f_n, stride);
+	if (st != BLA_OK) return st;
+	const Same g = same_geometry(h, w, k, stride);
+	const Layout16 L = layout16(h, w, k, stride, false);
+	const int cp = round8(c_in);
+	const size_t p_bytes = padded_bytes(batch, L.hp, L.wp, cp);
+	// the composition's own shape checks (grid and 32-bit index limits), still before the device is asked for
+	if ((st = check_pad_shape(batch, c_in, h, w, L.hp, L.wp, L.top, L.left, 1)) != BLA_OK) return st;
+	if ((st = check_gathered_shape(f_n, batch, L.hp, L.wp, cp, k, stride, g.ho, g.wo, ep_bias_stride)) != BLA_OK) return st;
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	void* ws = nullptr;
+	st = ensure_workspace(p_bytes + kernels_bytes(f_n, k, cp), &ws);
+	if (st != BLA_OK) return st;
+	unsigned char* base = (unsigned char*)ws;
+	uint16_t* P = (uint16_t*)base;
+	uint16_t* A = (uint16_t*)(base + p_bytes);
+	hipStream_t s = pick_stream(stream);
+	if ((st = launch_pad(s, d_x, P, batch, c_in, h, w, L.hp, L.wp, L.top, L.left, 1)) != BLA_OK) return st;
+	if ((st = launch_kernels(s, d_kern, A, f_n, c_in, k, 0)) != BLA_OK) return st;
+	return launch_gathered(s, A, f_n, P, batch, L.hp, L.wp, cp, k, stride, g.ho, g.wo, d_out, ep_bias, ep_bias_stride);
+}
+
+bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x, int batch,
+                                                   int h, int w, int k, int c_in, int f_n, int stride) {
+	const char* who = "bla_conv2d_backward_batched_f32_as_bf16";
+	BLA_REQUIRE(d_del_y, BLA_ERR_INVALID, "%s: NULL del_y", who);
+	BLA_REQUIRE(!d_del_kern || d_x, BLA_ERR_INVALID, "%s: the weight gradient needs the forward input", who);
+	BLA_REQUIRE(!d_del_x || d_kern, BLA_ERR_INVALID, "%s: the data gradient needs the kernels", who);
+	bla_status st = check_conv(who, batch, h, w, k, c_in, f_n, stride);
+	if (st != BLA_OK) return st;
+	if (d_del_x && stride != 1 && strict_reference()) {
+		set_error("the data gradient is undefined in the reference for stride %d (_col2im, lib/conv.c:80-135)", stride);
+		return BLA_ERR_UNDEFINED;
+	}
+	const Same g = same_geometry(h, w, k, stride);
+	const Layout16 L = layout16(h, w, k, stride, true);
+	const int fp = round8(f_n);
+	const long n = (long)batch * g.ho * g.wo;
+	BLA_REQUIRE(n < (1L << 31) - 128 && (long)c_in * k * k < (1L << 31), BLA_ERR_INVALID, "%s: %ld output pixels exceed 32-bit indexing", who, n);
+	const int np = round8((int)n), ckk = c_in * k * k;
+	if (d_del_x) {
+		if ((st = check_pad_shape(batch, f_n, g.ho, g.wo, L.hp, L.wp, L.top, L.left, L.dilate)) != BLA_OK) return st;
+		if ((st = check_gathered_shape(c_in, batch, L.hp, L.wp, fp, k, 1, h, w, 0)) != BLA_OK) return st;
+	}
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	// one workspace for both gradients, one behind the other on the stream: [dY16 | G] for the weight gradient, then [P | A] for the data gradient
+	const size_t dy_bytes = round_up((size_t)f_n * np * 2, 256), g_bytes = round_up((size_t)ckk * np * 2, 256);
+	const size_t p_bytes = padded_bytes(batch, L.hp, L.wp, fp);
+	const size_t need_w = d_del_kern ? dy_bytes + g_bytes : 0, need_d = d_del_x ? p_bytes + kernels_bytes(c_in, k, fp) : 0;
+	if (!need_w && !need_d) return BLA_OK;
+	void* ws = nullptr;
+	st = ensure_workspace(need_w > need_d ? need_w : need_d, &ws);
+	if (st != BLA_OK) return st;
+	unsigned char* base = (unsigned char*)ws;
+	hipStream_t s = pick_stream(stream);
+	if (d_del_kern) {
+		uint16_t* dy16 = (uint16_t*)base;
+		uint16_t* G = (uint16_t*)(base + dy_bytes);
+		WgradArgs a{d_del_y, dy16, f_n, (int)n, np, c_in, h, w, k, stride, g.wo, g.ho * g.wo, g.pt, g.pl};
+		if ((st = launch_wgrad_operand<false>(s, a)) != BLA_OK) return st;
+		a.src = d_x; a.dst = G; a.rows = ckk;
+		if ((st = launch_wgrad_operand<true>(s, a)) != BLA_OK) return st;
+		// del_kern [F][C k k] = dY16 [F][np] . G [C k k][np]^T: rows of G in (c, p, q) order, so the result is already [F][C][k][k]
+		if ((st = gemm_bf16_launch(s, 0, 1, f_n, ckk, np, dy16, np, G, np, d_del_kern, ckk, BLA_C_F32, nullptr, nullptr)) != BLA_OK) return st;
+	}
+	if (d_del_x) {
+		uint16_t* P = (uint16_t*)base;
+		uint16_t* A = (uint16_t*)(base + p_bytes);
+		if ((st = launch_pad(s, d_del_y, P, batch, f_n, g.ho, g.wo, L.hp, L.wp, L.top, L.left, L.dilate)) != BLA_OK) return st;
+		if ((st = launch_kernels(s, d_kern, A, f_n, c_in, k, 1)) != BLA_OK) return st;
+		if ((st = launch_gathered(s, A, c_in, P, batch, L.hp, L.wp, fp, k, 1, h, w, d_del_x, nullptr, 0)) != BLA_OK) return st;
+	}
+	return BLA_OK;
+}
+
+}  // extern "C"

@@ -273,6 +273,8 @@ size_t tcopy_bytes(bool fast, int transa, int transb, int m, int n, int k) {
 	return (transa ? round_up((size_t)m * k * 2, 256) : 0) + (!transb ? round_up((size_t)n * k * 2, 256) : 0);
 }
 
+}  // namespace
+
 // the product itself; ws holds tcopy_bytes() bytes (16-byte aligned)
 bla_status gemm_bf16_launch(hipStream_t s, int transa, int transb, int m, int n, int k, const uint16_t* A, int lda, const uint16_t* B, int ldb, void* C, int ldc,
                             int c_type, const bla_gemm_epilogue* ep, unsigned char* ws) {
@@ -320,7 +322,6 @@ bla_status gemm_bf16_launch(hipStream_t s, int transa, int transb, int m, int n,
 	return BLA_OK;
 }
 
-}  // namespace
 }  // namespace bla
 
 using namespace bla;

@@ -111,6 +111,10 @@ bla_status thin_conv_wgrad(hipStream_t s, const float* del_y, const float* x, fl
 
 // bla_gemm.hip: what bla_gemm_last_kernel() answers; the bf16 products (bla_gemm_bf16.hip) record their variant here
 void gemm_note_last_kernel(const char* name);
+// bla_gemm_bf16.hip: the bf16 product behind bla_gemm_bf16, arguments already checked (bla_conv_bf16.hip's weight gradient launches its nt form);
+// ws: the bytes the transposed copies of nn / tn / tt need, 16-byte aligned (nt: none, may be NULL)
+bla_status gemm_bf16_launch(hipStream_t s, int transa, int transb, int m, int n, int k, const uint16_t* A, int lda, const uint16_t* B, int ldb, void* C, int ldc,
+                            int c_type, const bla_gemm_epilogue* ep, unsigned char* ws);
 
 // bla_gemm_thin.hip: batched products with a short contraction (k <= 64, a multiple of 8; m, n multiples of 32) and a large output, one wave per
 // 32 x (32..128) block straight from global memory; up to three (A, B) pairs accumulate before the one store.  Strides in floats per batch index.

@@ -67,6 +67,9 @@ SIGNATURES = {
     "bla_transpose_b16": (_I, [_VP, _VP, _I, _VP, _I, _I, _I]),
     "bla_gemm_bf16": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, C.POINTER(Epilogue)]),
     "bla_gemm_f32_as_bf16": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, C.POINTER(Epilogue)]),
+    "bla_conv_bf16_layout": (_I, [_I] * 5 + [C.POINTER(_I)] * 5), "bla_conv_bf16_pad": (_I, [_VP] * 3 + [_I] * 9),
+    "bla_conv_bf16_prepare_kernels": (_I, [_VP] * 3 + [_I] * 4), "bla_conv2d_gathered_bf16": (_I, [_VP, _VP, _I, _VP] + [_I] * 8 + [_VP, _VP, _I]),
+    "bla_conv2d_forward_batched_f32_as_bf16": (_I, [_VP] * 4 + [_I] * 7 + [_VP, _I]), "bla_conv2d_backward_batched_f32_as_bf16": (_I, [_VP] * 6 + [_I] * 7),
     "bla_scale_f32": (_I, [_VP, _VP, _SZ, _F]), "bla_add_f32": (_I, [_VP, _VP, _VP, _SZ]),
     "bla_hadamard_f32": (_I, [_VP, _VP, _VP, _SZ]), "bla_axpy_f32": (_I, [_VP, _VP, _VP, _F, _SZ]),
     "bla_relu_f32": (_I, [_VP, _VP, _SZ]), "bla_relu_ddx_f32": (_I, [_VP, _VP, _SZ]),
@@ -377,3 +380,40 @@ def gemm_bf16(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, bias_row
     check(lib().bla_gemm_bf16(stream, int(transa), int(transb), m, n, k, _ptr(a), lda or a.ld, _ptr(b), ldb or b.ld, _ptr(c), ldc or c.ld,
                               c_type, C.byref(ep)))
     return c
+
+
+# ---- mixed-precision convolution (include/bla.h: bf16 operands, fp32 accumulation) ---------------------------------------------------------------------
+def conv_bf16_layout(h, w, k, stride, data_gradient=False):
+    """(hp, wp, top, left, dilate) of the padded channel-last operand: the forward input, or (data_gradient) del_y dilated by the stride."""
+    v = [C.c_int() for _ in range(5)]
+    check(lib().bla_conv_bf16_layout(h, w, k, stride, int(data_gradient), *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def conv_bf16_pad(src, dst, batch, c, h, w, hp, wp, top, left, dilate=1, stream=None):
+    """fp32 [batch][c][h][w] -> bf16 [batch][hp][wp][Cp] (np.uint16 device array), every element of dst written."""
+    check(lib().bla_conv_bf16_pad(stream, _ptr(src), _ptr(dst), batch, c, h, w, hp, wp, top, left, dilate))
+    return dst
+
+
+def conv_bf16_prepare_kernels(kern, dst, f_n, c_n, k, data_gradient=False, stream=None):
+    """fp32 [f_n][c_n][k][k] -> the tap-major bf16 matrix: forward [f_n][k*k*Cp], or (data_gradient) flipped and transposed [c_n][k*k*Fp]."""
+    check(lib().bla_conv_bf16_prepare_kernels(stream, _ptr(kern), _ptr(dst), f_n, c_n, k, int(data_gradient)))
+    return dst
+
+
+def conv2d_gathered_bf16(a, rows, p, batch, hp, wp, cp, k, stride, ho, wo, out, ep_bias=None, ep_bias_stride=0, stream=None):
+    """out fp32 [batch][rows][ho][wo] = A [rows][k*k*cp] . gather(P [batch][hp][wp][cp]) (+ ep_bias[b * ep_bias_stride + row])."""
+    check(lib().bla_conv2d_gathered_bf16(stream, _ptr(a), rows, _ptr(p), batch, hp, wp, cp, k, stride, ho, wo, _ptr(out), _ptr(ep_bias), ep_bias_stride))
+    return out
+
+
+def conv2d_forward_as_bf16(x, kern, out, batch, h, w, k, c_in, f_n, stride, ep_bias=None, ep_bias_stride=0, stream=None):
+    """bla_conv2d_forward_batched_f32's arguments, fp32 in memory, multiplied in bf16: pad + prepare_kernels + gathered product in the workspace."""
+    check(lib().bla_conv2d_forward_batched_f32_as_bf16(stream, _ptr(x), _ptr(kern), _ptr(out), batch, h, w, k, c_in, f_n, stride, _ptr(ep_bias), ep_bias_stride))
+    return out
+
+
+def conv2d_backward_as_bf16(del_y, x, kern, del_kern, del_x, batch, h, w, k, c_in, f_n, stride, stream=None):
+    """Both gradients of the same convolution in bf16 (either output may be None): the materialised weight gradient, the gathered data gradient."""
+    check(lib().bla_conv2d_backward_batched_f32_as_bf16(stream, _ptr(del_y), _ptr(x), _ptr(kern), _ptr(del_kern), _ptr(del_x), batch, h, w, k, c_in, f_n, stride))

@@ -326,6 +326,53 @@ BLA_API bla_status bla_conv2d_forward_batched_f32(void* stream, const float* d_x
                                                   int c_in, int f_n, int stride);
 BLA_API bla_status bla_conv2d_backward_batched_f32(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern,
                                                    float* d_del_x, float* d_scratch, int batch, int h, int w, int k, int c_in, int f_n, int stride);
+/* ---- mixed-precision convolution: bf16 operands, fp32 accumulation, on the bf16 matrix instructions (csrc/bla_conv_bf16.hip) -------------
+ * An addition beside the fp32 entries above: no fp32 entry, plan or dispatcher decision changes.  bf16 = uint16_t bit patterns rounded as bla_f32_to_bf16
+ * rounds; Cp = the channel count rounded up to a multiple of 8; every base address 16-byte aligned.
+ *
+ * Padded channel-last activations  P [B][Hp][Wp][Cp]:  P[b][top + y d][left + x d][c] = rne(src[b][c][y][x]); every other element -- the halo, the holes of
+ * a dilation d > 1, the channels from C up to Cp -- is +0.  The 8 channels of one tap of one output pixel are then one aligned 16-byte chunk for any
+ * stride, kernel and map size, and the product's gather needs no bounds checks.
+ * Kernel matrices, tap-major:  forward  A [F][k k Cp]:  A[f][(p k + q) Cp + c] = rne(kern[f][c][p][q]);
+ *                              data gradient, flipped and transposed  A [C][k k Fp]:  A[c][((k-1-p) k + (k-1-q)) Fp + f] = rne(kern[f][c][p][q]);
+ * padding columns are +0.
+ *
+ * bla_conv_bf16_layout (host only): the padded extents of an h x w map.  data_gradient = 0, the operand of the forward pass and of nothing else here:
+ * TF-SAME top / left as lib/conv.c:13-28 computes them, hp = h + vertical padding, wp = w + horizontal padding, dilate = 1.  data_gradient = 1, h x w being
+ * the convolution's INPUT size: the layout of del_y [Ho][Wo] dilated by the stride: dilate = stride, top = k-1-pt, left = k-1-pl, hp = h+k-1, wp = w+k-1. */
+BLA_API bla_status bla_conv_bf16_layout(int h, int w, int k, int stride, int data_gradient, int* hp, int* wp, int* top, int* left, int* dilate);
+/* The copy described above, fp32 [batch][c][h][w] -> P [batch][hp][wp][Cp]: a convert-and-transpose through an LDS tile that writes EVERY element of d_dst
+ * (16-byte stores; 16-byte loads when d_src is 16-byte aligned and w % 4 == 0).  The map must fit: top + (h-1) dilate < hp, left + (w-1) dilate < wp. */
+BLA_API bla_status bla_conv_bf16_pad(void* stream, const float* d_src, uint16_t* d_dst, int batch, int c, int h, int w, int hp, int wp, int top, int left, int dilate);
+/* kern fp32 [f_n][c_n][k][k] -> the forward matrix [f_n][k k Cp] (data_gradient = 0) or the data gradient's [c_n][k k Fp] (1), every element written */
+BLA_API bla_status bla_conv_bf16_prepare_kernels(void* stream, const float* d_kern, uint16_t* d_dst, int f_n, int c_n, int k, int data_gradient);
+/*   out[b][r][i][j] = sum_{p,q,c} A[r][(p k + q) cp + c] * P[b][i stride + p][j stride + q][c]  (+ ep_bias[b * ep_bias_stride + r], in fp32, if ep_bias)
+ * A [rows][k k cp], P [batch][hp][wp][cp], out fp32 [batch][rows][ho][wo] (the project's layout).  One product for the forward pass (A = the forward matrix,
+ * P = the padded input) and for the data gradient (A = the flipped matrix, P = the dilated padded del_y, stride 1, ho x wo = the input's h x w).
+ * The kernel is bla_gemm_bf16's 128 x 128 x 64 fast kernel with the B operand gathered from P (columns = (image, output pixel)); the error is that of the
+ * fp32 accumulation alone (DESIGN 3.18's bound with K = k k cp).  bla_gemm_last_kernel() then answers conv_bf16_gather128x128x64_s<stride>.
+ * BLA_ERR_INVALID, before the device is asked for: a NULL A, P or out, an extent <= 0, stride < 1, cp % 8 != 0, an operand off 16-byte alignment, an
+ * output whose taps reach past the padded map ((ho-1) stride + k > hp or (wo-1) stride + k > wp), or sizes past 32-bit indexing (one padded image
+ * hp wp cp, or batch ho wo, at 2^31 or more).  No workspace. */
+BLA_API bla_status bla_conv2d_gathered_bf16(void* stream, const uint16_t* d_a, int rows, const uint16_t* d_p, int batch, int hp, int wp, int cp, int k, int stride,
+                                            int ho, int wo, float* d_out, const float* ep_bias, int ep_bias_stride);
+/* fp32 in memory, the argument meaning of bla_conv2d_forward_batched_f32 / bla_conv2d_backward_batched_f32 (no d_scratch): exactly the composition of the
+ * three entries above in the context workspace, bit for bit -- what bla_gemm_f32_as_bf16 is to bla_gemm_bf16.
+ *   forward:        pad(x) and prepare_kernels(kern, 0), then the gathered product with the optional bias.
+ *                   Workspace: B Hp Wp Cp * 2 + F k k Cp * 2 bytes (each part rounded up to 256).
+ *   data gradient:  pad(del_y) in the data-gradient layout and prepare_kernels(kern, 1), then the gathered product at stride 1.  At stride != 1 this is the
+ *                   dilated form (the adjoint of the forward map); BLA_STRICT_REFERENCE=1 refuses it with BLA_ERR_UNDEFINED as the fp32 entry does.
+ *                   Workspace: B (H+k-1) (W+k-1) Fp * 2 + C k k Fp * 2 bytes.
+ *   weight gradient: MATERIALISED.  With Np = B Ho Wo rounded up to 8: one kernel writes the bf16 im2col G [(c,p,q)][(b,i,j)] at pitch Np straight from x,
+ *                   one writes dY16 [f][(b,i,j)] at pitch Np from del_y (tails zero), and del_kern [F][C k k] = dY16 . G^T is bla_gemm_bf16's fast nt
+ *                   product with m = F, n = C k k, k = Np (bla_gemm_last_kernel() names it).  Workspace: (F + C k k) Np * 2 bytes.
+ * Either output of the backward entry may be NULL; its workspace is the larger of the two gradients' (they run one behind the other on the stream).
+ * Pure argument errors (NULL pointers, extents <= 0, stride < 1) answer BLA_ERR_INVALID before the device is asked for; outputs are untouched after any
+ * refusal.  These calls may grow the workspace: run once eagerly, with shapes at least as large, before capturing into a graph. */
+BLA_API bla_status bla_conv2d_forward_batched_f32_as_bf16(void* stream, const float* d_x, const float* d_kern, float* d_out, int batch, int h, int w, int k,
+                                                          int c_in, int f_n, int stride, const float* ep_bias, int ep_bias_stride);
+BLA_API bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern,
+                                                           float* d_del_x, int batch, int h, int w, int k, int c_in, int f_n, int stride);
 /* What the last bla_conv2d_* call launched (host side only, as bla_gemm_last_kernel): reset on entry to every forward / backward call, one token per product
  * in launch order, separated by spaces.  A token is <role>:<path>[/<attribute>...]:
  *   role   fwd, wgrad, dgrad, dgrad.dil (the data gradient on a zero-dilated del_y); pair (both gradients in one launch of the tiled kernels, weight
