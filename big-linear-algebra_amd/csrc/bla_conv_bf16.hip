@@ -341,6 +341,23 @@ bla_status launch_wgrad_operand(hipStream_t s, const WgradArgs& a) {
 	return BLA_OK;
 }
 
+// The materialised weight gradient in the workspace at `base`: [dY16 | G | the product's partial tiles], each part rounded up to 256 bytes.
+// splits: gemm_bf16_launch_splitk's (1 = the unsplit product)
+bla_status launch_wgrad(hipStream_t s, unsigned char* base, const float* d_del_y, const float* d_x, float* d_del_kern, int h, int w, int k, int c_in, int f_n, int stride,
+                        const Same& g, int n, int splits) {
+	const int np = round8(n), ckk = c_in * k * k;
+	const size_t dy_bytes = round_up((size_t)f_n * np * 2, 256), g_bytes = round_up((size_t)ckk * np * 2, 256);
+	uint16_t* dy16 = (uint16_t*)base;
+	uint16_t* G = (uint16_t*)(base + dy_bytes);
+	WgradArgs a{d_del_y, dy16, f_n, n, np, c_in, h, w, k, stride, g.wo, g.ho * g.wo, g.pt, g.pl};
+	bla_status st;
+	if ((st = launch_wgrad_operand<false>(s, a)) != BLA_OK) return st;
+	a.src = d_x; a.dst = G; a.rows = ckk;
+	if ((st = launch_wgrad_operand<true>(s, a)) != BLA_OK) return st;
+	// del_kern [F][C k k] = dY16 [F][np] . G [C k k][np]^T: rows of G in (c, p, q) order, so the result is already [F][C][k][k]
+	return gemm_bf16_launch_splitk(s, 0, 1, f_n, ckk, np, dy16, np, G, np, d_del_kern, ckk, BLA_C_F32, nullptr, base + dy_bytes + g_bytes, splits);
+}
+
 size_t padded_bytes(int batch, int hp, int wp, int cp) { return round_up((size_t)batch * hp * wp * cp * 2, 256); }
 size_t kernels_bytes(int rows, int k, int inner_p) { return round_up((size_t)rows * k * k * inner_p * 2, 256); }
 
@@ -448,16 +465,7 @@ bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const float* d_
 	if (st != BLA_OK) return st;
 	unsigned char* base = (unsigned char*)ws;
 	hipStream_t s = pick_stream(stream);
-	if (d_del_kern) {
-		uint16_t* dy16 = (uint16_t*)base;
-		uint16_t* G = (uint16_t*)(base + dy_bytes);
-		WgradArgs a{d_del_y, dy16, f_n, (int)n, np, c_in, h, w, k, stride, g.wo, g.ho * g.wo, g.pt, g.pl};
-		if ((st = launch_wgrad_operand<false>(s, a)) != BLA_OK) return st;
-		a.src = d_x; a.dst = G; a.rows = ckk;
-		if ((st = launch_wgrad_operand<true>(s, a)) != BLA_OK) return st;
-		// del_kern [F][C k k] = dY16 [F][np] . G [C k k][np]^T: rows of G in (c, p, q) order, so the result is already [F][C][k][k]
-		if ((st = gemm_bf16_launch(s, 0, 1, f_n, ckk, np, dy16, np, G, np, d_del_kern, ckk, BLA_C_F32, nullptr, nullptr)) != BLA_OK) return st;
-	}
+	if (d_del_kern && (st = launch_wgrad(s, base, d_del_y, d_x, d_del_kern, h, w, k, c_in, f_n, stride, g, (int)n, 1)) != BLA_OK) return st;
 	if (d_del_x) {
 		uint16_t* P = (uint16_t*)base;
 		uint16_t* A = (uint16_t*)(base + p_bytes);
@@ -466,6 +474,26 @@ bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const float* d_
 		if ((st = launch_gathered(s, A, c_in, P, batch, L.hp, L.wp, fp, k, 1, h, w, d_del_x, nullptr, 0)) != BLA_OK) return st;
 	}
 	return BLA_OK;
+}
+
+bla_status bla_conv2d_weight_gradient_batched_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, float* d_del_kern, int batch, int h, int w, int k, int c_in,
+                                                          int f_n, int stride, int splits) {
+	const char* who = "bla_conv2d_weight_gradient_batched_f32_as_bf16";
+	BLA_REQUIRE(d_del_y && d_x && d_del_kern, BLA_ERR_INVALID, "%s: NULL pointer", who);
+	BLA_REQUIRE(splits >= 0, BLA_ERR_INVALID, "%s: splits %d", who, splits);
+	bla_status st = check_conv(who, batch, h, w, k, c_in, f_n, stride);
+	if (st != BLA_OK) return st;
+	const Same g = same_geometry(h, w, k, stride);
+	const long n = (long)batch * g.ho * g.wo;
+	BLA_REQUIRE(n < (1L << 31) - 128 && (long)c_in * k * k < (1L << 31), BLA_ERR_INVALID, "%s: %ld output pixels exceed 32-bit indexing", who, n);
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	const int np = round8((int)n), ckk = c_in * k * k;
+	const size_t dy_bytes = round_up((size_t)f_n * np * 2, 256), g_bytes = round_up((size_t)ckk * np * 2, 256);
+	void* ws = nullptr;
+	st = ensure_workspace(dy_bytes + g_bytes + gemm_bf16_splitk_partial_bytes(f_n, ckk, np, splits), &ws);
+	if (st != BLA_OK) return st;
+	return launch_wgrad(pick_stream(stream), (unsigned char*)ws, d_del_y, d_x, d_del_kern, h, w, k, c_in, f_n, stride, g, (int)n, splits);
 }
 
 }  // extern "C"

@@ -11,6 +11,9 @@
 //   * v_mfma_f32_32x32x16_bf16: lane l holds A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][col l & 31], j < 8 -- one 16-byte chunk each;
 //     C/D: col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).  Each wave owns 64 x 64 = 2 x 2 such tiles.
 //   * Workgroup -> tile: XCD-aware (the 8 XCDs take contiguous chunks of the tile order), then groups of 8 tile rows walked column by column.
+//   * K-split (SPLIT = true): a grid of tiles x S workgroups; workgroup (tile, s) runs the same slab loop over the slabs [s sps, (s + 1) sps)
+//     and stores its fp32 accumulator tile whole to partial [s][tile][128][128]; gemm_bf16_fold_kernel adds the S partials of an element in ascending s
+//     and runs the epilogue.  No atomics, no arrival counters: the result does not depend on the order in which workgroups run.
 #include "bla_internal.h"
 
 namespace bla {
@@ -35,6 +38,7 @@ struct Bf16Args {
 	const float* bias_row; const float* bias_col;
 	int relu;
 	long sa_r, sa_k, sb_k, sb_c;   // general kernel: element strides of op(A)[r][kk] and op(B)[kk][c]
+	float* partial; int sps;       // K-split: the partial tiles [split][tile][128][128], slabs per split
 };
 
 template <bool C_BF16>
@@ -62,11 +66,13 @@ __device__ __forceinline__ int xcd_tile(int bid, int nwg) {   // bijective for a
 
 constexpr int BM = 128, BN = 128, BK = 64, SLAB_BYTES = BM * BK * 2;
 
-template <bool C_BF16>
+template <bool C_BF16, bool SPLIT>
 __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(Bf16Args p) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // [A slab 16 KiB][B slab 16 KiB]
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	int pid = xcd_tile(blockIdx.x, p.tiles_m * p.tiles_n);
+	const int tiles = p.tiles_m * p.tiles_n;
+	const int split = SPLIT ? blockIdx.x / tiles : 0;        // split-major: the tiles of one split are consecutive workgroups, in the unsplit order
+	int pid = xcd_tile(SPLIT ? blockIdx.x - split * tiles : blockIdx.x, tiles);
 	const int gsz = 8 * p.tiles_n, grp = pid / gsz, first = grp * 8, gm = min(p.tiles_m - first, 8);
 	const int tm = first + (pid % gsz) % gm, tn = (pid % gsz) / gm;
 	const int row0 = tm * BM, col0 = tn * BN;
@@ -93,7 +99,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(Bf16Args p) {
 			for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
 	const int wm = wave >> 1, wn = wave & 1, fr = lane & 31, fh = lane >> 5;
-	for (int kb = 0; kb < p.k; kb += BK) {
+	const int k_begin = SPLIT ? split * p.sps * BK : 0, k_end = SPLIT ? min(p.k, k_begin + p.sps * BK) : p.k;
+	for (int kb = k_begin; kb < k_end; kb += BK) {
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
 			const bool in = kb + kc[i] < p.k;
@@ -121,6 +128,16 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(Bf16Args p) {
 		}
 		__syncthreads();
 	}
+	if (SPLIT) {   // the whole tile, unconditioned: rows past m and columns past n hold the zeros their lanes fetched
+		float* P = p.partial + ((size_t)split * tiles + (size_t)tm * p.tiles_n + tn) * (BM * BN);
+#pragma unroll
+		for (int i = 0; i < 2; ++i)
+#pragma unroll
+			for (int j = 0; j < 2; ++j)
+#pragma unroll
+				for (int r = 0; r < 16; ++r) P[(wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * BN + wn * 64 + j * 32 + fr] = acc[i][j][r];
+		return;
+	}
 #pragma unroll
 	for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -132,6 +149,28 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(Bf16Args p) {
 				if (row < p.m && c < p.n) epilogue_store<C_BF16>(p, row, c, acc[i][j][r]);
 			}
 		}
+}
+
+// The fold of a K-split product: one thread per 4 consecutive columns of one row of C (they lie in one tile: 128 % 4 == 0).  acc starts as partial 0 and
+// takes partials 1 .. S-1 in ascending order, one fp32 add each; then the unsplit kernel's epilogue, on elements inside m x n only.
+template <bool C_BF16>
+__global__ __launch_bounds__(256) void gemm_bf16_fold_kernel(Bf16Args p, int splits) {
+	const int quads = (p.n + 3) >> 2;
+	const long id = (long)blockIdx.x * 256 + threadIdx.x;
+	if (id >= (long)p.m * quads) return;
+	const int r = (int)(id / quads), c = (int)(id % quads) * 4;
+	const size_t per_split = (size_t)p.tiles_m * p.tiles_n * (BM * BN);
+	const float* P = p.partial + ((size_t)(r >> 7) * p.tiles_n + (c >> 7)) * (BM * BN) + (r & 127) * BN + (c & 127);
+	float4 acc = *(const float4*)P;
+#pragma unroll 4
+	for (int s = 1; s < splits; ++s) {
+		const float4 v = *(const float4*)(P + (size_t)s * per_split);
+		acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+	}
+	const float a4[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+	for (int j = 0; j < 4; ++j)
+		if (c + j < p.n) epilogue_store<C_BF16>(p, r, c + j, a4[j]);
 }
 
 // Any shape, pitch, alignment and layout: one output element per thread, 2-byte loads, a k-ascending fp32 fma chain (products of bf16 values are exact).
@@ -273,11 +312,44 @@ size_t tcopy_bytes(bool fast, int transa, int transb, int m, int n, int k) {
 	return (transa ? round_up((size_t)m * k * 2, 256) : 0) + (!transb ? round_up((size_t)n * k * 2, 256) : 0);
 }
 
+// ---- the K-split's plan: pure functions of the shape (include/bla.h states both rules) -----------------------------------------------------------
+struct SplitPlan { int eff, sps; size_t partial_bytes; };
+
+// the automatic rule: the number of splits to ask the partition rule for
+int auto_splits(long tiles, int slabs, int cus) {
+	const long slots = 3L * (cus > 0 ? cus : 256);   // three workgroups share a CU at the kernel's registers and LDS
+	if (tiles >= slots || slabs < 2 * BLA_GEMM_BF16_SPLITK_MIN_SLABS) return 1;
+	const long by_slots = slots / tiles, by_slabs = slabs / BLA_GEMM_BF16_SPLITK_MIN_SLABS;
+	return (int)(by_slots < by_slabs ? by_slots : by_slabs);
+}
+
+SplitPlan split_plan(int m, int n, int k, int splits, int cus) {
+	const long tiles = (long)((m + BM - 1) / BM) * ((n + BN - 1) / BN);
+	const int slabs = (k + BK - 1) / BK;
+	SplitPlan p{1, slabs, 0};
+	if (tiles == 0 || slabs == 0) return p;
+	int S = splits == 0 ? auto_splits(tiles, slabs, cus) : splits;
+	S = S < 1 ? 1 : (S > slabs ? slabs : S);
+	p.sps = (slabs + S - 1) / S;
+	p.eff = (slabs + p.sps - 1) / p.sps;   // no split is empty
+	if (p.eff > 1) p.partial_bytes = (size_t)p.eff * (size_t)tiles * (BM * BN * sizeof(float));
+	return p;
+}
+
 }  // namespace
 
 // the product itself; ws holds tcopy_bytes() bytes (16-byte aligned)
 bla_status gemm_bf16_launch(hipStream_t s, int transa, int transb, int m, int n, int k, const uint16_t* A, int lda, const uint16_t* B, int ldb, void* C, int ldc,
                             int c_type, const bla_gemm_epilogue* ep, unsigned char* ws) {
+	return gemm_bf16_launch_splitk(s, transa, transb, m, n, k, A, lda, B, ldb, C, ldc, c_type, ep, ws, 1);
+}
+
+size_t gemm_bf16_splitk_partial_bytes(int m, int n, int k, int splits) { return split_plan(m, n, k, splits, ctx().num_cus).partial_bytes; }
+
+// the same with the contraction cut into `splits` ranges (0: the automatic rule for the context's CUs; 1: exactly the launch above); ws holds
+// tcopy_bytes() bytes and, behind them at the next multiple of 256, the plan's partial_bytes
+bla_status gemm_bf16_launch_splitk(hipStream_t s, int transa, int transb, int m, int n, int k, const uint16_t* A, int lda, const uint16_t* B, int ldb, void* C, int ldc,
+                                   int c_type, const bla_gemm_epilogue* ep, unsigned char* ws, int splits) {
 	if (m == 0 || n == 0) return BLA_OK;
 	Bf16Args a{};
 	a.C = C; a.m = m; a.n = n; a.k = k; a.ldc = ldc;
@@ -298,15 +370,31 @@ bla_status gemm_bf16_launch(hipStream_t s, int transa, int transb, int m, int n,
 			BLA_REQUIRE(ws, BLA_ERR_INVALID, "bla_gemm_bf16: no workspace");
 			bla_status st = launch_transpose(s, B, ldb, (uint16_t*)ws, k, k, n);
 			if (st != BLA_OK) return st;
-			B = (const uint16_t*)ws; ldb = k;
+			B = (const uint16_t*)ws; ldb = k; ws += round_up((size_t)n * k * 2, 256);
 		}
 		a.A = A; a.B = B; a.lda = lda; a.ldb = ldb; a.zero = zero_word();
 		a.tiles_m = (m + BM - 1) / BM; a.tiles_n = (n + BN - 1) / BN;
-		const dim3 grid((unsigned)((long)a.tiles_m * a.tiles_n));
-		if (c_type == BLA_C_BF16) hipLaunchKernelGGL(gemm_bf16_nt_kernel<true>, grid, dim3(256), 2 * SLAB_BYTES, s, a);
-		else hipLaunchKernelGGL(gemm_bf16_nt_kernel<false>, grid, dim3(256), 2 * SLAB_BYTES, s, a);
-		BLA_HIP(hipGetLastError());
-		snprintf(name, sizeof name, "gemm_bf16_mfma128x128x64_%s_%s%s%s", lay, ct, transa ? "_tcopyA" : "", !transb ? "_tcopyB" : "");
+		const long tiles = (long)a.tiles_m * a.tiles_n;
+		const SplitPlan plan = split_plan(m, n, k, splits, ctx().num_cus);
+		if (plan.eff == 1) {
+			const dim3 grid((unsigned)tiles);
+			if (c_type == BLA_C_BF16) hipLaunchKernelGGL((gemm_bf16_nt_kernel<true, false>), grid, dim3(256), 2 * SLAB_BYTES, s, a);
+			else hipLaunchKernelGGL((gemm_bf16_nt_kernel<false, false>), grid, dim3(256), 2 * SLAB_BYTES, s, a);
+			BLA_HIP(hipGetLastError());
+			snprintf(name, sizeof name, "gemm_bf16_mfma128x128x64_%s_%s%s%s", lay, ct, transa ? "_tcopyA" : "", !transb ? "_tcopyB" : "");
+		} else {
+			BLA_REQUIRE(ws, BLA_ERR_INVALID, "bla_gemm_bf16_splitk: no workspace");
+			const long quads = (long)m * ((n + 3) / 4);
+			BLA_REQUIRE(tiles * plan.eff < (1L << 31) && (quads + 255) / 256 < (1L << 31), BLA_ERR_INVALID, "bla_gemm_bf16_splitk: %ld tiles x %d splits exceed the grid", tiles, plan.eff);
+			a.partial = (float*)ws; a.sps = plan.sps;
+			hipLaunchKernelGGL((gemm_bf16_nt_kernel<false, true>), dim3((unsigned)(tiles * plan.eff)), dim3(256), 2 * SLAB_BYTES, s, a);
+			BLA_HIP(hipGetLastError());
+			const dim3 fold((unsigned)((quads + 255) / 256));
+			if (c_type == BLA_C_BF16) hipLaunchKernelGGL(gemm_bf16_fold_kernel<true>, fold, dim3(256), 0, s, a, plan.eff);
+			else hipLaunchKernelGGL(gemm_bf16_fold_kernel<false>, fold, dim3(256), 0, s, a, plan.eff);
+			BLA_HIP(hipGetLastError());
+			snprintf(name, sizeof name, "gemm_bf16_mfma128x128x64_%s_%s%s%s_splitk%d", lay, ct, transa ? "_tcopyA" : "", !transb ? "_tcopyB" : "", plan.eff);
+		}
 	} else {
 		a.A = A; a.B = B;
 		a.sa_r = transa ? 1 : lda; a.sa_k = transa ? lda : 1;
@@ -377,6 +465,36 @@ bla_status bla_gemm_bf16(void* stream, int transa, int transb, int m, int n, int
 		if (st != BLA_OK) return st;
 	}
 	return gemm_bf16_launch(pick_stream(stream), transa, transb, m, n, k, d_a, lda, d_b, ldb, d_c, ldc, c_type, ep, (unsigned char*)ws);
+}
+
+bla_status bla_gemm_bf16_splitk_plan(int m, int n, int k, int splits, int cus, int* eff_splits, int* slabs_per_split, size_t* partial_bytes) {
+	BLA_REQUIRE(m >= 0 && n >= 0 && k >= 0 && splits >= 0, BLA_ERR_INVALID, "bla_gemm_bf16_splitk_plan: negative argument (m %d n %d k %d splits %d)", m, n, k, splits);
+	const SplitPlan p = split_plan(m, n, k, splits, cus);
+	if (eff_splits) *eff_splits = p.eff;
+	if (slabs_per_split) *slabs_per_split = p.sps;
+	if (partial_bytes) *partial_bytes = p.partial_bytes;
+	return BLA_OK;
+}
+
+bla_status bla_gemm_bf16_splitk(void* stream, int transa, int transb, int m, int n, int k, const uint16_t* d_a, int lda, const uint16_t* d_b, int ldb,
+                                void* d_c, int ldc, int c_type, const bla_gemm_epilogue* ep, int splits) {
+	BLA_REQUIRE(splits >= 0, BLA_ERR_INVALID, "bla_gemm_bf16_splitk: splits %d", splits);
+	bla_status st = check_epilogue(ep);
+	if (st != BLA_OK) return st;
+	BLA_REQUIRE(c_type == BLA_C_F32 || c_type == BLA_C_BF16, BLA_ERR_INVALID, "bla_gemm_bf16_splitk: c_type %d", c_type);
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	transa = transa != 0; transb = transb != 0;
+	st = check_product(m, n, k, d_a, lda, transa, d_b, ldb, transb, d_c, ldc);
+	if (st != BLA_OK) return st;
+	void* ws = nullptr;
+	const bool fast = fast_path(k, d_a, lda, d_b, ldb);
+	const size_t need = tcopy_bytes(fast, transa, transb, m, n, k) + (fast ? gemm_bf16_splitk_partial_bytes(m, n, k, splits) : 0);   // off the fast path nothing is split
+	if (need) {
+		st = ensure_workspace(need, &ws);
+		if (st != BLA_OK) return st;
+	}
+	return gemm_bf16_launch_splitk(pick_stream(stream), transa, transb, m, n, k, d_a, lda, d_b, ldb, d_c, ldc, c_type, ep, (unsigned char*)ws, splits);
 }
 
 bla_status bla_gemm_f32_as_bf16(void* stream, int transa, int transb, int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb,

@@ -115,6 +115,12 @@ void gemm_note_last_kernel(const char* name);
 // ws: the bytes the transposed copies of nn / tn / tt need, 16-byte aligned (nt: none, may be NULL)
 bla_status gemm_bf16_launch(hipStream_t s, int transa, int transb, int m, int n, int k, const uint16_t* A, int lda, const uint16_t* B, int ldb, void* C, int ldc,
                             int c_type, const bla_gemm_epilogue* ep, unsigned char* ws);
+// its K-split form (bla_gemm_bf16_splitk; bla_conv_bf16.hip's weight-gradient entry launches the nt form): splits as in bla.h (0 = the automatic rule for
+// the context's CUs, 1 = exactly gemm_bf16_launch); ws: the transposed copies' bytes, then -- 256-byte aligned -- gemm_bf16_splitk_partial_bytes() bytes
+// of partial tiles (what bla_gemm_bf16_splitk_plan answers for a fast-path call with the context's CUs; 0 when the plan does not split)
+bla_status gemm_bf16_launch_splitk(hipStream_t s, int transa, int transb, int m, int n, int k, const uint16_t* A, int lda, const uint16_t* B, int ldb, void* C, int ldc,
+                                   int c_type, const bla_gemm_epilogue* ep, unsigned char* ws, int splits);
+size_t gemm_bf16_splitk_partial_bytes(int m, int n, int k, int splits);
 
 // bla_gemm_thin.hip: batched products with a short contraction (k <= 64, a multiple of 8; m, n multiples of 32) and a large output, one wave per
 // 32 x (32..128) block straight from global memory; up to three (A, B) pairs accumulate before the one store.  Strides in floats per batch index.

@@ -67,6 +67,9 @@ SIGNATURES = {
     "bla_transpose_b16": (_I, [_VP, _VP, _I, _VP, _I, _I, _I]),
     "bla_gemm_bf16": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, C.POINTER(Epilogue)]),
     "bla_gemm_f32_as_bf16": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, C.POINTER(Epilogue)]),
+    "bla_gemm_bf16_splitk_plan": (_I, [_I] * 5 + [C.POINTER(_I), C.POINTER(_I), C.POINTER(_SZ)]),
+    "bla_gemm_bf16_splitk": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, C.POINTER(Epilogue), _I]),
+    "bla_conv2d_weight_gradient_batched_f32_as_bf16": (_I, [_VP] * 4 + [_I] * 8),
     "bla_conv_bf16_layout": (_I, [_I] * 5 + [C.POINTER(_I)] * 5), "bla_conv_bf16_pad": (_I, [_VP] * 3 + [_I] * 9),
     "bla_conv_bf16_prepare_kernels": (_I, [_VP] * 3 + [_I] * 4), "bla_conv2d_gathered_bf16": (_I, [_VP, _VP, _I, _VP] + [_I] * 8 + [_VP, _VP, _I]),
     "bla_conv2d_forward_batched_f32_as_bf16": (_I, [_VP] * 4 + [_I] * 7 + [_VP, _I]), "bla_conv2d_backward_batched_f32_as_bf16": (_I, [_VP] * 6 + [_I] * 7),
@@ -382,6 +385,29 @@ def gemm_bf16(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, bias_row
     return c
 
 
+def gemm_bf16_splitk_plan(m, n, k, splits=0, cus=0):
+    """(S_eff, slabs per split, partial bytes) of a fast-path m x n x k product asked to split `splits` ways (0: the automatic rule for `cus` CUs)."""
+    eff, sps, nbytes = C.c_int(), C.c_int(), C.c_size_t()
+    check(lib().bla_gemm_bf16_splitk_plan(m, n, k, splits, cus, C.byref(eff), C.byref(sps), C.byref(nbytes)))
+    return eff.value, sps.value, nbytes.value
+
+
+def gemm_bf16_splitk(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, bias_row=None, bias_col=None, act=ACT_NONE, stream=None,
+                     m=None, n=None, k=None, lda=None, ldb=None, ldc=None, splits=0):
+    """gemm_bf16 with the contraction cut into `splits` ranges whose partial tiles a second kernel adds in a fixed order (0: the automatic rule)."""
+    if m is None:
+        m = a.shape[1] if transa else a.shape[0]
+    if k is None:
+        k = a.shape[0] if transa else a.shape[1]
+    if n is None:
+        n = b.shape[0] if transb else b.shape[1]
+    ep = Epilogue(alpha=alpha, beta=beta, bias_row=_ptr(bias_row), bias_col=_ptr(bias_col), act=act)
+    c_type = C_BF16 if c.dtype == np.uint16 else C_F32
+    check(lib().bla_gemm_bf16_splitk(stream, int(transa), int(transb), m, n, k, _ptr(a), lda or a.ld, _ptr(b), ldb or b.ld, _ptr(c), ldc or c.ld,
+                                     c_type, C.byref(ep), splits))
+    return c
+
+
 # ---- mixed-precision convolution (include/bla.h: bf16 operands, fp32 accumulation) ---------------------------------------------------------------------
 def conv_bf16_layout(h, w, k, stride, data_gradient=False):
     """(hp, wp, top, left, dilate) of the padded channel-last operand: the forward input, or (data_gradient) del_y dilated by the stride."""
@@ -417,3 +443,9 @@ def conv2d_forward_as_bf16(x, kern, out, batch, h, w, k, c_in, f_n, stride, ep_b
 def conv2d_backward_as_bf16(del_y, x, kern, del_kern, del_x, batch, h, w, k, c_in, f_n, stride, stream=None):
     """Both gradients of the same convolution in bf16 (either output may be None): the materialised weight gradient, the gathered data gradient."""
     check(lib().bla_conv2d_backward_batched_f32_as_bf16(stream, _ptr(del_y), _ptr(x), _ptr(kern), _ptr(del_kern), _ptr(del_x), batch, h, w, k, c_in, f_n, stride))
+
+
+def conv2d_weight_gradient_as_bf16(del_y, x, del_kern, batch, h, w, k, c_in, f_n, stride, splits=0, stream=None):
+    """The bf16 weight gradient alone, its product K-split (splits: 0 = the automatic rule, 1 = the backward entry's own product)."""
+    check(lib().bla_conv2d_weight_gradient_batched_f32_as_bf16(stream, _ptr(del_y), _ptr(x), _ptr(del_kern), batch, h, w, k, c_in, f_n, stride, splits))
+    return del_kern

@@ -225,6 +225,35 @@ BLA_API bla_status bla_gemm_bf16(void* stream, int transa, int transb, int m, in
  * trades 16 mantissa bits of the operands for the bf16 matrix rate.  Epilogue and workspace rules: bla_gemm_bf16's. */
 BLA_API bla_status bla_gemm_f32_as_bf16(void* stream, int transa, int transb, int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb,
                                         float* d_c, int ldc, const bla_gemm_epilogue* ep);
+/* K-split of the fast path: for a product with few 128 x 128 output tiles and a long contraction (every weight gradient), which the unsplit
+ * kernel runs on tiles_m tiles_n workgroups however many compute units there are.  An addition: bla_gemm_bf16 never splits.
+ *
+ * Partition rule.  slabs = ceil(k / 64).  The requested S is clamped to [1, slabs]; sps = ceil(slabs / S) slabs per split; S_eff = ceil(slabs / sps), so
+ * no split is empty.  Split s takes k in [s sps 64, min(k, (s + 1) sps 64)).  A grid of tiles x S_eff workgroups runs the unsplit slab loop over its range
+ * and stores its fp32 accumulator tile to partial [s][tile][128][128] in the context workspace, behind the transposed copies; a second kernel then computes
+ * acc = P[0]; acc += P[1]; ... acc += P[S_eff - 1] per element (fp32, ascending s) and runs bla_gemm_bf16's epilogue on it.  No atomics and no arrival
+ * order: the same call gives the same bits every time.  The error bound of the unsplit product holds unchanged.
+ * S_eff == 1 IS bla_gemm_bf16's launch (same kernel, same name, no partials).  A call off the fast path (odd k, misaligned operand, odd pitch) runs the
+ * general kernel unsplit.  With S_eff > 1 bla_gemm_last_kernel() answers the fast path's name with the suffix _splitk<S_eff>, e.g.
+ * gemm_bf16_mfma128x128x64_nt_f32_splitk6.
+ *
+ * Automatic rule (splits = 0), a pure function of tiles = tiles_m tiles_n, slabs and the number of compute units cus (cus <= 0: 256):
+ *     slots = 3 cus                        three workgroups share a compute unit at the kernel's registers and LDS
+ *     S = 1                                when tiles >= slots, or when slabs < 2 BLA_GEMM_BF16_SPLITK_MIN_SLABS
+ *     S = min(floor(slots / tiles), floor(slabs / BLA_GEMM_BF16_SPLITK_MIN_SLABS))   otherwise; then the partition rule.
+ * BLA_GEMM_BF16_SPLITK_MIN_SLABS is the number of slabs below which a partial tile's 128 KB of write-and-read traffic is no longer paid for
+ * (DESIGN 3.20 has the sweep that chose it).
+ *
+ * bla_gemm_bf16_splitk_plan (host only, needs no device): what a fast-path call with these extents launches.  splits >= 1: the partition rule;
+ * splits == 0: the automatic rule for cus compute units.  partial_bytes = S_eff > 1 ? S_eff tiles_m tiles_n 65536 : 0.  Any out pointer may be NULL.
+ * BLA_ERR_INVALID: a negative m, n, k or splits.  m, n or k of 0: S_eff 1, no partials. */
+#define BLA_GEMM_BF16_SPLITK_MIN_SLABS 8
+BLA_API bla_status bla_gemm_bf16_splitk_plan(int m, int n, int k, int splits, int cus, int* eff_splits, int* slabs_per_split, size_t* partial_bytes);
+/* bla_gemm_bf16's argument list, checks and epilogue, plus splits: >= 1 the requested S, 0 the automatic rule with the context's compute units.
+ * splits < 0: BLA_ERR_INVALID before anything is launched, C untouched.  Workspace: bla_gemm_bf16's plus the plan's partial_bytes (the capture rule of
+ * bla_gemm_bf16 applies). */
+BLA_API bla_status bla_gemm_bf16_splitk(void* stream, int transa, int transb, int m, int n, int k, const uint16_t* d_a, int lda, const uint16_t* d_b, int ldb,
+                                        void* d_c, int ldc, int c_type, const bla_gemm_epilogue* ep, int splits);
 
 /* ---- elementwise / broadcast / transpose / reductions: lib/matrix.c:59-205, lib/util.c:7-55 -------------
  * All operate in place on device memory exactly like their reference counterparts operate on host
@@ -373,6 +402,15 @@ BLA_API bla_status bla_conv2d_forward_batched_f32_as_bf16(void* stream, const fl
                                                           int c_in, int f_n, int stride, const float* ep_bias, int ep_bias_stride);
 BLA_API bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern,
                                                            float* d_del_x, int batch, int h, int w, int k, int c_in, int f_n, int stride);
+/* The weight gradient alone, its product K-split: the two operand passes of the backward entry above (dY16 and G at pitch Np, unchanged) into the context
+ * workspace, then del_kern [F][C k k] = dY16 . G^T through bla_gemm_bf16_splitk's nt launch with m = F, n = C k k, k = Np and `splits` (0 = the automatic
+ * rule, 1 = exactly the backward entry's weight gradient) -- that composition, bit for bit; bla_gemm_last_kernel() names the product, with _splitk<S_eff>
+ * when it was split.  The product has ceil(F / 128) ceil(C k k / 128) output tiles over a contraction of B Ho Wo, so unsplit it occupies a handful of
+ * compute units; the backward entry is not changed, and a caller who wants the fast backward pass calls this entry, then the backward entry with
+ * d_del_kern = NULL.  Workspace: (F + C k k) Np * 2 bytes plus the plan's partial_bytes.  BLA_ERR_INVALID before the device is asked for: a NULL del_y,
+ * x or del_kern, splits < 0, an extent <= 0, stride < 1; del_kern is untouched after any refusal. */
+BLA_API bla_status bla_conv2d_weight_gradient_batched_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, float* d_del_kern, int batch, int h, int w,
+                                                                  int k, int c_in, int f_n, int stride, int splits);
 /* What the last bla_conv2d_* call launched (host side only, as bla_gemm_last_kernel): reset on entry to every forward / backward call, one token per product
  * in launch order, separated by spaces.  A token is <role>:<path>[/<attribute>...]:
  *   role   fwd, wgrad, dgrad, dgrad.dil (the data gradient on a zero-dilated del_y); pair (both gradients in one launch of the tiled kernels, weight
