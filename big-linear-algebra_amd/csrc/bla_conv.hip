@@ -42,16 +42,14 @@ void conv_plan_note(const char* fmt, ...) {
 }
 void conv_plan_begin() { conv_plan_note("%s%s:", g_plan_len ? " " : "", g_plan_role); }
 
-struct Geometry { int ho, wo, pt, pl; };
-
-// TF "SAME" geometry exactly as lib/conv.c:13-28,55-56 computes it (ceil on a float quotient).
-static Geometry same_geometry(int h, int w, int k, int s) {
+// bla_internal.h
+Geometry same_geometry(int h, int w, int k, int s) {
 	Geometry g;
-	int vpad = (int)((ceil(((float)h) / s) - 1) * s + k - h);
-	if (vpad < 0) vpad = 0;
-	int hpad = (int)((ceil(((float)w) / s) - 1) * s + k - w);
-	if (hpad < 0) hpad = 0;
-	g.pt = vpad / 2; g.pl = hpad / 2;
+	g.vpad = (int)((ceil(((float)h) / s) - 1) * s + k - h);
+	if (g.vpad < 0) g.vpad = 0;
+	g.hpad = (int)((ceil(((float)w) / s) - 1) * s + k - w);
+	if (g.hpad < 0) g.hpad = 0;
+	g.pt = g.vpad / 2; g.pl = g.hpad / 2;
 	g.ho = (int)ceil((float)h / s); g.wo = (int)ceil((float)w / s);
 	return g;
 }
@@ -135,8 +133,8 @@ __global__ void __launch_bounds__(kThreads) dilate_kernel(const float* __restric
 	}
 }
 
-// BLA_STRICT_REFERENCE=1: operations the reference leaves undefined are refused instead of given their intended meaning
-static bool strict_reference() {
+// bla_internal.h
+bool strict_reference() {
 	static const bool v = [] { const char* e = getenv("BLA_STRICT_REFERENCE"); return e && e[0] == '1'; }();
 	return v;
 }

@@ -1,8 +1,6 @@
 // bla_conv_bf16.hip -- batched convolution with bf16 operands and fp32 accumulation (include/bla.h, "mixed-precision convolution").
 //
-// The product (conv_bf16_gather_kernel) is gemm_bf16_nt_kernel (bla_gemm_bf16.hip) with a gathered B operand: the same 128 x 128 x 64 tile, the same
-// v_mfma_f32_32x32x16_bf16 fragments, the same 16-byte global_load_lds pieces with the XOR swizzle on the source address, the same XCD-aware tile order and
-// the same zero-word source for lanes outside m, n or K.  What differs:
+// The product (conv_bf16_gather_kernel) is the tile of bla_bf16_tile.h with a gathered B operand and a store of its own:
 //   * B row n is the output pixel (image b, i, j) of the padded channel-last copy P [B][Hp][Wp][Cp]; its k-th element is
 //         P[pixel_base(n) + (p Wp + q) Cp + c],   pixel_base(n) = ((b Hp + i s) Wp + j s) Cp,   k = (p kk + q) Cp + c   (tap-major, channel-minor).
 //     Cp % 8 == 0 makes every 8-element chunk of k one tap's 8 consecutive channels = 16 aligned bytes of P, whatever the stride, kernel and map size; the
@@ -15,29 +13,10 @@
 // Around it: the pad copy (fp32 [B][C][H][W] -> P, a convert-and-transpose through an LDS tile that writes EVERY element of P), the tap-major kernel
 // matrices, and the materialised weight gradient (a bf16 im2col and a bf16 copy of del_y in front of the existing fast nt product).
 #include "bla_internal.h"
-#include <cmath>
+#include "bla_bf16_tile.h"
 
 namespace bla {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {   // bla_f32_to_bf16's rounding
-	uint32_t u = __float_as_uint(f);
-	if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-	return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ uint32_t pack2(float a, float b) { return f32_to_bf16_rne(a) | ((uint32_t)f32_to_bf16_rne(b) << 16); }
-
-__device__ __forceinline__ int xcd_tile(int bid, int nwg) {   // as in bla_gemm_bf16.hip
-	int q = nwg >> 3, r = nwg & 7, x = bid & 7, i = bid >> 3;
-	return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
-
-constexpr int BM = 128, BN = 128, BK = 64, SLAB_BYTES = BM * BK * 2;
 
 struct GatherArgs {
 	const uint16_t* A; const uint16_t* P; float* out; const void* zero;
@@ -48,76 +27,29 @@ struct GatherArgs {
 };
 
 __global__ __launch_bounds__(256) void conv_bf16_gather_kernel(GatherArgs p) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // [A slab 16 KiB][B slab 16 KiB]
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	int pid = xcd_tile(blockIdx.x, p.tiles_m * p.tiles_n);
-	const int gsz = 8 * p.tiles_n, grp = pid / gsz, first = grp * 8, gm = min(p.tiles_m - first, 8);
-	const int tm = first + (pid % gsz) % gm, tn = (pid % gsz) / gm;
-	const int row0 = tm * BM, col0 = tn * BN;
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const Bf16Tile t = bf16_tile_of(blockIdx.x, p.tiles_m, p.tiles_n);
+	const int row0 = t.tm * BM, col0 = t.tn * BN;
 
-	const uint16_t* pa[4]; const uint16_t* pb[4];
-	bool oka[4], okb[4];
-	int kc[2];   // first k of the chunk this lane fetches: piece i takes kc[i & 1] (the swizzle term (row >> 1) & 7 is 4 (i & 1) + (lane >> 4))
+	const uint16_t* pb[4];   // pixel_base of the piece's B row
 #pragma unroll
 	for (int i = 0; i < 4; ++i) {
-		const int row = (wave * 4 + i) * 8 + (lane >> 3);
-		const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-		if (i < 2) kc[i] = chunk * 8;
-		oka[i] = row0 + row < p.rows;
-		okb[i] = col0 + row < p.n;
-		pa[i] = p.A + (size_t)(oka[i] ? row0 + row : 0) * p.K + chunk * 8;
-		const int n = okb[i] ? col0 + row : 0;
+		const int row = col0 + bf16_piece_row(wave, lane, i), n = row < p.n ? row : 0;
 		const int b = n / p.howo, pix = n - b * p.howo, oi = pix / p.wo, oj = pix - oi * p.wo;
 		pb[i] = p.P + (((size_t)b * p.hp + (size_t)oi * p.stride) * p.wp + (size_t)oj * p.stride) * p.cp;
 	}
 	f32x16 acc[2][2];
-#pragma unroll
-	for (int i = 0; i < 2; ++i)
-#pragma unroll
-		for (int j = 0; j < 2; ++j)
-#pragma unroll
-			for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+	bf16_tile_product(lds, {p.A, p.K, p.rows, p.n, p.K, row0, col0, p.zero}, 0, p.K, [&](int i, int kb) {
+		const uint32_t k0 = (uint32_t)(kb + bf16_piece_chunk(lane, i) * 8);   // the same for pieces i and i + 2: two tap offsets per slab
+		const uint32_t tap = __umulhi(k0, p.magic_cp), c = k0 - tap * p.cp;
+		const uint32_t tp = __umulhi(tap, p.magic_kk), tq = tap - tp * p.kk;
+		return pb[i] + (int)((tp * p.wp + tq) * p.cp + c);   // a lane past K has a meaningless offset and never uses it
+	}, acc);
 
-	const int wm = wave >> 1, wn = wave & 1, fr = lane & 31, fh = lane >> 5;
-	for (int kb = 0; kb < p.K; kb += BK) {
-		int off[2]; bool in[2];
-#pragma unroll
-		for (int e = 0; e < 2; ++e) {
-			const uint32_t k0 = (uint32_t)(kb + kc[e]);
-			const uint32_t tap = __umulhi(k0, p.magic_cp), c = k0 - tap * p.cp;
-			const uint32_t tp = __umulhi(tap, p.magic_kk), tq = tap - tp * p.kk;
-			off[e] = (int)((tp * p.wp + tq) * p.cp + c);
-			in[e] = k0 < (uint32_t)p.K;   // a lane past K has a meaningless offset and never uses it
-		}
-#pragma unroll
-		for (int i = 0; i < 4; ++i) {
-			const void* sa = (oka[i] && in[i & 1]) ? (const void*)(pa[i] + kb) : p.zero;
-			const void* sb = (okb[i] && in[i & 1]) ? (const void*)(pb[i] + off[i & 1]) : p.zero;
-			__builtin_amdgcn_global_load_lds((gbl_ptr_t)sa, (lds_ptr_t)(lds + (wave * 4 + i) * 1024), 16, 0, 0);
-			__builtin_amdgcn_global_load_lds((gbl_ptr_t)sb, (lds_ptr_t)(lds + SLAB_BYTES + (wave * 4 + i) * 1024), 16, 0, 0);
-		}
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__syncthreads();
-#pragma unroll
-		for (int s = 0; s < BK / 16; ++s) {
-			bf16x8 fa[2], fb[2];
-			const int g = 2 * s + fh;
-#pragma unroll
-			for (int i = 0; i < 2; ++i) {
-				const int ra = wm * 64 + i * 32 + fr, rb = wn * 64 + i * 32 + fr;
-				fa[i] = *(const bf16x8*)(lds + ra * 128 + ((g ^ ((ra >> 1) & 7)) << 4));
-				fb[i] = *(const bf16x8*)(lds + SLAB_BYTES + rb * 128 + ((g ^ ((rb >> 1) & 7)) << 4));
-			}
-#pragma unroll
-			for (int i = 0; i < 2; ++i)
-#pragma unroll
-				for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-		}
-		__syncthreads();
-	}
 #pragma unroll
 	for (int j = 0; j < 2; ++j) {
-		const int n = col0 + wn * 64 + j * 32 + fr;
+		const int n = col0 + bf16_acc_col(j);
 		if (n >= p.n) continue;
 		const int b = n / p.howo, pix = n - b * p.howo;
 		float* o = p.out + (size_t)b * p.rows * p.howo + pix;
@@ -126,7 +58,7 @@ __global__ __launch_bounds__(256) void conv_bf16_gather_kernel(GatherArgs p) {
 		for (int i = 0; i < 2; ++i)
 #pragma unroll
 			for (int r = 0; r < 16; ++r) {
-				const int row = row0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+				const int row = row0 + bf16_acc_row(i, r);
 				if (row < p.rows) o[(size_t)row * p.howo] = bias ? acc[i][j][r] + bias[row] : acc[i][j][r];
 			}
 	}
@@ -227,33 +159,11 @@ __global__ __launch_bounds__(256) void conv_bf16_wgrad_operand_kernel(WgradArgs 
 	*(uint4*)(a.dst + (size_t)row * a.np + n0) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline size_t round_up(size_t x, size_t to) { return (x + to - 1) / to * to; }
-inline int round8(int x) { return (x + 7) & ~7; }
-
-struct Same { int ho, wo, pt, pl, vpad, hpad; };
-// TF "SAME" geometry exactly as lib/conv.c:13-28,55-56 computes it (ceil on a float quotient)
-Same same_geometry(int h, int w, int k, int s) {
-	Same g;
-	g.vpad = (int)((ceil(((float)h) / s) - 1) * s + k - h);
-	if (g.vpad < 0) g.vpad = 0;
-	g.hpad = (int)((ceil(((float)w) / s) - 1) * s + k - w);
-	if (g.hpad < 0) g.hpad = 0;
-	g.pt = g.vpad / 2; g.pl = g.hpad / 2;
-	g.ho = (int)ceil((float)h / s); g.wo = (int)ceil((float)w / s);
-	return g;
-}
-
 struct Layout16 { int hp, wp, top, left, dilate; };
 Layout16 layout16(int h, int w, int k, int stride, bool dgrad) {
-	const Same g = same_geometry(h, w, k, stride);
+	const Geometry g = same_geometry(h, w, k, stride);
 	if (dgrad) return {h + k - 1, w + k - 1, k - 1 - g.pt, k - 1 - g.pl, stride};
 	return {h + g.vpad, w + g.hpad, g.pt, g.pl, 1};
-}
-
-bool strict_reference() {
-	static const bool v = [] { const char* e = getenv("BLA_STRICT_REFERENCE"); return e && e[0] == '1'; }();
-	return v;
 }
 
 // ---- pure argument checks (no device is asked for) ---------------------------------------------------------------------------------------------------
@@ -341,21 +251,26 @@ bla_status launch_wgrad_operand(hipStream_t s, const WgradArgs& a) {
 	return BLA_OK;
 }
 
-// The materialised weight gradient in the workspace at `base`: [dY16 | G | the product's partial tiles], each part rounded up to 256 bytes.
-// splits: gemm_bf16_launch_splitk's (1 = the unsplit product)
-bla_status launch_wgrad(hipStream_t s, unsigned char* base, const float* d_del_y, const float* d_x, float* d_del_kern, int h, int w, int k, int c_in, int f_n, int stride,
-                        const Same& g, int n, int splits) {
+// The materialised weight gradient's workspace: [dY16 [F][np] | G [C k k][np] | the product's partial tiles], each part rounded up to 256 bytes
+struct WgradLayout { int np, ckk; size_t dy_bytes, g_bytes; };
+WgradLayout wgrad_layout(int f_n, int c_in, int k, int n) {
 	const int np = round8(n), ckk = c_in * k * k;
-	const size_t dy_bytes = round_up((size_t)f_n * np * 2, 256), g_bytes = round_up((size_t)ckk * np * 2, 256);
+	return {np, ckk, round_up((size_t)f_n * np * 2, 256), round_up((size_t)ckk * np * 2, 256)};
+}
+
+// ... in the workspace at `base`.  splits: gemm_bf16_launch_splitk's (1 = the unsplit product)
+bla_status launch_wgrad(hipStream_t s, unsigned char* base, const float* d_del_y, const float* d_x, float* d_del_kern, int h, int w, int k, int c_in, int f_n, int stride,
+                        const Geometry& g, int n, int splits) {
+	const WgradLayout L = wgrad_layout(f_n, c_in, k, n);
 	uint16_t* dy16 = (uint16_t*)base;
-	uint16_t* G = (uint16_t*)(base + dy_bytes);
-	WgradArgs a{d_del_y, dy16, f_n, n, np, c_in, h, w, k, stride, g.wo, g.ho * g.wo, g.pt, g.pl};
+	uint16_t* G = (uint16_t*)(base + L.dy_bytes);
+	WgradArgs a{d_del_y, dy16, f_n, n, L.np, c_in, h, w, k, stride, g.wo, g.ho * g.wo, g.pt, g.pl};
 	bla_status st;
 	if ((st = launch_wgrad_operand<false>(s, a)) != BLA_OK) return st;
-	a.src = d_x; a.dst = G; a.rows = ckk;
+	a.src = d_x; a.dst = G; a.rows = L.ckk;
 	if ((st = launch_wgrad_operand<true>(s, a)) != BLA_OK) return st;
 	// del_kern [F][C k k] = dY16 [F][np] . G [C k k][np]^T: rows of G in (c, p, q) order, so the result is already [F][C][k][k]
-	return gemm_bf16_launch_splitk(s, 0, 1, f_n, ckk, np, dy16, np, G, np, d_del_kern, ckk, BLA_C_F32, nullptr, base + dy_bytes + g_bytes, splits);
+	return gemm_bf16_launch_splitk(s, 0, 1, f_n, L.ckk, L.np, dy16, L.np, G, L.np, d_del_kern, L.ckk, BLA_C_F32, nullptr, base + L.dy_bytes + L.g_bytes, splits);
 }
 
 size_t padded_bytes(int batch, int hp, int wp, int cp) { return round_up((size_t)batch * hp * wp * cp * 2, 256); }
@@ -410,7 +325,7 @@ bla_status bla_conv2d_forward_batched_f32_as_bf16(void* stream, const float* d_x
 	BLA_REQUIRE(d_x && d_kern && d_out, BLA_ERR_INVALID, "%s: NULL pointer", who);
 	bla_status st = check_conv(who, batch, h, w, k, c_in, f_n, stride);
 	if (st != BLA_OK) return st;
-	const Same g = same_geometry(h, w, k, stride);
+	const Geometry g = same_geometry(h, w, k, stride);
 	const Layout16 L = layout16(h, w, k, stride, false);
 	const int cp = round8(c_in);
 	const size_t p_bytes = padded_bytes(batch, L.hp, L.wp, cp);
@@ -443,12 +358,11 @@ bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const float* d_
 		set_error("the data gradient is undefined in the reference for stride %d (_col2im, lib/conv.c:80-135)", stride);
 		return BLA_ERR_UNDEFINED;
 	}
-	const Same g = same_geometry(h, w, k, stride);
+	const Geometry g = same_geometry(h, w, k, stride);
 	const Layout16 L = layout16(h, w, k, stride, true);
 	const int fp = round8(f_n);
 	const long n = (long)batch * g.ho * g.wo;
 	BLA_REQUIRE(n < (1L << 31) - 128 && (long)c_in * k * k < (1L << 31), BLA_ERR_INVALID, "%s: %ld output pixels exceed 32-bit indexing", who, n);
-	const int np = round8((int)n), ckk = c_in * k * k;
 	if (d_del_x) {
 		if ((st = check_pad_shape(batch, f_n, g.ho, g.wo, L.hp, L.wp, L.top, L.left, L.dilate)) != BLA_OK) return st;
 		if ((st = check_gathered_shape(c_in, batch, L.hp, L.wp, fp, k, 1, h, w, 0)) != BLA_OK) return st;
@@ -456,9 +370,9 @@ bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const float* d_
 	st = require_ready();
 	if (st != BLA_OK) return st;
 	// one workspace for both gradients, one behind the other on the stream: [dY16 | G] for the weight gradient, then [P | A] for the data gradient
-	const size_t dy_bytes = round_up((size_t)f_n * np * 2, 256), g_bytes = round_up((size_t)ckk * np * 2, 256);
+	const WgradLayout W = wgrad_layout(f_n, c_in, k, (int)n);
 	const size_t p_bytes = padded_bytes(batch, L.hp, L.wp, fp);
-	const size_t need_w = d_del_kern ? dy_bytes + g_bytes : 0, need_d = d_del_x ? p_bytes + kernels_bytes(c_in, k, fp) : 0;
+	const size_t need_w = d_del_kern ? W.dy_bytes + W.g_bytes : 0, need_d = d_del_x ? p_bytes + kernels_bytes(c_in, k, fp) : 0;
 	if (!need_w && !need_d) return BLA_OK;
 	void* ws = nullptr;
 	st = ensure_workspace(need_w > need_d ? need_w : need_d, &ws);
@@ -483,15 +397,14 @@ bla_status bla_conv2d_weight_gradient_batched_f32_as_bf16(void* stream, const fl
 	BLA_REQUIRE(splits >= 0, BLA_ERR_INVALID, "%s: splits %d", who, splits);
 	bla_status st = check_conv(who, batch, h, w, k, c_in, f_n, stride);
 	if (st != BLA_OK) return st;
-	const Same g = same_geometry(h, w, k, stride);
+	const Geometry g = same_geometry(h, w, k, stride);
 	const long n = (long)batch * g.ho * g.wo;
 	BLA_REQUIRE(n < (1L << 31) - 128 && (long)c_in * k * k < (1L << 31), BLA_ERR_INVALID, "%s: %ld output pixels exceed 32-bit indexing", who, n);
 	st = require_ready();
 	if (st != BLA_OK) return st;
-	const int np = round8((int)n), ckk = c_in * k * k;
-	const size_t dy_bytes = round_up((size_t)f_n * np * 2, 256), g_bytes = round_up((size_t)ckk * np * 2, 256);
+	const WgradLayout W = wgrad_layout(f_n, c_in, k, (int)n);
 	void* ws = nullptr;
-	st = ensure_workspace(dy_bytes + g_bytes + gemm_bf16_splitk_partial_bytes(f_n, ckk, np, splits), &ws);
+	st = ensure_workspace(W.dy_bytes + W.g_bytes + gemm_bf16_splitk_partial_bytes(f_n, W.ckk, W.np, splits), &ws);
 	if (st != BLA_OK) return st;
 	return launch_wgrad(pick_stream(stream), (unsigned char*)ws, d_del_y, d_x, d_del_kern, h, w, k, c_in, f_n, stride, g, (int)n, splits);
 }

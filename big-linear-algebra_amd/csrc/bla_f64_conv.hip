@@ -10,17 +10,6 @@ using namespace bla;
 namespace {
 constexpr int kT = 256;
 unsigned grid_of(size_t n) { size_t b = (n + kT - 1) / kT; return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
-struct Geo { int ho, wo, pt, pl; };
-// TF "SAME" geometry exactly as lib/conv.c:13-28,55-56 computes it (ceil on a float quotient)
-Geo same_geo(int h, int w, int k, int s) {
-	Geo g;
-	int vpad = (int)((ceil(((float)h) / s) - 1) * s + k - h); if (vpad < 0) vpad = 0;
-	int hpad = (int)((ceil(((float)w) / s) - 1) * s + k - w); if (hpad < 0) hpad = 0;
-	g.pt = vpad / 2; g.pl = hpad / 2;
-	g.ho = (int)ceil((float)h / s); g.wo = (int)ceil((float)w / s);
-	return g;
-}
-
 // lib/conv.c:58-74
 __global__ void __launch_bounds__(kT) im2col_f64_kernel(const double* __restrict__ x, double* __restrict__ out, int h, int w, int k, int c_in, int s, int ho, int wo, int pt,
                                                         int pl) {
@@ -134,7 +123,7 @@ extern "C" {
 bla_status bla_im2col_f64(void* stream, const double* d_x, double* d_out, int h, int w, int k, int c_in, int stride) {
 	BLA_ENTER();
 	BLA_REQUIRE(h > 0 && w > 0 && k > 0 && c_in > 0 && stride > 0 && d_x && d_out, BLA_ERR_INVALID, "bad im2col argument");
-	const Geo g = same_geo(h, w, k, stride);
+	const Geometry g = same_geometry(h, w, k, stride);
 	hipLaunchKernelGGL(im2col_f64_kernel, dim3(grid_of((size_t)g.ho * g.wo * k * k * c_in)), dim3(kT), 0, pick_stream(stream), d_x, d_out, h, w, k, c_in, stride, g.ho, g.wo,
 	                   g.pt, g.pl);
 	BLA_HIP(hipGetLastError());
@@ -144,11 +133,8 @@ bla_status bla_im2col_f64(void* stream, const double* d_x, double* d_out, int h,
 bla_status bla_col2im_f64(void* stream, const double* d_cols, double* d_out, int h, int w, int k, int c_n, int stride) {
 	BLA_ENTER();
 	BLA_REQUIRE(h > 0 && w > 0 && k > 0 && c_n > 0 && stride > 0 && d_cols && d_out, BLA_ERR_INVALID, "bad col2im argument");
-	if (stride != 1) {
-		const char* e = getenv("BLA_STRICT_REFERENCE");
-		if (e && e[0] == '1') { set_error("_col2im is undefined for stride %d in the reference (lib/conv.c:80-135)", stride); return BLA_ERR_UNDEFINED; }
-	}
-	const Geo g = same_geo(h, w, k, stride);
+	if (stride != 1 && strict_reference()) { set_error("_col2im is undefined for stride %d in the reference (lib/conv.c:80-135)", stride); return BLA_ERR_UNDEFINED; }
+	const Geometry g = same_geometry(h, w, k, stride);
 	hipLaunchKernelGGL(col2im_f64_kernel, dim3(grid_of((size_t)c_n * h * w)), dim3(kT), 0, pick_stream(stream), d_cols, d_out, h, w, k, c_n, stride, g.ho, g.wo, g.pt, g.pl);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
@@ -166,19 +152,19 @@ bla_status bla_conv_forward_f64(void* stream, const double* d_x, const double* d
 	BLA_ENTER();
 	BLA_REQUIRE(d_x && d_kern && d_im2col && d_kmat && d_product && d_output && f_n > 0, BLA_ERR_INVALID, "bad conv argument");
 	if ((st = bla_im2col_f64(stream, d_x, d_im2col, h, w, k, c_in, stride))) return st;
-	const Geo g = same_geo(h, w, k, stride);
+	const Geometry g = same_geometry(h, w, k, stride);
 	const int hw = g.ho * g.wo, kkc = k * k * c_in;
 	if ((st = bla_kernels_to_matrix_f64(stream, d_kern, d_kmat, f_n, c_in, k))) return st;
 	if ((st = bla_gemm_f64(stream, 0, 0, hw, f_n, kkc, d_im2col, kkc, d_kmat, f_n, d_product, f_n, 1.0, 0.0))) return st;   /* im2col . kernel_matrix, :210 */
 	return bla_reshape_channels_matrix_f64(stream, d_output, d_product, f_n, hw);
 }
 
-/* conv_ddx(), lib/conv.c:214-229 (intended first step); stride != 1: the adjoint (refused under BLA_STRICT_REFERENCE=1) */
+/* conv_ddx(), lib/conv.c:214-229 (intended first step); stride != 1: the adjoint (refused under the strict switch) */
 bla_status bla_conv_backward_f64(void* stream, const double* d_del_y, const double* d_im2col, const double* d_kmat, double* d_del_q, double* d_del_kmat, double* d_del_kern,
                                  double* d_del_col, double* d_del_x, int h, int w, int k, int c_in, int f_n, int stride) {
 	BLA_ENTER();
 	BLA_REQUIRE(d_del_y && d_im2col && d_kmat && d_del_q && d_del_kmat && d_del_kern && d_del_col && d_del_x, BLA_ERR_INVALID, "null operand");
-	const Geo g = same_geo(h, w, k, stride);
+	const Geometry g = same_geometry(h, w, k, stride);
 	const int hw = g.ho * g.wo, kkc = k * k * c_in;
 	if ((st = bla_reshape_matrix_channels_f64(stream, d_del_q, d_del_y, f_n, hw))) return st;
 	if ((st = bla_gemm_f64(stream, 1, 0, kkc, f_n, hw, d_im2col, kkc, d_del_q, f_n, d_del_kmat, f_n, 1.0, 0.0))) return st;   /* :221-222 */

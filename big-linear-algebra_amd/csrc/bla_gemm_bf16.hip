@@ -1,35 +1,14 @@
 // bla_gemm_bf16.hip -- bf16 operands, fp32 accumulation (include/bla.h, "mixed precision"): the conversions, the 16-bit transpose, the product.
 //
-// The fast kernel (gemm_bf16_nt_kernel) is the plain LDS-DMA structure: a 128 x 128 output tile per 256-thread workgroup, 64-deep K slabs, one 32 KiB
-// LDS image, two barriers per slab (stage, wait, barrier, multiply, barrier); several workgroups per CU overlap one another's staging.
-//   * Both operands K-contiguous (A [m][k], B [n][k]).  A slab of an operand is 128 rows x 128 bytes; wave w's i-th global_load_lds_dwordx4 fills the 1 KiB
-//     piece (4w + i) = 8 rows, lane l -> row l >> 3, 16-byte chunk l & 7.  The LDS image stays lane-linear (the DMA writes base + 16 * lane); the swizzle is
-//     on the SOURCE address: LDS chunk c of row r holds global chunk c ^ ((r >> 1) & 7), and the fragment reads apply the same XOR.  With 128-byte rows two
-//     rows share a 256-byte bank row, so the 16 rows a ds_read_b128 lane group reads land on 16 different 16-byte slots.
-//   * Edges: a lane whose row is past m (n) or whose chunk is past k fetches from 256 bytes of zeros the context keeps (zero_word()); no address outside
-//     the operands is ever formed into a load.  k % 8 == 0 makes every chunk wholly inside or wholly outside.  Stores are bounds-checked.
-//   * v_mfma_f32_32x32x16_bf16: lane l holds A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][col l & 31], j < 8 -- one 16-byte chunk each;
-//     C/D: col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).  Each wave owns 64 x 64 = 2 x 2 such tiles.
-//   * Workgroup -> tile: XCD-aware (the 8 XCDs take contiguous chunks of the tile order), then groups of 8 tile rows walked column by column.
+// The fast kernel (gemm_bf16_nt_kernel) is the tile of bla_bf16_tile.h with a dense B [n][k]; its epilogue honours alpha, beta, both biases and ReLU.
 //   * K-split (SPLIT = true): a grid of tiles x S workgroups; workgroup (tile, s) runs the same slab loop over the slabs [s sps, (s + 1) sps)
 //     and stores its fp32 accumulator tile whole to partial [s][tile][128][128]; gemm_bf16_fold_kernel adds the S partials of an element in ascending s
 //     and runs the epilogue.  No atomics, no arrival counters: the result does not depend on the order in which workgroups run.
 #include "bla_internal.h"
+#include "bla_bf16_tile.h"
 
 namespace bla {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
-	uint32_t u = __float_as_uint(f);
-	if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // NaN stays NaN
-	return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
 
 struct Bf16Args {
 	const uint16_t* A; const uint16_t* B; void* C; const void* zero;
@@ -59,93 +38,43 @@ __device__ __forceinline__ void epilogue_store(const Bf16Args& p, int r, int c, 
 	}
 }
 
-__device__ __forceinline__ int xcd_tile(int bid, int nwg) {   // bijective for any count
-	int q = nwg >> 3, r = nwg & 7, x = bid & 7, i = bid >> 3;
-	return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
-
-constexpr int BM = 128, BN = 128, BK = 64, SLAB_BYTES = BM * BK * 2;
-
 template <bool C_BF16, bool SPLIT>
 __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(Bf16Args p) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // [A slab 16 KiB][B slab 16 KiB]
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const int tiles = p.tiles_m * p.tiles_n;
 	const int split = SPLIT ? blockIdx.x / tiles : 0;        // split-major: the tiles of one split are consecutive workgroups, in the unsplit order
-	int pid = xcd_tile(SPLIT ? blockIdx.x - split * tiles : blockIdx.x, tiles);
-	const int gsz = 8 * p.tiles_n, grp = pid / gsz, first = grp * 8, gm = min(p.tiles_m - first, 8);
-	const int tm = first + (pid % gsz) % gm, tn = (pid % gsz) / gm;
-	const int row0 = tm * BM, col0 = tn * BN;
+	const Bf16Tile t = bf16_tile_of(SPLIT ? blockIdx.x - split * tiles : blockIdx.x, p.tiles_m, p.tiles_n);
+	const int row0 = t.tm * BM, col0 = t.tn * BN;
 
-	const uint16_t* pa[4]; const uint16_t* pb[4];
-	int kc[4];   // first k of the chunk this lane fetches for piece i (the same for A and B)
-	bool oka[4], okb[4];
+	const uint16_t* pb[4];
 #pragma unroll
 	for (int i = 0; i < 4; ++i) {
-		const int row = (wave * 4 + i) * 8 + (lane >> 3);
-		const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-		kc[i] = chunk * 8;
-		oka[i] = row0 + row < p.m;
-		okb[i] = col0 + row < p.n;
-		pa[i] = p.A + (size_t)(oka[i] ? row0 + row : 0) * p.lda + kc[i];
-		pb[i] = p.B + (size_t)(okb[i] ? col0 + row : 0) * p.ldb + kc[i];
+		const int row = col0 + bf16_piece_row(wave, lane, i);
+		pb[i] = p.B + (size_t)(row < p.n ? row : 0) * p.ldb + bf16_piece_chunk(lane, i) * 8;
 	}
 	f32x16 acc[2][2];
-#pragma unroll
-	for (int i = 0; i < 2; ++i)
-#pragma unroll
-		for (int j = 0; j < 2; ++j)
-#pragma unroll
-			for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-	const int wm = wave >> 1, wn = wave & 1, fr = lane & 31, fh = lane >> 5;
 	const int k_begin = SPLIT ? split * p.sps * BK : 0, k_end = SPLIT ? min(p.k, k_begin + p.sps * BK) : p.k;
-	for (int kb = k_begin; kb < k_end; kb += BK) {
-#pragma unroll
-		for (int i = 0; i < 4; ++i) {
-			const bool in = kb + kc[i] < p.k;
-			const void* sa = (oka[i] && in) ? (const void*)(pa[i] + kb) : p.zero;
-			const void* sb = (okb[i] && in) ? (const void*)(pb[i] + kb) : p.zero;
-			__builtin_amdgcn_global_load_lds((gbl_ptr_t)sa, (lds_ptr_t)(lds + (wave * 4 + i) * 1024), 16, 0, 0);
-			__builtin_amdgcn_global_load_lds((gbl_ptr_t)sb, (lds_ptr_t)(lds + SLAB_BYTES + (wave * 4 + i) * 1024), 16, 0, 0);
-		}
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__syncthreads();
-#pragma unroll
-		for (int s = 0; s < BK / 16; ++s) {
-			bf16x8 fa[2], fb[2];
-			const int g = 2 * s + fh;
-#pragma unroll
-			for (int i = 0; i < 2; ++i) {
-				const int ra = wm * 64 + i * 32 + fr, rb = wn * 64 + i * 32 + fr;
-				fa[i] = *(const bf16x8*)(lds + ra * 128 + ((g ^ ((ra >> 1) & 7)) << 4));
-				fb[i] = *(const bf16x8*)(lds + SLAB_BYTES + rb * 128 + ((g ^ ((rb >> 1) & 7)) << 4));
-			}
-#pragma unroll
-			for (int i = 0; i < 2; ++i)
-#pragma unroll
-				for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-		}
-		__syncthreads();
-	}
+	bf16_tile_product(lds, {p.A, p.lda, p.m, p.n, p.k, row0, col0, p.zero}, k_begin, k_end, [&](int i, int kb) { return pb[i] + kb; }, acc);
+
 	if (SPLIT) {   // the whole tile, unconditioned: rows past m and columns past n hold the zeros their lanes fetched
-		float* P = p.partial + ((size_t)split * tiles + (size_t)tm * p.tiles_n + tn) * (BM * BN);
+		float* P = p.partial + ((size_t)split * tiles + (size_t)t.tm * p.tiles_n + t.tn) * (BM * BN);
 #pragma unroll
 		for (int i = 0; i < 2; ++i)
 #pragma unroll
 			for (int j = 0; j < 2; ++j)
 #pragma unroll
-				for (int r = 0; r < 16; ++r) P[(wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * BN + wn * 64 + j * 32 + fr] = acc[i][j][r];
+				for (int r = 0; r < 16; ++r) P[bf16_acc_row(i, r) * BN + bf16_acc_col(j)] = acc[i][j][r];
 		return;
 	}
 #pragma unroll
 	for (int i = 0; i < 2; ++i)
 #pragma unroll
 		for (int j = 0; j < 2; ++j) {
-			const int c = col0 + wn * 64 + j * 32 + fr;
+			const int c = col0 + bf16_acc_col(j);
 #pragma unroll
 			for (int r = 0; r < 16; ++r) {
-				const int row = row0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+				const int row = row0 + bf16_acc_row(i, r);
 				if (row < p.m && c < p.n) epilogue_store<C_BF16>(p, row, c, acc[i][j][r]);
 			}
 		}
@@ -255,9 +184,6 @@ __global__ __launch_bounds__(256) void transpose_b16_kernel(const uint16_t* src,
 		}
 	}
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline size_t round_up(size_t x, size_t to) { return (x + to - 1) / to * to; }
 
 bla_status window_args(const void* src, long ld_src, const void* dst, long ld_dst, int rows, int cols, const char* who) {
 	BLA_REQUIRE(rows >= 0 && cols >= 0, BLA_ERR_INVALID, "%s: negative extent %d x %d", who, rows, cols);

@@ -47,6 +47,9 @@ bla_status side_lane_join(hipStream_t main);
 // out[i] = sum_{j<len} m[i*stride + j], i < count (bla_elementwise.hip)
 bla_status window_sum(void* stream, const float* m, int count, int len, int stride, float* out);
 inline hipStream_t pick_stream(void* s) { return s ? (hipStream_t)s : ctx().stream; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline size_t round_up(size_t x, size_t to) { return (x + to - 1) / to * to; }
+inline int round8(int x) { return (x + 7) & ~7; }
 // a device word that is always 0.0f (source address of the zero padding in gathered operands)
 inline const float* zero_word() { return reinterpret_cast<const float*>(ctx().tile_counters + 16384); }
 // Implicit-GEMM convolution over a batch of images on the direct-to-LDS 128x128x16 kernel, B operand gathered (bla_gemm.hip):
@@ -75,6 +78,13 @@ bla_status gather_gemm_classes(hipStream_t s, const GatherProduct& g, int batch,
 // on mode 7 or 3 (whole 128 x 128 tiles: gather_pair_fits); slabs: gather_product_slab_floats floats each (0: none)
 bool gather_pair_fits(int mode, int M, int N);
 bla_status gather_pair_products(hipStream_t s, int batch, const GatherProduct& w, float* w_slab, const GatherProduct& d, float* d_slab);
+
+// bla_conv.hip: TF "SAME" geometry exactly as lib/conv.c:13-28,55-56 computes it (ceil on a float quotient): the output map, the top / left padding and
+// the total vertical / horizontal padding.  Every convolution of the library, fp32, bf16 and f64, takes its geometry from here.
+struct Geometry { int ho, wo, pt, pl, vpad, hpad; };
+Geometry same_geometry(int h, int w, int k, int s);
+// the strict switch of include/bla.h, read once per process: operations the reference leaves undefined are refused instead of given their intended meaning
+bool strict_reference();
 
 // bla_conv.hip: implicit-GEMM convolution with the adds the U-Net puts behind it: out = conv + ep_bias[image * ep_bias_stride + channel];
 // ep_out2 = out + ep_add, both optional.  One image: folded into the store; a batch: one pass behind the product.

@@ -24,7 +24,8 @@ pytestmark = pytest.mark.gpu
 F32, F64, U16, U32 = np.float32, np.float64, np.uint16, np.uint32
 GUARD = 64
 LAYOUTS = ["nn", "nt", "tn", "tt"]
-EXACT_SHAPES = [(1, 1, 8), (127, 129, 72), (128, 128, 64), (129, 127, 1000), (289, 161, 1024), (384, 640, 128), (768, 768, 256)]
+EXACT_SHAPES = [(1, 1, 8), (127, 129, 72), (128, 128, 64), (129, 127, 1000), (289, 161, 1024), (384, 640, 128), (768, 768, 256),
+                (1153, 129, 64)]             # 10 x 2 tiles: the tile order's groups of 8 and of 2 tile rows, ragged both ways
 FAST, GENERAL = "gemm_bf16_mfma128x128x64_", "gemm_bf16_general_"
 
 

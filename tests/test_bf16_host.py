@@ -160,6 +160,24 @@ def test_mutated_accumulation_leaves_the_bound(restated_case, mutation):
     assert (err > c["bound"]).any(), mutation
 
 
+# ---- workgroup -> tile, restated (csrc/bla_bf16_tile.h: xcd_tile, then groups of 8 tile rows walked column by column) -----------------------------------
+def tile_of(bid, tiles_m, tiles_n):
+    nwg = tiles_m * tiles_n
+    q, r, x, i = nwg >> 3, nwg & 7, bid & 7, bid >> 3
+    pid = (x * (q + 1) if x < r else r * (q + 1) + (x - r) * q) + i
+    gsz = 8 * tiles_n
+    first = pid // gsz * 8
+    gm = min(tiles_m - first, 8)
+    return first + (pid % gsz) % gm, (pid % gsz) // gm
+
+
+@pytest.mark.parametrize("tiles_m,tiles_n", [(6, 6), (10, 2), (9, 1), (8, 3), (17, 5), (1, 1)])
+def test_tile_order_hits_every_tile_once(tiles_m, tiles_n):
+    """6 x 6: the largest grid the GPU tests had; 10 x 2 and 9 x 1: a last group of fewer than 8 tile rows (the GPU cases 1153 x 129 and F = 1100)."""
+    hit = sorted(tile_of(bid, tiles_m, tiles_n) for bid in range(tiles_m * tiles_n))
+    assert hit == [(tm, tn) for tm in range(tiles_m) for tn in range(tiles_n)]
+
+
 # ---- without a device ---------------------------------------------------------------------------------------------------------------------------------
 def no_device(pkg):
     import torch

@@ -29,7 +29,8 @@ FAST, GENERAL = "gemm_bf16_mfma128x128x64_", "gemm_bf16_general_"
 #              m    n    k    S
 EXACT_CASES = [(128, 128, 128, 2), (129, 127, 1000, 2), (129, 127, 1000, 3), (129, 127, 1000, 5), (129, 127, 1000, 16),
                (127, 129, 72, 2),            # the second split is a single 8-deep chunk
-               (289, 161, 1024, 7), (1, 1, 8, 4)]
+               (289, 161, 1024, 7), (1, 1, 8, 4),
+               (1153, 129, 192, 3)]          # 10 x 2 tiles: the tile order's groups of 8 and of 2 tile rows, ragged both ways
 
 
 @pytest.fixture(scope="module")

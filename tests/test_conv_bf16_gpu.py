@@ -29,7 +29,8 @@ CASES = [(3, 3, 5, 5, 7, 3, 1),        # Cp = 8, K = 72: a short last slab, a si
          (1, 8, 16, 7, 9, 3, 2),       # stride 2, odd map
          (2, 16, 16, 4, 4, 1, 1),      # 1 x 1: no halo
          (1, 8, 8, 6, 6, 5, 1),        # k = 5
-         (5, 64, 128, 8, 8, 3, 1)]     # several whole tiles, K = 576 = nine whole slabs
+         (5, 64, 128, 8, 8, 3, 1),     # several whole tiles, K = 576 = nine whole slabs
+         (1, 8, 1100, 4, 4, 1, 1)]     # F = 1100: nine row tiles = a group of 8 and a last group of 1 (the tile order's short last group), one ragged pixel tile, K = 8
 IDS = ["B%d_C%d_F%d_%dx%d_k%d_s%d" % c for c in CASES]
 
 
