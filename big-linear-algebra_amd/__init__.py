@@ -8,7 +8,8 @@ from . import build as _build  # noqa: F401
 from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilogue,  # noqa: F401
                      to_device, empty, zeros, sync, ACT_NONE, ACT_RELU, gemm_bf16, to_bf16, from_bf16, C_F32, C_BF16,
                      conv_bf16_layout, conv_bf16_pad, conv_bf16_prepare_kernels, conv2d_gathered_bf16, conv2d_forward_as_bf16,
-                     conv2d_backward_as_bf16, gemm_bf16_splitk_plan, gemm_bf16_splitk, conv2d_weight_gradient_as_bf16)
+                     conv2d_backward_as_bf16, gemm_bf16_splitk_plan, gemm_bf16_splitk, conv2d_weight_gradient_as_bf16,
+                     conv2d_weight_gradient_gathered_bf16, conv2d_backward_gathered_as_bf16)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
@@ -16,4 +17,5 @@ build_native = _build.build_native
 __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Epilogue", "to_device", "empty",
            "zeros", "sync", "build_native", "ACT_NONE", "ACT_RELU", "gemm_bf16", "to_bf16", "from_bf16", "C_F32", "C_BF16",
            "conv_bf16_layout", "conv_bf16_pad", "conv_bf16_prepare_kernels", "conv2d_gathered_bf16", "conv2d_forward_as_bf16",
-           "conv2d_backward_as_bf16", "gemm_bf16_splitk_plan", "gemm_bf16_splitk", "conv2d_weight_gradient_as_bf16"]
+           "conv2d_backward_as_bf16", "gemm_bf16_splitk_plan", "gemm_bf16_splitk", "conv2d_weight_gradient_as_bf16",
+           "conv2d_weight_gradient_gathered_bf16", "conv2d_backward_gathered_as_bf16"]

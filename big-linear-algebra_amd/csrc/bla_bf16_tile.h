@@ -1,5 +1,7 @@
 // bla_bf16_tile.h -- the 128 x 128 x 64 bf16 tile (fp32 accumulation on v_mfma_f32_32x32x16_bf16), device side, once: bla_gemm_bf16.hip's product and
-// bla_conv_bf16.hip's gathered product are both this tile around a B source, a K range and a visitor of the accumulators.
+// bla_conv_bf16.hip's gathered product are both this tile around a B source, a K range and a visitor of the accumulators.  A second slab loop,
+// bf16_tile_product_kmajor, takes both operands K-MAJOR (the implicit weight gradient): the same tile, pieces, barriers and accumulator map around
+// transposed LDS reads.
 //
 // The plain LDS-DMA structure: a 128 x 128 output tile per 256-thread workgroup, 64-deep K slabs, one 32 KiB LDS image, two barriers per slab (stage,
 // wait, barrier, multiply, barrier); several workgroups per CU overlap one another's staging.
@@ -109,6 +111,99 @@ __device__ __forceinline__ void bf16_tile_product(unsigned char* lds, const Bf16
 				const int ra = wm * 64 + i * 32 + fr, rb = wn * 64 + i * 32 + fr;
 				fa[i] = *(const bf16x8*)(lds + ra * 128 + ((g ^ ((ra >> 1) & 7)) << 4));
 				fb[i] = *(const bf16x8*)(lds + SLAB_BYTES + rb * 128 + ((g ^ ((rb >> 1) & 7)) << 4));
+			}
+#pragma unroll
+			for (int i = 0; i < 2; ++i)
+#pragma unroll
+				for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+		}
+		__syncthreads();
+	}
+}
+
+// ---- the slab loop, both operands K-MAJOR -----------------------------------------------------------------------------------------------
+// acc = A[k_begin .. k_end)[row0 .. row0 + 128)^T . B[k_begin .. k_end)[col0 .. col0 + 128): both operands are stored [k][column] with the columns
+// contiguous (the implicit weight gradient contracts over pixels and both its operands are channel-last), and the MFMA fragments -- 8 consecutive k of
+// one column -- come out of LDS through the transposed read ds_read_b64_tr_b16.
+//   * A slab of an operand is [64 k-rows][128 columns] = 256-byte rows, 16 KiB, 16 pieces of 1 KiB = 4 k-rows; wave w issues pieces 4w + i.  The DMA is
+//     lane-linear: lane l of piece pc fills row r = 4 pc + (l >> 4), 16-byte slot l & 15.  The swizzle is again on the SOURCE address: slot c of row r
+//     holds global chunk c ^ x(r), x(r) = ((r & 3) << 2) | ((r >> 2) & 3) = ((l >> 4) << 2) | i, so a lane's column chunk per piece is a loop constant
+//     and what moves from slab to slab is its k-row.  off(row, ch) = 256 row + 16 (ch ^ x(row)).
+//   * Fragment of k-step s (< 4) for the 32-column block at chunk cb: lane L needs column L & 31 at k = 16 s + 8 (L >> 5) + j, j < 8: two transposed
+//     reads t = 0, 1 of the 4-row x 16-column block at row r0 = 16 s + 8 (L >> 5) + 4 t, chunk c0 = cb + 2 ((L >> 4) & 1); with L & 15 = 4 q + p the lane
+//     supplies off(r0 + q, c0 + (p >> 1)) + 8 (p & 1) and receives column L & 15 of the block, row q in element q: read t is fragment elements 4t .. 4t+3.
+//     x(r0 + q) = (q << 2) | (2 (L >> 5) + t) does not depend on s: a lane has one address per (block, t) and adds 4096 s.  A and B are read the same
+//     way, so their k order agrees by construction.  Every lane of every wave reads (no lane-dependent branch: the instruction needs EXEC all ones).
+//   * Edges as above: a chunk whose first column is at or past m (n), or whose k-row is at or past k, comes from the zero word.  m % 8 == 0 and n % 8 == 0
+//     make every chunk wholly inside or wholly outside.
+// What a kernel supplies: a_at(piece i, kb) and b_at(piece i, kb) = the address of this lane's 16-byte chunk of A (B) for piece i of the slab at kb,
+// i.e. k-row kb + bf16_kmajor_row(wave, lane, i), first column row0 (col0) + 8 bf16_kmajor_chunk(lane, i); asked for regardless, so they must not load.
+// next_slab() runs once per slab, behind its eight DMAs and in front of the wait for them: a kernel whose sources keep per-slab state (the convolution's
+// pixel offsets) moves it on there, under the loads' latency; kb rises by BK from k_begin.
+__device__ __forceinline__ int bf16_kmajor_row(int wave, int lane, int i) { return (wave * 4 + i) * 4 + (lane >> 4); }
+__device__ __forceinline__ int bf16_kmajor_chunk(int lane, int i) { return (lane & 15) ^ (((lane >> 4) << 2) | i); }
+
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ bf16x8 bf16_kmajor_fragment(unsigned char* lds, int off0, int off1) {   // the two transposed reads of one fragment
+	const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(lds + off0));
+	const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(lds + off1));
+	const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+	return __builtin_bit_cast(bf16x8, v);
+}
+
+struct Bf16KmajorOperands { int m, n, k, row0, col0; const void* zero; };   // m, n: the operands' column extents, multiples of 8; k: their k-rows
+
+template <class ASource, class BSource, class NextSlab>
+__device__ __forceinline__ void bf16_tile_product_kmajor(unsigned char* lds, const Bf16KmajorOperands& t, int k_begin, int k_end, ASource&& a_at, BSource&& b_at,
+                                                         NextSlab&& next_slab, f32x16 (&acc)[2][2]) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	bool oka[4], okb[4];
+	int kr[4];   // this lane's k-row within the slab, per piece
+#pragma unroll
+	for (int i = 0; i < 4; ++i) {
+		kr[i] = bf16_kmajor_row(wave, lane, i);
+		oka[i] = t.row0 + bf16_kmajor_chunk(lane, i) * 8 < t.m;
+		okb[i] = t.col0 + bf16_kmajor_chunk(lane, i) * 8 < t.n;
+	}
+#pragma unroll
+	for (int i = 0; i < 2; ++i)
+#pragma unroll
+		for (int j = 0; j < 2; ++j)
+#pragma unroll
+			for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+	// the fragment addresses at k-step 0: [operand block i][read t]
+	const int wm = wave >> 1, wn = wave & 1, fh = lane >> 5, g16 = (lane >> 4) & 1, q = (lane & 15) >> 2, p = lane & 3;
+	int ra[2][2], rb[2][2];
+#pragma unroll
+	for (int i = 0; i < 2; ++i)
+#pragma unroll
+		for (int tt = 0; tt < 2; ++tt) {
+			const int row = 8 * fh + 4 * tt + q, x = (q << 2) | (2 * fh + tt);
+			ra[i][tt] = 256 * row + 16 * ((wm * 8 + i * 4 + 2 * g16 + (p >> 1)) ^ x) + 8 * (p & 1);
+			rb[i][tt] = SLAB_BYTES + 256 * row + 16 * ((wn * 8 + i * 4 + 2 * g16 + (p >> 1)) ^ x) + 8 * (p & 1);
+		}
+
+	for (int kb = k_begin; kb < k_end; kb += BK) {
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			const bool in = kb + kr[i] < t.k;
+			const void* a = a_at(i, kb);   // formed in front of the choice, not inside it: a select per address, no branch among the DMAs
+			const void* b = b_at(i, kb);
+			bf16_stage16((oka[i] && in) ? a : t.zero, lds + (wave * 4 + i) * 1024);
+			bf16_stage16((okb[i] && in) ? b : t.zero, lds + SLAB_BYTES + (wave * 4 + i) * 1024);
+		}
+		next_slab();
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		__syncthreads();
+#pragma unroll
+		for (int s = 0; s < BK / 16; ++s) {
+			bf16x8 fa[2], fb[2];
+#pragma unroll
+			for (int i = 0; i < 2; ++i) {
+				fa[i] = bf16_kmajor_fragment(lds, ra[i][0] + 4096 * s, ra[i][1] + 4096 * s);
+				fb[i] = bf16_kmajor_fragment(lds, rb[i][0] + 4096 * s, rb[i][1] + 4096 * s);
 			}
 #pragma unroll
 			for (int i = 0; i < 2; ++i)

@@ -11,7 +11,8 @@
 //   * the store maps (row, n) to out [b][row][pix]: lanes run along n, so a wave's store instruction writes runs of consecutive floats, also in a tile that
 //     straddles two images.
 // Around it: the pad copy (fp32 [B][C][H][W] -> P, a convert-and-transpose through an LDS tile that writes EVERY element of P), the tap-major kernel
-// matrices, and the materialised weight gradient (a bf16 im2col and a bf16 copy of del_y in front of the existing fast nt product).
+// matrices, the materialised weight gradient (a bf16 im2col and a bf16 copy of del_y in front of the existing fast nt product), and the implicit weight
+// gradient (conv_bf16_wgrad_kernel): the k-major tile on the two padded copies a backward pass has anyway, K-split with a fixed-order fold.
 #include "bla_internal.h"
 #include "bla_bf16_tile.h"
 
@@ -159,6 +160,94 @@ __global__ __launch_bounds__(256) void conv_bf16_wgrad_operand_kernel(WgradArgs 
 	*(uint4*)(a.dst + (size_t)row * a.np + n0) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
 }
 
+// ---- the implicit weight gradient: no operand pass of its own ------------------------------------------------------------------------------
+//   D[f][(p k + q) Cp + c] = sum_n Q[b][top + i d][left + j d][f] . P[b][i s + p][j s + q][c],   n = (b, i, j) over the N = B Ho Wo output pixels
+// Q is the data gradient's padded, dilated channel-last copy of del_y, P the forward pass's padded channel-last copy of x: the contraction runs over
+// pixels, so both operands are k-major with contiguous columns -- bf16_tile_product_kmajor.  k-row n of A is the Fp channels of Q's pixel n, k-row n of B
+// the k x k window of P's pixel n, one tap's Cp channels after the other.  A lane's column chunk is a loop constant (for B: a tap offset and a channel,
+// derived once); its four k-rows per slab are four pixels.  Their (i, j) and their element offsets in Q and P are derived once, by division, for the
+// split's first slab, and then move INCREMENTALLY: the next slab is 64 pixels on, 64 = db Ho Wo + di Wo + dj, so j += dj and i += di with at most one
+// carry each, and the offsets take a constant step plus one correction per carry (host-made constants; adds, compares and selects only -- registers
+// and VALU, no table load in front of a DMA and no multiplication in the loop).  The step runs behind the slab's DMAs, before the wait for them.
+// Every workgroup stores its accumulator tile whole to partial [split][tile][128][128] (also with one split); the fold permutes (tap, c) -> [c][p][q].
+struct WgradImplicitArgs {
+	const uint16_t* Q; const uint16_t* P; float* partial; const void* zero;
+	int fp, ncols, n, tiles_m, tiles_n, sps;      // ncols = kk * kk * cp, n = batch * ho * wo
+	int hq, wq, top, left, dilate;
+	int hp, wp, cp, kk, stride;
+	int ho, wo;
+	int dj, di;                                   // 64 pixels on: j += dj, i += di (+ carries), the image += db (only inside the steps below)
+	int q_step, q_carry_j, q_carry_i;             // Q's element offset: the step without carries, the correction when j wraps, when i wraps
+	int p_step, p_carry_j, p_carry_i;             // P's
+};
+
+__global__ __launch_bounds__(256) void conv_bf16_wgrad_kernel(WgradImplicitArgs a) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int tiles = a.tiles_m * a.tiles_n, split = blockIdx.x / tiles;   // split-major
+	const Bf16Tile t = bf16_tile_of(blockIdx.x - split * tiles, a.tiles_m, a.tiles_n);
+	const int row0 = t.tm * BM, col0 = t.tn * BN;
+	const int k_begin = split * a.sps * BK, k_end = min(a.n, k_begin + a.sps * BK);
+
+	// per piece: the pixel's (i, j) and the element offsets of this lane's chunk in Q and P, for the slab that is staged next.  A k-row at or past n has
+	// meaningless offsets (uint32 arithmetic, wrapping) and the tile never uses them.
+	int oi[4], oj[4];
+	uint32_t oq[4], op[4];
+#pragma unroll
+	for (int i = 0; i < 4; ++i) {
+		const int f0 = row0 + bf16_kmajor_chunk(lane, i) * 8, col = col0 + bf16_kmajor_chunk(lane, i) * 8;
+		const int cc = col < a.ncols ? col : 0, tap = cc / a.cp, c0 = cc - tap * a.cp, tp = tap / a.kk, tq = tap - tp * a.kk;   // cp % 8 == 0: a chunk stays inside one tap
+		const int n = k_begin + bf16_kmajor_row(wave, lane, i), howo = a.ho * a.wo, b = n / howo, pix = n - b * howo;
+		oi[i] = pix / a.wo; oj[i] = pix - oi[i] * a.wo;
+		oq[i] = (((uint32_t)b * a.hq + a.top + oi[i] * a.dilate) * a.wq + a.left + oj[i] * a.dilate) * a.fp + (f0 < a.fp ? f0 : 0);
+		op[i] = (((uint32_t)b * a.hp + oi[i] * a.stride + tp) * a.wp + oj[i] * a.stride + tq) * a.cp + c0;
+	}
+	f32x16 acc[2][2];
+	bf16_tile_product_kmajor(lds, {a.fp, a.ncols, a.n, row0, col0, a.zero}, k_begin, k_end,
+		[&](int i, int) { return a.Q + oq[i]; },
+		[&](int i, int) { return a.P + op[i]; },
+		[&]() {
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				int j = oj[i] + a.dj;
+				const bool cj = j >= a.wo;
+				j -= cj ? a.wo : 0;
+				int r = oi[i] + a.di + (cj ? 1 : 0);
+				const bool ci = r >= a.ho;
+				r -= ci ? a.ho : 0;
+				oj[i] = j; oi[i] = r;
+				oq[i] += (uint32_t)a.q_step + (cj ? (uint32_t)a.q_carry_j : 0u) + (ci ? (uint32_t)a.q_carry_i : 0u);
+				op[i] += (uint32_t)a.p_step + (cj ? (uint32_t)a.p_carry_j : 0u) + (ci ? (uint32_t)a.p_carry_i : 0u);
+			}
+		}, acc);
+
+	// the whole tile, unconditioned: rows from Fp up and columns from k k Cp up hold the zeros their lanes fetched
+	float* T = a.partial + ((size_t)split * tiles + (size_t)t.tm * a.tiles_n + t.tn) * (BM * BN);
+#pragma unroll
+	for (int i = 0; i < 2; ++i)
+#pragma unroll
+		for (int j = 0; j < 2; ++j)
+#pragma unroll
+			for (int r = 0; r < 16; ++r) T[bf16_acc_row(i, r) * BN + bf16_acc_col(j)] = acc[i][j][r];
+}
+
+// The fold: one thread per element of del_kern [F][C][k][k]: acc = partial[0]; acc += partial[1]; ... ascending, at row f, column (p k + q) Cp + c.
+// Rows from F up and channels from C up are never read.  With one split it is a permuting copy.
+__global__ __launch_bounds__(256) void conv_bf16_wgrad_fold_kernel(const float* __restrict__ partial, float* __restrict__ del_kern, int f_n, int c_n, int kk, int cp,
+                                                                   int tiles_m, int tiles_n, int splits) {
+	const int ckk = c_n * kk * kk;
+	const long id = (long)blockIdx.x * 256 + threadIdx.x;
+	if (id >= (long)f_n * ckk) return;
+	const int f = (int)(id / ckk), rest = (int)(id % ckk), c = rest / (kk * kk), tap = rest % (kk * kk);   // tap = p k + q
+	const int col = tap * cp + c;
+	const size_t per_split = (size_t)tiles_m * tiles_n * (BM * BN);
+	const float* T = partial + ((size_t)(f >> 7) * tiles_n + (col >> 7)) * (BM * BN) + (f & 127) * BN + (col & 127);
+	float acc = T[0];
+#pragma unroll 4
+	for (int s = 1; s < splits; ++s) acc += T[(size_t)s * per_split];
+	del_kern[id] = acc;
+}
+
 struct Layout16 { int hp, wp, top, left, dilate; };
 Layout16 layout16(int h, int w, int k, int stride, bool dgrad) {
 	const Geometry g = same_geometry(h, w, k, stride);
@@ -196,6 +285,27 @@ bla_status check_gathered_shape(int rows, int batch, int hp, int wp, int cp, int
 	const long K = (long)k * k * cp, n = (long)batch * ho * wo;
 	BLA_REQUIRE((long)hp * wp * cp < (1L << 31) && (K + 128) * cp < (1L << 31) && n < (1L << 31) - 128 && ((rows + 127L) / 128) * ((n + 127) / 128) < (1L << 31), BLA_ERR_INVALID,
 	            "bla_conv2d_gathered_bf16: the product exceeds 32-bit indexing (padded image %ld elements, K %ld, columns %ld)", (long)hp * wp * cp, K, n);
+	return BLA_OK;
+}
+
+// the implicit weight gradient forms an address for every (output pixel, tap) in P and every output pixel in Q and checks nothing in the kernel
+bla_status check_wgrad_implicit_shape(int hq, int wq, int fp, int top, int left, int dilate, int hp, int wp, int cp, int batch, int k, int stride, int ho, int wo, int f_n,
+                                      int c_n, int splits) {
+	const char* who = "bla_conv2d_weight_gradient_gathered_bf16";
+	BLA_REQUIRE(splits >= 0, BLA_ERR_INVALID, "%s: splits %d", who, splits);
+	BLA_REQUIRE(hq > 0 && wq > 0 && fp > 0 && hp > 0 && wp > 0 && cp > 0 && batch > 0 && k > 0 && ho > 0 && wo > 0 && f_n > 0 && c_n > 0, BLA_ERR_INVALID,
+	            "%s: extent <= 0 (hq %d wq %d fp %d hp %d wp %d cp %d batch %d k %d ho %d wo %d f %d c %d)", who, hq, wq, fp, hp, wp, cp, batch, k, ho, wo, f_n, c_n);
+	BLA_REQUIRE(stride >= 1 && dilate >= 1 && top >= 0 && left >= 0, BLA_ERR_INVALID, "%s: stride %d dilate %d top %d left %d", who, stride, dilate, top, left);
+	BLA_REQUIRE(fp % 8 == 0 && cp % 8 == 0, BLA_ERR_INVALID, "%s: fp %d or cp %d is not a multiple of 8", who, fp, cp);
+	BLA_REQUIRE(fp >= f_n && cp >= c_n, BLA_ERR_INVALID, "%s: fp %d < f_n %d or cp %d < c_n %d", who, fp, f_n, cp, c_n);
+	BLA_REQUIRE((long)(ho - 1) * stride + k <= hp && (long)(wo - 1) * stride + k <= wp, BLA_ERR_INVALID,
+	            "%s: a %d x %d output at stride %d, k %d reads past the %d x %d padded map", who, ho, wo, stride, k, hp, wp);
+	BLA_REQUIRE((long)top + (long)(ho - 1) * dilate < hq && (long)left + (long)(wo - 1) * dilate < wq, BLA_ERR_INVALID,
+	            "%s: the %d x %d gradient at (%d, %d), dilation %d, does not fit %d x %d", who, ho, wo, top, left, dilate, hq, wq);
+	const long n = (long)batch * ho * wo, ncols = (long)k * k * cp;
+	BLA_REQUIRE((long)batch * hq * wq * fp < (1L << 31) && (long)batch * hp * wp * cp < (1L << 31) && n < (1L << 31) - 128 && ncols < (1L << 31) - 128 &&
+	            (long)f_n * c_n * k * k < (1L << 31), BLA_ERR_INVALID,
+	            "%s: the product exceeds 32-bit indexing (Q %ld, P %ld elements, %ld pixels, %ld columns)", who, (long)batch * hq * wq * fp, (long)batch * hp * wp * cp, n, ncols);
 	return BLA_OK;
 }
 
@@ -238,6 +348,47 @@ bla_status launch_gathered(hipStream_t s, const uint16_t* A, int rows, const uin
 	BLA_HIP(hipGetLastError());
 	char name[64];
 	snprintf(name, sizeof name, "conv_bf16_gather128x128x64_s%d", stride);
+	gemm_note_last_kernel(name);
+	return BLA_OK;
+}
+
+// The implicit weight gradient's K-split: DESIGN 3.20's rules on m = F, n = k k Cp, k = N for the context's CUs; the partial tiles exist with one split too
+struct WgradImplicitPlan { int eff, sps, tiles_m, tiles_n; size_t partial_bytes; };
+WgradImplicitPlan wgrad_implicit_plan(int f_n, int k, int cp, int n, int splits) {
+	WgradImplicitPlan p{1, 1, (f_n + BM - 1) / BM, (k * k * cp + BN - 1) / BN, 0};
+	bla_gemm_bf16_splitk_plan(f_n, k * k * cp, n, splits, ctx().num_cus, &p.eff, &p.sps, nullptr);
+	p.partial_bytes = (size_t)p.eff * p.tiles_m * p.tiles_n * (BM * BN * sizeof(float));
+	return p;
+}
+
+// arguments already checked (check_wgrad_implicit_shape); partial holds plan.partial_bytes
+bla_status launch_wgrad_implicit(hipStream_t s, const uint16_t* Q, int hq, int wq, int fp, int top, int left, int dilate, const uint16_t* P, int hp, int wp, int cp, int batch,
+                                 int k, int stride, int ho, int wo, int f_n, int c_n, float* del_kern, float* partial, const WgradImplicitPlan& plan) {
+	WgradImplicitArgs a{};
+	a.Q = Q; a.P = P; a.partial = partial; a.zero = zero_word();
+	a.fp = fp; a.ncols = k * k * cp; a.n = batch * ho * wo; a.tiles_m = plan.tiles_m; a.tiles_n = plan.tiles_n; a.sps = plan.sps;
+	a.hq = hq; a.wq = wq; a.top = top; a.left = left; a.dilate = dilate;
+	a.hp = hp; a.wp = wp; a.cp = cp; a.kk = k; a.stride = stride;
+	a.ho = ho; a.wo = wo;
+	// 64 pixels on: 64 = db ho wo + di wo + dj.  The offsets are uint32 and wrap (db images on may lie past the operand: such a k-row is past n and
+	// unused), so the steps are formed in 64 bits and truncated
+	const long db = BK / (ho * wo), rest = BK % (ho * wo), di = rest / wo, dj = rest % wo;
+	auto wrap = [](long v) { return (int)(uint32_t)(unsigned long)v; };
+	a.di = (int)di; a.dj = (int)dj;
+	a.q_step = wrap(((db * hq + di * dilate) * wq + dj * dilate) * fp);
+	a.q_carry_j = wrap((long)(wq - wo) * dilate * fp);              // j -= wo, i += 1
+	a.q_carry_i = wrap(((long)hq - (long)ho * dilate) * wq * fp);   // i -= ho, the image += 1
+	a.p_step = wrap(((db * hp + di * stride) * wp + dj * stride) * cp);
+	a.p_carry_j = wrap((long)(wp - wo) * stride * cp);
+	a.p_carry_i = wrap(((long)hp - (long)ho * stride) * wp * cp);
+	const long grid = (long)plan.tiles_m * plan.tiles_n * plan.eff, out = (long)f_n * c_n * k * k;
+	BLA_REQUIRE(grid < (1L << 31), BLA_ERR_INVALID, "bla_conv2d_weight_gradient_gathered_bf16: %ld workgroups exceed the grid", grid);
+	hipLaunchKernelGGL(conv_bf16_wgrad_kernel, dim3((unsigned)grid), dim3(256), 2 * SLAB_BYTES, s, a);
+	BLA_HIP(hipGetLastError());
+	hipLaunchKernelGGL(conv_bf16_wgrad_fold_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, s, partial, del_kern, f_n, c_n, k, cp, plan.tiles_m, plan.tiles_n, plan.eff);
+	BLA_HIP(hipGetLastError());
+	char name[64];
+	snprintf(name, sizeof name, "conv_bf16_wgrad128x128x64_s%d_splitk%d", stride, plan.eff);
 	gemm_note_last_kernel(name);
 	return BLA_OK;
 }
@@ -407,6 +558,72 @@ bla_status bla_conv2d_weight_gradient_batched_f32_as_bf16(void* stream, const fl
 	st = ensure_workspace(W.dy_bytes + W.g_bytes + gemm_bf16_splitk_partial_bytes(f_n, W.ckk, W.np, splits), &ws);
 	if (st != BLA_OK) return st;
 	return launch_wgrad(pick_stream(stream), (unsigned char*)ws, d_del_y, d_x, d_del_kern, h, w, k, c_in, f_n, stride, g, (int)n, splits);
+}
+
+bla_status bla_conv2d_weight_gradient_gathered_bf16(void* stream, const uint16_t* d_q, int hq, int wq, int fp, int top, int left, int dilate, const uint16_t* d_p, int hp, int wp,
+                                                    int cp, int batch, int k, int stride, int ho, int wo, int f_n, int c_n, float* d_del_kern, int splits) {
+	BLA_REQUIRE(d_q && d_p && d_del_kern, BLA_ERR_INVALID, "bla_conv2d_weight_gradient_gathered_bf16: NULL pointer");
+	BLA_REQUIRE(aligned16(d_q) && aligned16(d_p), BLA_ERR_INVALID, "bla_conv2d_weight_gradient_gathered_bf16: an operand is not 16-byte aligned");
+	bla_status st = check_wgrad_implicit_shape(hq, wq, fp, top, left, dilate, hp, wp, cp, batch, k, stride, ho, wo, f_n, c_n, splits);
+	if (st != BLA_OK) return st;
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	const WgradImplicitPlan plan = wgrad_implicit_plan(f_n, k, cp, batch * ho * wo, splits);
+	void* ws = nullptr;
+	st = ensure_workspace(plan.partial_bytes, &ws);
+	if (st != BLA_OK) return st;
+	return launch_wgrad_implicit(pick_stream(stream), d_q, hq, wq, fp, top, left, dilate, d_p, hp, wp, cp, batch, k, stride, ho, wo, f_n, c_n, d_del_kern, (float*)ws, plan);
+}
+
+bla_status bla_conv2d_backward_gathered_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x, int batch,
+                                                    int h, int w, int k, int c_in, int f_n, int stride, int splits) {
+	const char* who = "bla_conv2d_backward_gathered_f32_as_bf16";
+	BLA_REQUIRE(d_del_y, BLA_ERR_INVALID, "%s: NULL del_y", who);
+	BLA_REQUIRE(!d_del_kern || d_x, BLA_ERR_INVALID, "%s: the weight gradient needs the forward input", who);
+	BLA_REQUIRE(!d_del_x || d_kern, BLA_ERR_INVALID, "%s: the data gradient needs the kernels", who);
+	BLA_REQUIRE(splits >= 0, BLA_ERR_INVALID, "%s: splits %d", who, splits);
+	bla_status st = check_conv(who, batch, h, w, k, c_in, f_n, stride);
+	if (st != BLA_OK) return st;
+	if (d_del_x && stride != 1 && strict_reference()) {
+		set_error("the data gradient is undefined in the reference for stride %d (_col2im, lib/conv.c:80-135)", stride);
+		return BLA_ERR_UNDEFINED;
+	}
+	if (!d_del_kern && !d_del_x) return BLA_OK;
+	const Geometry g = same_geometry(h, w, k, stride);
+	const Layout16 Lp = layout16(h, w, k, stride, false), Lq = layout16(h, w, k, stride, true);
+	const int cp = round8(c_in), fp = round8(f_n);
+	// the composition's own shape checks, still before the device is asked for
+	if ((st = check_pad_shape(batch, f_n, g.ho, g.wo, Lq.hp, Lq.wp, Lq.top, Lq.left, Lq.dilate)) != BLA_OK) return st;
+	if (d_del_kern) {
+		if ((st = check_pad_shape(batch, c_in, h, w, Lp.hp, Lp.wp, Lp.top, Lp.left, 1)) != BLA_OK) return st;
+		if ((st = check_wgrad_implicit_shape(Lq.hp, Lq.wp, fp, Lq.top, Lq.left, Lq.dilate, Lp.hp, Lp.wp, cp, batch, k, stride, g.ho, g.wo, f_n, c_in, splits)) != BLA_OK) return st;
+	}
+	if (d_del_x && (st = check_gathered_shape(c_in, batch, Lq.hp, Lq.wp, fp, k, 1, h, w, 0)) != BLA_OK) return st;
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	// one workspace: [P | Q | A | partials]
+	WgradImplicitPlan plan{};
+	if (d_del_kern) plan = wgrad_implicit_plan(f_n, k, cp, batch * g.ho * g.wo, splits);
+	const size_t p_bytes = d_del_kern ? padded_bytes(batch, Lp.hp, Lp.wp, cp) : 0, q_bytes = padded_bytes(batch, Lq.hp, Lq.wp, fp);
+	const size_t a_bytes = d_del_x ? kernels_bytes(c_in, k, fp) : 0;
+	void* ws = nullptr;
+	st = ensure_workspace(p_bytes + q_bytes + a_bytes + plan.partial_bytes, &ws);
+	if (st != BLA_OK) return st;
+	unsigned char* base = (unsigned char*)ws;
+	uint16_t* P = (uint16_t*)base;
+	uint16_t* Q = (uint16_t*)(base + p_bytes);
+	uint16_t* A = (uint16_t*)(base + p_bytes + q_bytes);
+	float* partial = (float*)(base + p_bytes + q_bytes + a_bytes);
+	hipStream_t s = pick_stream(stream);
+	if (d_del_kern && (st = launch_pad(s, d_x, P, batch, c_in, h, w, Lp.hp, Lp.wp, Lp.top, Lp.left, 1)) != BLA_OK) return st;
+	if ((st = launch_pad(s, d_del_y, Q, batch, f_n, g.ho, g.wo, Lq.hp, Lq.wp, Lq.top, Lq.left, Lq.dilate)) != BLA_OK) return st;   // once, for both gradients
+	if (d_del_kern && (st = launch_wgrad_implicit(s, Q, Lq.hp, Lq.wp, fp, Lq.top, Lq.left, Lq.dilate, P, Lp.hp, Lp.wp, cp, batch, k, stride, g.ho, g.wo, f_n, c_in, d_del_kern,
+	                                              partial, plan)) != BLA_OK) return st;
+	if (d_del_x) {
+		if ((st = launch_kernels(s, d_kern, A, f_n, c_in, k, 1)) != BLA_OK) return st;
+		if ((st = launch_gathered(s, A, c_in, Q, batch, Lq.hp, Lq.wp, fp, k, 1, h, w, d_del_x, nullptr, 0)) != BLA_OK) return st;
+	}
+	return BLA_OK;
 }
 
 }  // extern "C"

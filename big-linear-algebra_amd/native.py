@@ -70,6 +70,8 @@ SIGNATURES = {
     "bla_gemm_bf16_splitk_plan": (_I, [_I] * 5 + [C.POINTER(_I), C.POINTER(_I), C.POINTER(_SZ)]),
     "bla_gemm_bf16_splitk": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, C.POINTER(Epilogue), _I]),
     "bla_conv2d_weight_gradient_batched_f32_as_bf16": (_I, [_VP] * 4 + [_I] * 8),
+    "bla_conv2d_weight_gradient_gathered_bf16": (_I, [_VP, _VP] + [_I] * 6 + [_VP] + [_I] * 10 + [_VP, _I]),
+    "bla_conv2d_backward_gathered_f32_as_bf16": (_I, [_VP] * 6 + [_I] * 8),
     "bla_conv_bf16_layout": (_I, [_I] * 5 + [C.POINTER(_I)] * 5), "bla_conv_bf16_pad": (_I, [_VP] * 3 + [_I] * 9),
     "bla_conv_bf16_prepare_kernels": (_I, [_VP] * 3 + [_I] * 4), "bla_conv2d_gathered_bf16": (_I, [_VP, _VP, _I, _VP] + [_I] * 8 + [_VP, _VP, _I]),
     "bla_conv2d_forward_batched_f32_as_bf16": (_I, [_VP] * 4 + [_I] * 7 + [_VP, _I]), "bla_conv2d_backward_batched_f32_as_bf16": (_I, [_VP] * 6 + [_I] * 7),
@@ -449,3 +451,15 @@ def conv2d_weight_gradient_as_bf16(del_y, x, del_kern, batch, h, w, k, c_in, f_n
     """The bf16 weight gradient alone, its product K-split (splits: 0 = the automatic rule, 1 = the backward entry's own product)."""
     check(lib().bla_conv2d_weight_gradient_batched_f32_as_bf16(stream, _ptr(del_y), _ptr(x), _ptr(del_kern), batch, h, w, k, c_in, f_n, stride, splits))
     return del_kern
+
+
+def conv2d_weight_gradient_gathered_bf16(q, hq, wq, fp, top, left, dilate, p, hp, wp, cp, batch, k, stride, ho, wo, f_n, c_n, del_kern, splits=0, stream=None):
+    """The implicit bf16 weight gradient on the caller's padded copies: Q = del_y in the data-gradient layout, P = x in the forward layout."""
+    check(lib().bla_conv2d_weight_gradient_gathered_bf16(stream, _ptr(q), hq, wq, fp, top, left, dilate, _ptr(p), hp, wp, cp, batch, k, stride, ho, wo, f_n, c_n,
+                                                         _ptr(del_kern), splits))
+    return del_kern
+
+
+def conv2d_backward_gathered_as_bf16(del_y, x, kern, del_kern, del_x, batch, h, w, k, c_in, f_n, stride, splits=0, stream=None):
+    """Both gradients in bf16 (either output may be None) with del_y padded once for both: the implicit weight gradient, the gathered data gradient."""
+    check(lib().bla_conv2d_backward_gathered_f32_as_bf16(stream, _ptr(del_y), _ptr(x), _ptr(kern), _ptr(del_kern), _ptr(del_x), batch, h, w, k, c_in, f_n, stride, splits))

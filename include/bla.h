@@ -411,6 +411,32 @@ BLA_API bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const f
  * x or del_kern, splits < 0, an extent <= 0, stride < 1; del_kern is untouched after any refusal. */
 BLA_API bla_status bla_conv2d_weight_gradient_batched_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, float* d_del_kern, int batch, int h, int w,
                                                                   int k, int c_in, int f_n, int stride, int splits);
+/* The IMPLICIT weight gradient, on the caller's padded copies -- the two a bf16 backward pass has anyway -- with no operand pass of its own:
+ *   del_kern[f][c][p][q] = sum_{b,i,j} Q[b][top + i dilate][left + j dilate][f] * P[b][i stride + p][j stride + q][c],   i < ho, j < wo
+ * Q [batch][hq][wq][fp] is del_y [batch][f_n][ho][wo] in bla_conv_bf16_layout(.., data_gradient = 1)'s layout (the data gradient's operand), P
+ * [batch][hp][wp][cp] is x in the forward layout; del_kern is fp32 [f_n][c_n][k][k].  Only Q's positions (top + i dilate, left + j dilate) and channels
+ * below f_n, and P's channels below c_n, reach a written element: the holes of the dilation and the padding channels may hold anything.  P's halo is read.
+ * The product contracts over the N = batch ho wo pixels, so both operands are pixel-major with contiguous channels; the kernel is the 128 x 128 x 64 tile
+ * with both operands k-major, its fragments read from LDS transposed (ds_read_b64_tr_b16).  K-split exactly as bla_gemm_bf16_splitk: the partition rule
+ * and the automatic rule on m = f_n, n = k k cp, k = N (bla_gemm_bf16_splitk_plan(f_n, k k cp, N, splits, cus) answers S_eff and the slabs per split);
+ * a grid of tiles x S_eff workgroups stores partial [s][tile][128][128] to the context workspace and a second kernel folds
+ * acc = P[0]; acc += P[1]; ... ascending per element of del_kern, permuting (tap, channel) to [c][p][q].  S_eff = 1 runs the same two launches.  No
+ * atomics, no arrival order: the same call gives the same bits every time.  The error is that of the fp32 accumulation alone: DESIGN 3.20's bound with
+ * k = N.  bla_gemm_last_kernel() answers conv_bf16_wgrad128x128x64_s<stride>_splitk<S_eff> (S_eff = 1 included).
+ * BLA_ERR_INVALID, before the device is asked for and with del_kern untouched: a NULL Q, P or del_kern, splits < 0, an extent <= 0, stride or dilate < 1,
+ * top or left < 0, fp % 8 != 0 or cp % 8 != 0, fp < f_n or cp < c_n, an operand off 16-byte alignment, taps that reach past the padded map
+ * ((ho-1) stride + k > hp or (wo-1) stride + k > wp), a gradient that does not fit Q (top + (ho-1) dilate >= hq or left + (wo-1) dilate >= wq), or sizes
+ * past 32-bit indexing (batch hq wq fp, batch hp wp cp, N + 128 or k k cp + 128 at 2^31 or more).  Workspace: S_eff tiles 65536 bytes. */
+BLA_API bla_status bla_conv2d_weight_gradient_gathered_bf16(void* stream, const uint16_t* d_q, int hq, int wq, int fp, int top, int left, int dilate,
+                                                            const uint16_t* d_p, int hp, int wp, int cp, int batch, int k, int stride, int ho, int wo, int f_n,
+                                                            int c_n, float* d_del_kern, int splits);
+/* bla_conv2d_backward_batched_f32_as_bf16's arguments, input requirements and refusals (either output may be NULL; BLA_STRICT_REFERENCE=1 refuses a stride
+ * != 1 data gradient with BLA_ERR_UNDEFINED), plus splits (< 0: BLA_ERR_INVALID).  Exactly this composition in the context workspace
+ * [P | Q | A | partials], bit for bit: (1) pad(x) in the forward layout, when d_del_kern is given; (2) pad(del_y) ONCE in the data-gradient layout;
+ * (3) bla_conv2d_weight_gradient_gathered_bf16 on (Q, P) with `splits`; (4) prepare_kernels(kern, 1) and bla_conv2d_gathered_bf16 on Q at stride 1, when
+ * d_del_x is given.  An addition: the backward entry above is not changed.  May grow the workspace (the capture rule above applies). */
+BLA_API bla_status bla_conv2d_backward_gathered_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern,
+                                                            float* d_del_x, int batch, int h, int w, int k, int c_in, int f_n, int stride, int splits);
 /* What the last bla_conv2d_* call launched (host side only, as bla_gemm_last_kernel): reset on entry to every forward / backward call, one token per product
  * in launch order, separated by spaces.  A token is <role>:<path>[/<attribute>...]:
  *   role   fwd, wgrad, dgrad, dgrad.dil (the data gradient on a zero-dilated del_y); pair (both gradients in one launch of the tiled kernels, weight
