@@ -11,6 +11,7 @@ hipcc cross-compiles gfx950 without a GPU, so this runs in the CPU-only build co
 import glob
 import importlib.util
 import os
+import re
 import subprocess
 import sys
 
@@ -48,9 +49,23 @@ def _run(cmd):
     return r.stdout
 
 
+def included_headers(path, seen=None):
+    """The headers a source depends on: its quoted #includes, followed transitively (an edit to bla_gather_kernel.h rebuilds bla_gather.hip alone)."""
+    seen = set() if seen is None else seen
+    with open(path, errors="replace") as f:
+        names = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', f.read(), re.M)
+    for n in names:
+        h = os.path.normpath(os.path.join(os.path.dirname(path), n))
+        if not os.path.exists(h):
+            h = os.path.normpath(os.path.join(INCLUDE, n))
+        if os.path.exists(h) and h not in seen:
+            seen.add(h)
+            included_headers(h, seen)
+    return sorted(seen)
+
+
 def build_hip(force=False, verbose=False):
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h"))
     objs = []
     jobs = []
     for s in srcs:
@@ -59,7 +74,7 @@ def build_hip(force=False, verbose=False):
         only = os.environ.get("BLA_BUILD_ONLY")   # experiments on one translation unit: "bla_gather.hip,bla_conv.hip" rebuilds just those (the others keep their objects)
         if only and os.path.basename(s) not in only.split(",") and os.path.exists(o):
             continue
-        if force or _newer(o, [s] + hdrs):
+        if force or _newer(o, [s] + included_headers(s)):
             cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
                    "-DBLA_BUILDING", "-I", INCLUDE, "-c", s, "-o", o] + os.environ.get("BLA_EXTRA_HIPCC_FLAGS", "").split()   # e.g. -DBLA_WSK_DIAG
             jobs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True), cmd))

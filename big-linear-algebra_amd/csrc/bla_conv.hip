@@ -890,7 +890,7 @@ static bool use_tiled_gather(const ConvArgs& a, int batch, int mode) {
 // Which kernel a forward-shaped pass (forward, stride-1 data gradient) runs on, decided in ONE place: conv2d_forward asks it whether the tile store
 // will apply the epilogue, launch_implicit follows it.
 enum FwdPath { FWD_WSK = 0, FWD_TILED_CHECKED = 1, FWD_TILED_PADDED = 3, FWD_TILED_WINDOW = 7 };
-// The image window in LDS (gather mode 7 of bla_gemm_kernel.h): 3x3, stride 1, SAME padding of one pixel, image rows of 16 or 32 pixels, whole 128-pixel
+// The image window in LDS (gather mode 7 of bla_gather_kernel.h): 3x3, stride 1, SAME padding of one pixel, image rows of 16 or 32 pixels, whole 128-pixel
 // tiles inside one image, channels in groups of 16, one pass over K with a workgroup for about every CU.  BLA_CONV_WINDOW=0 keeps the padded copy.
 static bool window_geometry(const ConvArgs& a, int batch) {
 	static const bool off = [] { const char* e = getenv("BLA_CONV_WINDOW"); return e && e[0] == '0'; }();

@@ -1,6 +1,6 @@
-// bla_gather.hip -- implicit-GEMM convolution on the direct-to-LDS GEMM pipeline: the host side of the gathered-operand variants of
-// gemm_f32_glds_kernel (bla_gemm_kernel.h; gather modes in GemmArgs) -- tile / split planning and the launches.  Called from bla_conv.hip.
-#include "bla_gemm_kernel.h"
+// bla_gather.hip -- implicit-GEMM convolution on the direct-to-LDS GEMM pipeline: the gathered-operand kernels (bla_gather_kernel.h; gather modes in
+// GatherArgs) and their host side -- tile / split planning and the launches.  Called from bla_conv.hip.
+#include "bla_gather_kernel.h"
 
 namespace bla {
 
@@ -16,7 +16,7 @@ static bool gather_hs(int mode, int M, int N) {
 	static const bool hs4 = [] { const char* e = getenv("BLA_CONV_HS"); return !(e && e[0] == '1'); }();
 	return use_hs && M % 128 == 0 && N % 128 == 0 && (mode == 3 || (mode == 4 && hs4));
 }
-// mode 4 on the half-slab kernel: a slab's 16 output pixels must sit at the same places relative to its first pixel whatever the slab (bla_gemm_kernel.h)
+// mode 4 on the half-slab kernel: a slab's 16 output pixels must sit at the same places relative to its first pixel whatever the slab (bla_gather_kernel.h)
 static bool gather4_fixed_offsets(int wo) { return wo == 4 || wo == 8 || (wo >= 16 && wo % 16 == 0); }
 static int gather_k_per_split(int mode, int batch, int M, int N, int HWo) {
 	const long K = (long)batch * HWo;
@@ -67,16 +67,12 @@ __global__ void __launch_bounds__(256) gather_fold_epilogue_kernel(const float4*
 		if (out2) { const float4 a = add[i]; out2[i] = make_float4(s.x + a.x, s.y + a.y, s.z + a.z, s.w + a.w); }
 	}
 }
-// LDS of the image-window kernel (mode 7): two A slabs, two channel groups of the window -- [16 planes][128 / W + 2 rows][4 zeros + W], a group rounded up to
-// whole 1-KiB DMA instructions -- and 16 bytes of slack at either end (the kernel's W7_* constants)
-static size_t window_lds_bytes(int W) {
-	const size_t plane = (size_t)(128 / W + 2) * (W + 4), group = (16 * plane + 255) / 256 * 256;
-	return (2 * 128 * 16 + 2 * group + 8) * sizeof(float);
-}
+// LDS of the image-window kernel (mode 7)
+static size_t window_lds_bytes(int W) { return W == 32 ? Window<32>::LDS_BYTES : Window<16>::LDS_BYTES; }
 
 // Everything a launch of one gathered product needs but the slab address (a.slab: set by whoever owns the workspace, where slab_floats > 0).
 // hs: the half-slab instantiation of modes 3 and 4; window: mode 7's image row width (16 or 32; 0 for the other modes).
-namespace { struct GatherPlan { GemmArgs a; dim3 grid; size_t lds, slab_floats; bool hs; int window; }; }
+namespace { struct GatherPlan { GatherArgs a; dim3 grid; size_t lds, slab_floats; bool hs; int window, mode; }; }
 
 // the part of a plan token (bla_conv_last_plan) a gathered product knows: mode, half-slab ("hs") or older form, window width, K splits, and the site of a
 // fused epilogue -- the tile store or the fold of the slabs
@@ -87,14 +83,14 @@ static void note_product(const GatherProduct& g, const GatherPlan& p) {
 	if (g.ep.bias || g.ep.out2) conv_plan_note(p.a.splits == 1 ? "/ep=tile" : "/ep=fold");
 }
 
-// the fields of a gathered product's GemmArgs that every form shares (gather_plan, gather_gemm_classes)
-static GemmArgs gather_args(const GatherProduct& g) {
-	GemmArgs a = {};
+// the fields of a gathered product's GatherArgs that every form shares (gather_plan, gather_gemm_classes)
+static GatherArgs gather_args(const GatherProduct& g) {
+	GatherArgs a = {};
 	a.C = g.C; a.M = g.M; a.N = g.N; a.K = g.K; a.ldc = g.ldc;
 	if (g.mode == 4) { a.B = g.A; a.ldb = g.lda; }      // the dense operand (del_y) is the K-contiguous B
 	else { a.A = g.A; a.lda = g.lda; }
 	a.alpha = 1.f; a.beta = 0.f; a.act = BLA_ACT_NONE;
-	a.g_img = g.img; a.g_zero = zero_word(); a.g_ktab = g.ktab; a.g_ntab = g.ntab; a.g_mode = g.mode; a.g_H = g.H; a.g_W = g.W; a.g_HWo = g.HWo; a.g_img_stride = g.img_stride;
+	a.g_img = g.img; a.g_zero = zero_word(); a.g_ktab = g.ktab; a.g_ntab = g.ntab; a.g_H = g.H; a.g_W = g.W; a.g_HWo = g.HWo; a.g_img_stride = g.img_stride;
 	a.g_wo = g.wo;
 	a.tiles_m = (g.M + 127) / 128; a.tiles_n = (g.N + 127) / 128;
 	return a;
@@ -115,11 +111,11 @@ bla_status gather_gemm_classes(hipStream_t s, const GatherProduct& g, int batch,
 		BLA_REQUIRE(cls[i].K > 0 && cls[i].K % 16 == 0 && (uintptr_t)cls[i].A % 16 == 0, BLA_ERR_INVALID, "class %d: K = %d", i, cls[i].K);
 	GatherProduct first = g;
 	first.mode = 3; first.A = cls[0].A; first.K = first.lda = cls[0].K; first.ktab = cls[0].ktab; first.C = cls[0].C;
-	GemmArgs a = gather_args(first);
+	GatherArgs a = gather_args(first);
 	a.splits = 1; a.k_per_split = 1 << 30;
 	a.g_ncls = ncls; a.g_cls = d_cls;       // d_cls: the same entries in device memory (the caller's launch wrote them)
 	const dim3 grid((unsigned)(a.tiles_m * a.tiles_n), (unsigned)ncls, 1), block(256);
-	hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 3, false, true>), grid, block, 2 * (128 + 128) * 16 * sizeof(float), s, a);
+	hipLaunchKernelGGL((gather_kernel<3, true>), grid, block, 2 * (128 + 128) * 16 * sizeof(float), s, a);
 	BLA_HIP(hipGetLastError());
 	conv_plan_note("m3hs/x%d", ncls);
 	return BLA_OK;
@@ -142,10 +138,10 @@ static bla_status gather_plan(const GatherProduct& g, int batch, GatherPlan* p) 
 	}
 	// whole tiles: the half-slab pipeline (fragment sets per k-half, every LDS read and DMA dealt out between MFMAs) -- BLA_CONV_HS=0 keeps the older form
 	p->hs = gather_hs(mode, M, N) && (mode != 4 || gather4_fixed_offsets(g.wo));
-	p->window = mode == 7 ? g.W : 0;
+	p->window = mode == 7 ? g.W : 0; p->mode = mode;
 	BLA_REQUIRE(!(g.ep.bias || g.ep.out2) || mode == 7 || (mode == 3 && p->hs), BLA_ERR_INVALID,
 	            "the fused convolution epilogue needs the half-slab forward kernel (gather3_fuses_epilogue)");
-	GemmArgs& a = p->a;
+	GatherArgs& a = p->a;
 	a = gather_args(g);
 	int splits = 1;
 	a.k_per_split = K;
@@ -168,7 +164,7 @@ static bla_status gather_plan(const GatherProduct& g, int batch, GatherPlan* p) 
 // The fold behind a product whose contraction was cut over workgroups: the slabs summed in split order into C, with the epilogue where the tile store
 // could not apply it
 static bla_status gather_fold(hipStream_t s, const GatherPlan& p, const GatherEpilogue& ep) {
-	const GemmArgs& a = p.a;
+	const GatherArgs& a = p.a;
 	if (a.splits <= 1) return BLA_OK;
 	if (ep.bias || ep.out2) {
 		const size_t total4 = (size_t)a.M * a.N / 4, blocks = (total4 + 255) / 256;
@@ -179,8 +175,8 @@ static bla_status gather_fold(hipStream_t s, const GatherPlan& p, const GatherEp
 		return BLA_OK;
 	}
 	GemmArgs r = a;
-	if (a.g_mode == 4) { r.M = a.N; r.N = a.M; }   // the slabs hold the transposed tile: [split][N][M] -> C [N][M]
-	if (a.g_mode == 3) r.ldc = r.N;                // C-shaped slabs ([image][M][HWo]): a flat sum
+	if (p.mode == 4) { r.M = a.N; r.N = a.M; }   // the slabs hold the transposed tile: [split][N][M] -> C [N][M]
+	if (p.mode == 3) r.ldc = r.N;                // C-shaped slabs ([image][M][HWo]): a flat sum
 	BLA_HIP(launch_splitk_reduce(r, s));
 	return BLA_OK;
 }
@@ -201,14 +197,14 @@ bla_status gather_gemm(hipStream_t s, const GatherProduct& g, int batch) {
 		p.a.slab = (float*)ws;
 	}
 	const dim3 block(256);
-	if (p.window == 32) hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 7, false, true, 1, 32>), p.grid, block, p.lds, s, p.a);
-	else if (p.window) hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 7, false, true, 1, 16>), p.grid, block, p.lds, s, p.a);
-	else if (p.hs && g.mode == 3) hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 3, false, true>), p.grid, block, p.lds, s, p.a);
-	else if (p.hs) hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, true, 1, 2, false, 4, false, true>), p.grid, block, p.lds, s, p.a);
-	else if (g.mode == 1) hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 1>), p.grid, block, p.lds, s, p.a);
-	else if (g.mode == 2) hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 2>), p.grid, block, p.lds, s, p.a);
-	else if (g.mode == 3) hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, false, 1, 2, false, 3>), p.grid, block, p.lds, s, p.a);
-	else hipLaunchKernelGGL((gemm_f32_glds_kernel<128, 128, 16, 2, 2, true, true, 1, 2, false, 4>), p.grid, block, p.lds, s, p.a);
+	if (p.window == 32) hipLaunchKernelGGL((gather_kernel<7, true, 32>), p.grid, block, p.lds, s, p.a);
+	else if (p.window) hipLaunchKernelGGL((gather_kernel<7, true, 16>), p.grid, block, p.lds, s, p.a);
+	else if (p.hs && g.mode == 3) hipLaunchKernelGGL((gather_kernel<3, true>), p.grid, block, p.lds, s, p.a);
+	else if (p.hs) hipLaunchKernelGGL((gather_kernel<4, true>), p.grid, block, p.lds, s, p.a);
+	else if (g.mode == 1) hipLaunchKernelGGL((gather_kernel<1, false>), p.grid, block, p.lds, s, p.a);
+	else if (g.mode == 2) hipLaunchKernelGGL((gather_kernel<2, false>), p.grid, block, p.lds, s, p.a);
+	else if (g.mode == 3) hipLaunchKernelGGL((gather_kernel<3, false>), p.grid, block, p.lds, s, p.a);
+	else hipLaunchKernelGGL((gather_kernel<4, false>), p.grid, block, p.lds, s, p.a);
 	BLA_HIP(hipGetLastError());
 	note_product(g, p);
 	return gather_fold(s, p, g.ep);

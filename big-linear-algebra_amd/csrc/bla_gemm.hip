@@ -627,7 +627,7 @@ static hipError_t launch_glds(const GemmArgs& a, bool akc, bool bkc, dim3 grid, 
 	dim3 block(WM * WN * WK * 64);
 #define BLA_LAUNCH2(AK, BK_, RG)                                                                            \
 	do {                                                                                                    \
-		auto kern = gemm_f32_glds_kernel<BM, BN, BK, WM, WN, AK, BK_, MINW, NBUF, PERSIST, 0, RG, HS, WK>;  \
+		auto kern = gemm_f32_glds_kernel<BM, BN, BK, WM, WN, AK, BK_, MINW, NBUF, PERSIST, RG, HS, WK>;     \
 		if (lds_bytes > 48 * 1024) {                                                                        \
 			hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
 			if (e != hipSuccess) return e;                                                                  \
@@ -637,7 +637,9 @@ static hipError_t launch_glds(const GemmArgs& a, bool akc, bool bkc, dim3 grid, 
 	} while (0)
 #define BLA_LAUNCH(AK, BK_)                                                                                 \
 	do {                                                                                                    \
-		if (!((AK) && (BK_)) && a.rc_global && NBUF == 2 && !PERSIST) BLA_LAUNCH2(AK, BK_, true);           \
+		if constexpr (!((AK) && (BK_)) && NBUF == 2 && !PERSIST) {   /* the only kernels with a global_load_lds twin */ \
+			if (a.rc_global) BLA_LAUNCH2(AK, BK_, true);                                                    \
+		}                                                                                                   \
 		BLA_LAUNCH2(AK, BK_, false);                                                                        \
 	} while (0)
 	if (akc && !bkc) BLA_LAUNCH(true, false);

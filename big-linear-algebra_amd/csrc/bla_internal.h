@@ -63,7 +63,7 @@ struct GatherEpilogue { const float* bias; int bias_stride; const float* add; fl
 bool gather3_fuses_epilogue(int M, int N, int K);                      // true: a mode-3 product takes a GatherEpilogue
 // One gathered product: C = A . G (mode 4: its transpose), G gathered from img through the tables; H, W, HWo, img_stride as the mode reads them (the padded
 // modes: the copy's rows and row pitch).  wo: mode 4 -- the output map's width; 4, 8 or a multiple of 16 puts the weight gradient on the half-slab kernel
-// with fixed lane offsets, anything else (or 0) on the older form.  Mode 7 (the image window, bla_gemm_kernel.h) takes no tables.
+// with fixed lane offsets, anything else (or 0) on the older form.  Mode 7 (the image window, bla_gather_kernel.h) takes no tables.
 struct GatherProduct { int mode, M, N, K; const float* A; int lda; float* C; int ldc; const float* img; const int2* ktab; const int2* ntab; int H, W, HWo, img_stride; GatherEpilogue ep; int wo; };
 bla_status gather_gemm(hipStream_t s, const GatherProduct& g, int batch);
 // floats of the K-split slabs gather_gemm cuts the product into (0: one pass over K)
@@ -74,7 +74,7 @@ struct GatherClass { const float* A; int K; const int2* ktab; float* C; };
 bool gather_classes_fit(int ncls, int M, int N);
 bla_status gather_gemm_classes(hipStream_t s, const GatherProduct& g, int batch, const GatherClass* cls, const GatherClass* d_cls, int ncls);
 
-// Both gradients of one batched convolution in ONE launch (gather_pair_kernel, bla_gemm_kernel.h): w = the weight gradient on mode 4, d = the data gradient
+// Both gradients of one batched convolution in ONE launch (gather_pair_kernel, bla_gather_kernel.h): w = the weight gradient on mode 4, d = the data gradient
 // on mode 7 or 3 (whole 128 x 128 tiles: gather_pair_fits); slabs: gather_product_slab_floats floats each (0: none)
 bool gather_pair_fits(int mode, int M, int N);
 bla_status gather_pair_products(hipStream_t s, int batch, const GatherProduct& w, float* w_slab, const GatherProduct& d, float* d_slab);
