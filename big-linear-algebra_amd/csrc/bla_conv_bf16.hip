@@ -10,7 +10,8 @@
 //     from the host) -- registers and VALU only, no table load in front of a DMA (a vector load there drains every DMA in flight).
 //   * the store maps (row, n) to out [b][row][pix]: lanes run along n, so a wave's store instruction writes runs of consecutive floats, also in a tile that
 //     straddles two images.
-// Around it: the pad copy (fp32 [B][C][H][W] -> P, a convert-and-transpose through an LDS tile that writes EVERY element of P), the tap-major kernel
+// conv_bf16_gather_cl_kernel is the same K loop with a channel-last bf16 store: it writes the padded map the next product gathers from.
+// Around them: the pad copy (fp32 [B][C][H][W] -> P, a convert-and-transpose through an LDS tile that writes EVERY element of P), the tap-major kernel
 // matrices, the materialised weight gradient (a bf16 im2col and a bf16 copy of del_y in front of the existing fast nt product), and the implicit weight
 // gradient (conv_bf16_wgrad_kernel): the k-major tile on the two padded copies a backward pass has anyway, K-split with a fixed-order fold.
 #include "bla_internal.h"
@@ -27,12 +28,9 @@ struct GatherArgs {
 	const float* bias; int bias_stride;
 };
 
-__global__ __launch_bounds__(256) void conv_bf16_gather_kernel(GatherArgs p) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+// the K loop of both gather kernels: acc = the tile at (row0, col0)
+__device__ __forceinline__ void gather_tile_product(const GatherArgs& p, unsigned char* lds, int row0, int col0, f32x16 (&acc)[2][2]) {
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const Bf16Tile t = bf16_tile_of(blockIdx.x, p.tiles_m, p.tiles_n);
-	const int row0 = t.tm * BM, col0 = t.tn * BN;
-
 	const uint16_t* pb[4];   // pixel_base of the piece's B row
 #pragma unroll
 	for (int i = 0; i < 4; ++i) {
@@ -40,13 +38,20 @@ __global__ __launch_bounds__(256) void conv_bf16_gather_kernel(GatherArgs p) {
 		const int b = n / p.howo, pix = n - b * p.howo, oi = pix / p.wo, oj = pix - oi * p.wo;
 		pb[i] = p.P + (((size_t)b * p.hp + (size_t)oi * p.stride) * p.wp + (size_t)oj * p.stride) * p.cp;
 	}
-	f32x16 acc[2][2];
 	bf16_tile_product(lds, {p.A, p.K, p.rows, p.n, p.K, row0, col0, p.zero}, 0, p.K, [&](int i, int kb) {
 		const uint32_t k0 = (uint32_t)(kb + bf16_piece_chunk(lane, i) * 8);   // the same for pieces i and i + 2: two tap offsets per slab
 		const uint32_t tap = __umulhi(k0, p.magic_cp), c = k0 - tap * p.cp;
 		const uint32_t tp = __umulhi(tap, p.magic_kk), tq = tap - tp * p.kk;
 		return pb[i] + (int)((tp * p.wp + tq) * p.cp + c);   // a lane past K has a meaningless offset and never uses it
 	}, acc);
+}
+
+__global__ __launch_bounds__(256) void conv_bf16_gather_kernel(GatherArgs p) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+	const Bf16Tile t = bf16_tile_of(blockIdx.x, p.tiles_m, p.tiles_n);
+	const int row0 = t.tm * BM, col0 = t.tn * BN;
+	f32x16 acc[2][2];
+	gather_tile_product(p, lds, row0, col0, acc);
 
 #pragma unroll
 	for (int j = 0; j < 2; ++j) {
@@ -62,6 +67,74 @@ __global__ __launch_bounds__(256) void conv_bf16_gather_kernel(GatherArgs p) {
 				const int row = row0 + bf16_acc_row(i, r);
 				if (row < p.rows) o[(size_t)row * p.howo] = bias ? acc[i][j][r] + bias[row] : acc[i][j][r];
 			}
+	}
+}
+
+// ---- the same product with a channel-last bf16 output: the store writes the padded map the next product gathers from -------------------------
+// After the K loop lane l holds ONE pixel (bf16_acc_col) and, per 32-row block, four groups g of four consecutive channels 8 g + 4 (l >> 5) + e: lanes l
+// and l + 32 hold the two halves of every 8-channel chunk of the same pixel.  The epilogue runs on the fp32 values in the order of include/bla.h (bias,
+// relu, gate, the fp32 store), packs a group to 8 bytes, and v_permlane32_swap exchanges the halves of a pair of groups (2 m, 2 m + 1): afterwards lanes
+// 0-31 hold chunk 2 m whole, lanes 32-63 chunk 2 m + 1, and each lane stores 16 bytes -- 8 stores a lane for the tile, every one a whole aligned chunk of
+// dst.  The swap runs on every lane, whatever it holds (only loads and stores are predicated): a pixel at or past n stores nothing, a channel at or past
+// rows is the literal +0 (never its accumulator, which a NaN in P could have reached), a chunk at or past dst.cp is not stored.  The gate is read by the
+// lane that holds the four channels, one 8-byte load per group in front of the swap, because the fp32 output wants the gated value too.  relu, gate, out
+// and dst are workgroup-uniform branches around the same 64 accumulators.
+struct ChainArgs { GatherArgs g; int relu; bla_conv_bf16_map gate, dst; };
+
+__device__ __forceinline__ size_t map_pixel(const bla_conv_bf16_map& m, int b, int i, int j) {   // element offset of channel 0 of output pixel (b, i, j)
+	return (((size_t)b * m.hp + m.top + i * m.dilate) * m.wp + m.left + j * m.dilate) * m.cp;
+}
+
+__global__ __launch_bounds__(256, 3) void conv_bf16_gather_cl_kernel(ChainArgs a) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+	const GatherArgs& p = a.g;
+	const Bf16Tile t = bf16_tile_of(blockIdx.x, p.tiles_m, p.tiles_n);
+	const int row0 = t.tm * BM, col0 = t.tn * BN;
+	f32x16 acc[2][2];
+	gather_tile_product(p, lds, row0, col0, acc);
+
+#pragma unroll
+	for (int j = 0; j < 2; ++j) {
+		const int n = col0 + bf16_acc_col(j);
+		const bool live = n < p.n;
+		const int nn = live ? n : 0;   // a lane past n computes on pixel 0 and stores nothing
+		const int b = nn / p.howo, pix = nn - b * p.howo, oi = pix / p.wo, oj = pix - oi * p.wo;
+		float* o = p.out ? p.out + (size_t)b * p.rows * p.howo + pix : nullptr;
+		const float* bias = p.bias ? p.bias + (size_t)b * p.bias_stride : nullptr;
+		const uint16_t* gate = a.gate.d ? a.gate.d + map_pixel(a.gate, b, oi, oj) : nullptr;
+		uint16_t* dst = a.dst.d ? a.dst.d + map_pixel(a.dst, b, oi, oj) : nullptr;
+#pragma unroll
+		for (int i = 0; i < 2; ++i) {
+			uint2 packed[4];
+#pragma unroll
+			for (int g = 0; g < 4; ++g) {
+				const int row = row0 + bf16_acc_row(i, 4 * g);   // the group's first channel, a multiple of 4: row < rows puts row + 3 inside gate.cp
+				uint2 gb = make_uint2(0u, 0u);
+				if (a.gate.d && row < p.rows) gb = *(const uint2*)(gate + row);
+				float v[4];
+#pragma unroll
+				for (int e = 0; e < 4; ++e) {
+					const bool in = row + e < p.rows;
+					float x = acc[i][j][4 * g + e];
+					if (p.bias) x += bias[in ? row + e : 0];
+					if (a.relu) x = x > 0.f ? x : 0.f;
+					if (a.gate.d) x = bf16_to_f32((uint16_t)((e < 2 ? gb.x : gb.y) >> (16 * (e & 1)))) > 0.f ? x : 0.f;
+					v[e] = in ? x : 0.f;
+					if (p.out && live && in) o[(size_t)(row + e) * p.howo] = x;
+				}
+				packed[g] = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+			}
+			if (a.dst.d) {
+#pragma unroll
+				for (int m = 0; m < 2; ++m) {
+					const uint2 lo = packed[2 * m], hi = packed[2 * m + 1];
+					const auto sx = __builtin_amdgcn_permlane32_swap(lo.x, hi.x, false, false);
+					const auto sy = __builtin_amdgcn_permlane32_swap(lo.y, hi.y, false, false);
+					const int ch = row0 + (threadIdx.x >> 7) * 64 + i * 32 + 16 * m + 8 * ((threadIdx.x & 63) >> 5);   // lanes 0-31: chunk 2 m, 32-63: chunk 2 m + 1
+					if (live && ch < a.dst.cp) *(uint4*)(dst + ch) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+				}
+			}
+		}
 	}
 }
 
@@ -288,6 +361,18 @@ bla_status check_gathered_shape(int rows, int batch, int hp, int wp, int cp, int
 	return BLA_OK;
 }
 
+// a map of the chained entry: the kernel forms an address for every output pixel in it and checks nothing
+bla_status check_chain_map(const char* what, const bla_conv_bf16_map& m, int batch, int ho, int wo) {
+	const char* who = "bla_conv2d_gathered_bf16_chained";
+	BLA_REQUIRE(aligned16(m.d), BLA_ERR_INVALID, "%s: %s is not 16-byte aligned", who, what);
+	BLA_REQUIRE(m.hp > 0 && m.wp > 0 && m.cp > 0 && m.cp % 8 == 0, BLA_ERR_INVALID, "%s: %s has hp %d wp %d cp %d", who, what, m.hp, m.wp, m.cp);
+	BLA_REQUIRE(m.top >= 0 && m.left >= 0 && m.dilate >= 1, BLA_ERR_INVALID, "%s: %s has top %d left %d dilate %d", who, what, m.top, m.left, m.dilate);
+	BLA_REQUIRE((long)m.top + (long)(ho - 1) * m.dilate < m.hp && (long)m.left + (long)(wo - 1) * m.dilate < m.wp, BLA_ERR_INVALID,
+	            "%s: the %d x %d output at (%d, %d), dilation %d, does not fit %s (%d x %d)", who, ho, wo, m.top, m.left, m.dilate, what, m.hp, m.wp);
+	BLA_REQUIRE((long)batch * m.hp * m.wp * m.cp < (1L << 31), BLA_ERR_INVALID, "%s: %s holds %ld elements, 2^31 or more", who, what, (long)batch * m.hp * m.wp * m.cp);
+	return BLA_OK;
+}
+
 // the implicit weight gradient forms an address for every (output pixel, tap) in P and every output pixel in Q and checks nothing in the kernel
 bla_status check_wgrad_implicit_shape(int hq, int wq, int fp, int top, int left, int dilate, int hp, int wp, int cp, int batch, int k, int stride, int ho, int wo, int f_n,
                                       int c_n, int splits) {
@@ -333,8 +418,8 @@ bla_status launch_kernels(hipStream_t s, const float* kern, uint16_t* dst, int f
 	return BLA_OK;
 }
 
-bla_status launch_gathered(hipStream_t s, const uint16_t* A, int rows, const uint16_t* P, int batch, int hp, int wp, int cp, int k, int stride, int ho, int wo, float* out,
-                           const float* ep_bias, int ep_bias_stride) {
+GatherArgs gather_args(const uint16_t* A, int rows, const uint16_t* P, int batch, int hp, int wp, int cp, int k, int stride, int ho, int wo, float* out, const float* ep_bias,
+                       int ep_bias_stride) {
 	GatherArgs a{};
 	a.A = A; a.P = P; a.out = out; a.zero = zero_word();
 	a.rows = rows; a.n = batch * ho * wo; a.K = k * k * cp;
@@ -344,10 +429,28 @@ bla_status launch_gathered(hipStream_t s, const uint16_t* A, int rows, const uin
 	a.magic_cp = (uint32_t)(((1ull << 32) + cp - 1) / cp);
 	a.magic_kk = k == 1 ? 0u : (uint32_t)(((1ull << 32) + k - 1) / k);
 	a.bias = ep_bias; a.bias_stride = ep_bias_stride;
+	return a;
+}
+
+bla_status launch_gathered(hipStream_t s, const uint16_t* A, int rows, const uint16_t* P, int batch, int hp, int wp, int cp, int k, int stride, int ho, int wo, float* out,
+                           const float* ep_bias, int ep_bias_stride) {
+	const GatherArgs a = gather_args(A, rows, P, batch, hp, wp, cp, k, stride, ho, wo, out, ep_bias, ep_bias_stride);
 	hipLaunchKernelGGL(conv_bf16_gather_kernel, dim3((unsigned)((long)a.tiles_m * a.tiles_n)), dim3(256), 2 * SLAB_BYTES, s, a);
 	BLA_HIP(hipGetLastError());
 	char name[64];
 	snprintf(name, sizeof name, "conv_bf16_gather128x128x64_s%d", stride);
+	gemm_note_last_kernel(name);
+	return BLA_OK;
+}
+
+// the channel-last store's kernel, whatever outputs the epilogue names (with out_f32 alone it is the plain product behind relu / gate)
+bla_status launch_gathered_chained(hipStream_t s, const uint16_t* A, int rows, const uint16_t* P, int batch, int hp, int wp, int cp, int k, int stride, int ho, int wo,
+                                   const bla_conv_bf16_epilogue& ep) {
+	const ChainArgs a{gather_args(A, rows, P, batch, hp, wp, cp, k, stride, ho, wo, ep.out_f32, ep.bias, ep.bias_stride), ep.relu != 0, ep.gate, ep.dst};
+	hipLaunchKernelGGL(conv_bf16_gather_cl_kernel, dim3((unsigned)((long)a.g.tiles_m * a.g.tiles_n)), dim3(256), 2 * SLAB_BYTES, s, a);
+	BLA_HIP(hipGetLastError());
+	char name[64];
+	snprintf(name, sizeof name, ep.dst.d ? "conv_bf16_gather128x128x64_s%d_cl" : "conv_bf16_gather128x128x64_s%d", stride);
 	gemm_note_last_kernel(name);
 	return BLA_OK;
 }
@@ -468,6 +571,28 @@ bla_status bla_conv2d_gathered_bf16(void* stream, const uint16_t* d_a, int rows,
 	st = require_ready();
 	if (st != BLA_OK) return st;
 	return launch_gathered(pick_stream(stream), d_a, rows, d_p, batch, hp, wp, cp, k, stride, ho, wo, d_out, ep_bias, ep_bias_stride);
+}
+
+bla_status bla_conv2d_gathered_bf16_chained(void* stream, const uint16_t* d_a, int rows, const uint16_t* d_p, int batch, int hp, int wp, int cp, int k, int stride, int ho,
+                                            int wo, const bla_conv_bf16_epilogue* ep) {
+	const char* who = "bla_conv2d_gathered_bf16_chained";
+	BLA_REQUIRE(ep, BLA_ERR_INVALID, "%s: NULL epilogue", who);
+	BLA_REQUIRE(ep->out_f32 || ep->dst.d, BLA_ERR_INVALID, "%s: neither out_f32 nor dst", who);
+	BLA_REQUIRE(d_a && d_p, BLA_ERR_INVALID, "%s: NULL pointer", who);
+	BLA_REQUIRE(aligned16(d_a) && aligned16(d_p), BLA_ERR_INVALID, "%s: an operand is not 16-byte aligned", who);
+	bla_status st = check_gathered_shape(rows, batch, hp, wp, cp, k, stride, ho, wo, ep->bias_stride);
+	if (st != BLA_OK) return st;
+	if (ep->dst.d) {
+		BLA_REQUIRE(ep->dst.cp == round8(rows), BLA_ERR_INVALID, "%s: dst.cp %d is not %d rows rounded up to 8", who, ep->dst.cp, rows);
+		if ((st = check_chain_map("dst", ep->dst, batch, ho, wo)) != BLA_OK) return st;
+	}
+	if (ep->gate.d) {
+		BLA_REQUIRE(ep->gate.cp >= rows, BLA_ERR_INVALID, "%s: gate.cp %d < rows %d", who, ep->gate.cp, rows);
+		if ((st = check_chain_map("gate", ep->gate, batch, ho, wo)) != BLA_OK) return st;
+	}
+	st = require_ready();
+	if (st != BLA_OK) return st;
+	return launch_gathered_chained(pick_stream(stream), d_a, rows, d_p, batch, hp, wp, cp, k, stride, ho, wo, *ep);
 }
 
 bla_status bla_conv2d_forward_batched_f32_as_bf16(void* stream, const float* d_x, const float* d_kern, float* d_out, int batch, int h, int w, int k, int c_in, int f_n,

@@ -43,6 +43,16 @@ def _ptr_struct(name, fields):
     return type(name, (C.Structure,), {"_fields_": [(n, C.c_void_p) for n in fields], "__doc__": f"struct {name} of include/bla.h (device pointers)"})
 
 
+class ConvBf16Map(C.Structure):
+    """struct bla_conv_bf16_map (include/bla.h): a padded channel-last bf16 map [batch][hp][wp][cp] and where the tensor it carries sits in it."""
+    _fields_ = [("d", C.c_void_p)] + [(n, C.c_int) for n in ("hp", "wp", "cp", "top", "left", "dilate")]
+
+
+class ConvBf16Epilogue(C.Structure):
+    """struct bla_conv_bf16_epilogue (include/bla.h)."""
+    _fields_ = [("bias", C.c_void_p), ("bias_stride", C.c_int), ("relu", C.c_int), ("gate", ConvBf16Map), ("out_f32", C.c_void_p), ("dst", ConvBf16Map)]
+
+
 ResnetParams = _ptr_struct("bla_resnet_params", ("conv1", "conv2", "time_w", "time_b", "res"))
 ResnetGrads = _ptr_struct("bla_resnet_grads", ("conv1", "conv2", "time_w", "time_b", "res"))
 ResnetWs = _ptr_struct("bla_resnet_ws", ("mu1", "sd1", "relu1", "c1", "tdense", "mu2", "sd2", "relu2", "dp", "c2", "res"))
@@ -74,6 +84,7 @@ SIGNATURES = {
     "bla_conv2d_backward_gathered_f32_as_bf16": (_I, [_VP] * 6 + [_I] * 8),
     "bla_conv_bf16_layout": (_I, [_I] * 5 + [C.POINTER(_I)] * 5), "bla_conv_bf16_pad": (_I, [_VP] * 3 + [_I] * 9),
     "bla_conv_bf16_prepare_kernels": (_I, [_VP] * 3 + [_I] * 4), "bla_conv2d_gathered_bf16": (_I, [_VP, _VP, _I, _VP] + [_I] * 8 + [_VP, _VP, _I]),
+    "bla_conv2d_gathered_bf16_chained": (_I, [_VP, _VP, _I, _VP] + [_I] * 8 + [C.POINTER(ConvBf16Epilogue)]),
     "bla_conv2d_forward_batched_f32_as_bf16": (_I, [_VP] * 4 + [_I] * 7 + [_VP, _I]), "bla_conv2d_backward_batched_f32_as_bf16": (_I, [_VP] * 6 + [_I] * 7),
     "bla_scale_f32": (_I, [_VP, _VP, _SZ, _F]), "bla_add_f32": (_I, [_VP, _VP, _VP, _SZ]),
     "bla_hadamard_f32": (_I, [_VP, _VP, _VP, _SZ]), "bla_axpy_f32": (_I, [_VP, _VP, _VP, _F, _SZ]),
@@ -434,6 +445,20 @@ def conv2d_gathered_bf16(a, rows, p, batch, hp, wp, cp, k, stride, ho, wo, out, 
     """out fp32 [batch][rows][ho][wo] = A [rows][k*k*cp] . gather(P [batch][hp][wp][cp]) (+ ep_bias[b * ep_bias_stride + row])."""
     check(lib().bla_conv2d_gathered_bf16(stream, _ptr(a), rows, _ptr(p), batch, hp, wp, cp, k, stride, ho, wo, _ptr(out), _ptr(ep_bias), ep_bias_stride))
     return out
+
+
+def conv_bf16_map(d, hp, wp, cp, top, left, dilate=1):
+    """struct bla_conv_bf16_map around a device array (or address) of a padded channel-last bf16 map."""
+    return ConvBf16Map(_ptr(d), hp, wp, cp, top, left, dilate)
+
+
+def conv2d_gathered_bf16_chained(a, rows, p, batch, hp, wp, cp, k, stride, ho, wo, dst=None, out_f32=None, ep_bias=None, ep_bias_stride=0, relu=False, gate=None,
+                                 stream=None):
+    """conv2d_gathered_bf16's product behind bias, relu and a ReLU-derivative gate, written channel-last in bf16 into the next product's padded map:
+    dst and gate are conv_bf16_map(...) (or None), out_f32 the optional fp32 [batch][rows][ho][wo]."""
+    ep = ConvBf16Epilogue(bias=_ptr(ep_bias), bias_stride=ep_bias_stride, relu=int(relu), gate=gate or ConvBf16Map(), out_f32=_ptr(out_f32), dst=dst or ConvBf16Map())
+    check(lib().bla_conv2d_gathered_bf16_chained(stream, _ptr(a), rows, _ptr(p), batch, hp, wp, cp, k, stride, ho, wo, C.byref(ep)))
+    return dst
 
 
 def conv2d_forward_as_bf16(x, kern, out, batch, h, w, k, c_in, f_n, stride, ep_bias=None, ep_bias_stride=0, stream=None):

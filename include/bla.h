@@ -385,6 +385,31 @@ BLA_API bla_status bla_conv_bf16_prepare_kernels(void* stream, const float* d_ke
  * hp wp cp, or batch ho wo, at 2^31 or more).  No workspace. */
 BLA_API bla_status bla_conv2d_gathered_bf16(void* stream, const uint16_t* d_a, int rows, const uint16_t* d_p, int batch, int hp, int wp, int cp, int k, int stride,
                                             int ho, int wo, float* d_out, const float* ep_bias, int ep_bias_stride);
+/* The same product with a CHANNEL-LAST bf16 OUTPUT: it writes the padded map the next product reads, so consecutive bf16 convolutions chain
+ * with no fp32 round trip and no bla_conv_bf16_pad between them.  An addition: bla_conv2d_gathered_bf16 above keeps its kernel and its bits.
+ * A map is a padded channel-last bf16 tensor [batch][hp][wp][cp]: pixel (y, x), channel c of the tensor it carries sits at
+ * d[((b hp + top + y dilate) wp + left + x dilate) cp + c] -- bla_conv_bf16_layout's forward layout of the next convolution (dilate 1), or the
+ * data-gradient layout of the layer below (dilate = its stride).
+ * Per output element (b, r, i, j), all in fp32 and in this order:  t = the accumulator;  t += bias[b bias_stride + r] (one add, as above);
+ * relu: t = t > 0 ? t : +0;  gate.d: t = gate(b, i, j, r) > 0 ? t : +0 (ReLU's derivative, read from the bf16 activations of the layer's input map);
+ * out_f32[b][r][i][j] = t (if given);  dst(b, i, j, r) = rne(t), bla_f32_to_bf16's rounding (if dst.d is given).
+ * In dst, for every output pixel ALL dst.cp channels of position (top + i dilate, left + j dilate) are written -- channels rows .. dst.cp - 1 as +0, never
+ * a rounded accumulator -- in 16-byte stores of whole 8-channel chunks, and nothing else is touched: halo rows and columns and the holes of a dilation keep
+ * their bits.  A caller zero-fills a map once; its halo stays valid for every later pass that writes the same map.  dst.d and gate.d must not overlap d_p.
+ * bla_gemm_last_kernel() answers conv_bf16_gather128x128x64_s<stride>_cl when dst.d is given, conv_bf16_gather128x128x64_s<stride> otherwise.
+ * BLA_ERR_INVALID, before the device is asked for and with both outputs untouched: a NULL ep; out_f32 and dst.d both NULL; anything
+ * bla_conv2d_gathered_bf16 refuses; dst.cp != rows rounded up to 8; gate.cp % 8 != 0 or gate.cp < rows; a map base off 16-byte alignment; top or left < 0,
+ * dilate < 1; a map the output does not fit (top + (ho-1) dilate >= hp, left + (wo-1) dilate >= wp); a map of 2^31 elements or more.  No workspace. */
+typedef struct bla_conv_bf16_map { uint16_t* d; int hp, wp, cp, top, left, dilate; } bla_conv_bf16_map;
+typedef struct bla_conv_bf16_epilogue {
+    const float* bias; int bias_stride;   /* ep_bias / ep_bias_stride of bla_conv2d_gathered_bf16; NULL = none */
+    int relu;                              /* t = t > 0 ? t : +0 */
+    bla_conv_bf16_map gate;                /* gate.d != NULL: t = gate(b, i, j, r) > 0 ? t : +0 */
+    float* out_f32;                        /* optional: fp32 [batch][rows][ho][wo], the existing output */
+    bla_conv_bf16_map dst;                 /* optional (dst.d == NULL: none): the next product's operand */
+} bla_conv_bf16_epilogue;
+BLA_API bla_status bla_conv2d_gathered_bf16_chained(void* stream, const uint16_t* d_a, int rows, const uint16_t* d_p, int batch, int hp, int wp, int cp, int k,
+                                                    int stride, int ho, int wo, const bla_conv_bf16_epilogue* ep);
 /* fp32 in memory, the argument meaning of bla_conv2d_forward_batched_f32 / bla_conv2d_backward_batched_f32 (no d_scratch): exactly the composition of the
  * three entries above in the context workspace, bit for bit -- what bla_gemm_f32_as_bf16 is to bla_gemm_bf16.
  *   forward:        pad(x) and prepare_kernels(kern, 0), then the gathered product with the optional bias.
