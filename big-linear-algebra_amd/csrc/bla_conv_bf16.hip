@@ -14,6 +14,7 @@
 // Around them: the pad copy (fp32 [B][C][H][W] -> P, a convert-and-transpose through an LDS tile that writes EVERY element of P), the tap-major kernel
 // matrices, the materialised weight gradient (a bf16 im2col and a bf16 copy of del_y in front of the existing fast nt product), and the implicit weight
 // gradient (conv_bf16_wgrad_kernel): the k-major tile on the two padded copies a backward pass has anyway, K-split with a fixed-order fold.
+// At the end: the batched ResNet block composed of these entries and the norms of bla_norm_bf16.hip; it adds no kernel.
 #include "bla_internal.h"
 #include "bla_bf16_tile.h"
 
@@ -749,6 +750,117 @@ bla_status bla_conv2d_backward_gathered_f32_as_bf16(void* stream, const float* d
 		if ((st = launch_gathered(s, A, c_in, Q, batch, Lq.hp, Lq.wp, fp, k, 1, h, w, d_del_x, nullptr, 0)) != BLA_OK) return st;
 	}
 	return BLA_OK;
+}
+
+// ---- the batched ResNet block on the bf16 products (include/bla.h): a composition of the entries above and of bla_norm_bf16.hip -------------
+// Everything in the context workspace is consumed by a launch that is already on the stream before the next step writes there, so the steps share it from
+// its base: forward [A]; backward [Q2 | A | partials].  The two 1 x 1 residual entries size and lay out the workspace themselves (they may grow it, which
+// waits for the device first); nothing of the block's is live in it across those calls, and the base is asked for again behind them.
+bla_status bla_resnet_forward_batched_bf16(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p, const unsigned char* d_drop,
+                                           const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k, int tdim, int group_size,
+                                           const bla_resnet_bf16_maps* maps) {
+	const char* who = "bla_resnet_forward_batched_bf16";
+	BLA_REQUIRE(batch > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && k > 0 && tdim > 0 && group_size > 0, BLA_ERR_INVALID, "%s: extent <= 0", who);
+	BLA_REQUIRE(d_x && d_temb && p && d_drop && ws && d_result && maps && p->conv1 && p->conv2 && p->time_w && p->time_b, BLA_ERR_INVALID, "%s: NULL operand", who);
+	BLA_REQUIRE(ws->mu1 && ws->sd1 && ws->c1 && ws->tdense && ws->mu2 && ws->sd2 && ws->c2, BLA_ERR_INVALID, "%s: NULL workspace field", who);
+	BLA_REQUIRE(maps->p1 && maps->p2 && aligned16(maps->p1) && aligned16(maps->p2), BLA_ERR_INVALID, "%s: a map is NULL or off 16-byte alignment", who);
+	BLA_REQUIRE(cin == cout || (p->res && ws->res), BLA_ERR_INVALID, "%s: Cin != Cout needs the residual 1x1 kernels and workspace", who);
+	const Layout16 L = layout16(h, w, k, 1, false);
+	const int cpi = round8(cin), cpo = round8(cout);
+	const bla_conv_bf16_map p1{maps->p1, L.hp, L.wp, cpi, L.top, L.left, 1}, p2{maps->p2, L.hp, L.wp, cpo, L.top, L.left, 1};
+	bla_status st;
+	if ((st = check_chain_map("p1", p1, batch, h, w)) != BLA_OK || (st = check_chain_map("p2", p2, batch, h, w)) != BLA_OK) return st;
+	if ((st = check_gathered_shape(cout, batch, L.hp, L.wp, cpi, k, 1, h, w, cout)) != BLA_OK || (st = check_gathered_shape(cout, batch, L.hp, L.wp, cpo, k, 1, h, w, 0)) != BLA_OK) return st;
+	if ((st = require_ready()) != BLA_OK) return st;
+	if ((st = bla_group_norm_relu_bf16_map(stream, batch, d_x, cin, group_size, h, w, nullptr, ws->sd1, ws->mu1, nullptr, &p1)) != BLA_OK) return st;
+	bla_gemm_epilogue tep = {};
+	tep.alpha = 1.f; tep.bias_col = p->time_b;
+	if ((st = bla_gemm_f32(stream, 0, 0, batch, cout, tdim, d_temb, tdim, p->time_w, cout, ws->tdense, cout, &tep)) != BLA_OK) return st;
+	void* base = nullptr;
+	if ((st = ensure_workspace(kernels_bytes(cout, k, cpi > cpo ? cpi : cpo), &base)) != BLA_OK) return st;
+	uint16_t* A = (uint16_t*)base;
+	if ((st = bla_conv_bf16_prepare_kernels(stream, p->conv1, A, cout, cin, k, 0)) != BLA_OK) return st;
+	if ((st = bla_conv2d_gathered_bf16(stream, A, cout, p1.d, batch, L.hp, L.wp, cpi, k, 1, h, w, ws->c1, ws->tdense, cout)) != BLA_OK) return st;
+	if ((st = bla_group_norm_relu_bf16_map(stream, batch, ws->c1, cout, group_size, h, w, d_drop, ws->sd2, ws->mu2, nullptr, &p2)) != BLA_OK) return st;
+	if ((st = bla_conv_bf16_prepare_kernels(stream, p->conv2, A, cout, cout, k, 0)) != BLA_OK) return st;
+	if ((st = bla_conv2d_gathered_bf16(stream, A, cout, p2.d, batch, L.hp, L.wp, cpo, k, 1, h, w, ws->c2, nullptr, 0)) != BLA_OK) return st;
+	const float* r = d_x;
+	if (cin != cout) {
+		if ((st = bla_conv2d_forward_batched_f32_as_bf16(stream, d_x, p->res, ws->res, batch, h, w, 1, cin, cout, 1, nullptr, 0)) != BLA_OK) return st;
+		r = ws->res;
+	}
+	return bla_sum_f32(stream, d_result, ws->c2, r, (size_t)batch * cout * h * w);
+}
+
+bla_status bla_resnet_backward_batched_bf16(void* stream, int batch, const float* d_del_out, const float* d_x, const float* d_temb, const bla_resnet_params* p,
+                                            const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc, float* d_dtb, float* d_del_x, int h, int w,
+                                            int cin, int cout, int k, int tdim, int group_size, const bla_resnet_bf16_maps* maps, int splits) {
+	const char* who = "bla_resnet_backward_batched_bf16";
+	BLA_REQUIRE(batch > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && k > 0 && tdim > 0 && group_size > 0, BLA_ERR_INVALID, "%s: extent <= 0", who);
+	BLA_REQUIRE(splits >= 0, BLA_ERR_INVALID, "%s: splits %d", who, splits);
+	BLA_REQUIRE(d_del_out && d_x && d_temb && p && ws && g && sc && d_dtb && maps && p->conv1 && p->conv2 && g->conv1 && g->conv2 && g->time_w && g->time_b && sc->g_out_a &&
+	            sc->g_out_b && sc->g_in, BLA_ERR_INVALID, "%s: NULL operand", who);
+	BLA_REQUIRE(ws->mu1 && ws->sd1 && ws->c1 && ws->mu2 && ws->sd2, BLA_ERR_INVALID, "%s: NULL workspace field", who);
+	BLA_REQUIRE(maps->p1 && maps->p2 && maps->q1 && aligned16(maps->p1) && aligned16(maps->p2) && aligned16(maps->q1), BLA_ERR_INVALID,
+	            "%s: a map is NULL or off 16-byte alignment", who);
+	BLA_REQUIRE(cin == cout || (p->res && g->res), BLA_ERR_INVALID, "%s: Cin != Cout needs the residual 1x1 kernels and their gradient", who);
+	const Layout16 Lp = layout16(h, w, k, 1, false), Lq = layout16(h, w, k, 1, true);
+	const int cpi = round8(cin), cpo = round8(cout), hw = h * w;
+	const bla_conv_bf16_map p1{maps->p1, Lp.hp, Lp.wp, cpi, Lp.top, Lp.left, 1}, p2{maps->p2, Lp.hp, Lp.wp, cpo, Lp.top, Lp.left, 1};
+	const bla_conv_bf16_map q1{maps->q1, Lq.hp, Lq.wp, cpo, Lq.top, Lq.left, Lq.dilate};
+	bla_status st;
+	if ((st = check_pad_shape(batch, cout, h, w, Lq.hp, Lq.wp, Lq.top, Lq.left, Lq.dilate)) != BLA_OK) return st;
+	if ((st = check_wgrad_implicit_shape(Lq.hp, Lq.wp, cpo, Lq.top, Lq.left, Lq.dilate, Lp.hp, Lp.wp, cpo, batch, k, 1, h, w, cout, cout, splits)) != BLA_OK) return st;
+	if ((st = check_wgrad_implicit_shape(Lq.hp, Lq.wp, cpo, Lq.top, Lq.left, Lq.dilate, Lp.hp, Lp.wp, cpi, batch, k, 1, h, w, cout, cin, splits)) != BLA_OK) return st;
+	if ((st = check_gathered_shape(cout, batch, Lq.hp, Lq.wp, cpo, k, 1, h, w, 0)) != BLA_OK || (st = check_gathered_shape(cin, batch, Lq.hp, Lq.wp, cpo, k, 1, h, w, 0)) != BLA_OK) return st;
+	if ((st = check_chain_map("p1", p1, batch, h, w)) != BLA_OK || (st = check_chain_map("p2", p2, batch, h, w)) != BLA_OK || (st = check_chain_map("q1", q1, batch, h, w)) != BLA_OK) return st;
+	if ((st = require_ready()) != BLA_OK) return st;
+	const WgradImplicitPlan plan2 = wgrad_implicit_plan(cout, k, cpo, batch * hw, splits), plan1 = wgrad_implicit_plan(cout, k, cpi, batch * hw, splits);
+	const size_t q_bytes = padded_bytes(batch, Lq.hp, Lq.wp, cpo), a_bytes = kernels_bytes(cout > cin ? cout : cin, k, cpo);
+	const size_t need = q_bytes + a_bytes + (plan2.partial_bytes > plan1.partial_bytes ? plan2.partial_bytes : plan1.partial_bytes);
+	uint16_t *Q2 = nullptr, *A = nullptr;
+	float* partial = nullptr;
+	auto slots = [&]() -> bla_status {   // asked for again behind every call that lays the workspace out itself (it may have grown, and so moved)
+		void* base = nullptr;
+		const bla_status s2 = ensure_workspace(need, &base);
+		Q2 = (uint16_t*)base;
+		A = (uint16_t*)((unsigned char*)base + q_bytes);
+		partial = (float*)((unsigned char*)base + q_bytes + a_bytes);
+		return s2;
+	};
+	if ((st = slots()) != BLA_OK) return st;
+	hipStream_t s = pick_stream(stream);
+	// second chunk: del_out -> Q2, conv2's weight gradient, its data gradient gated by p2 (dropout mask and ReLU's derivative at once: p2 is zero wherever dp was)
+	if ((st = bla_conv_bf16_pad(stream, d_del_out, Q2, batch, cout, h, w, Lq.hp, Lq.wp, Lq.top, Lq.left, Lq.dilate)) != BLA_OK) return st;
+	if ((st = launch_wgrad_implicit(s, Q2, Lq.hp, Lq.wp, cpo, Lq.top, Lq.left, Lq.dilate, p2.d, Lp.hp, Lp.wp, cpo, batch, k, 1, h, w, cout, cout, g->conv2, partial, plan2)) != BLA_OK)
+		return st;
+	if ((st = bla_conv_bf16_prepare_kernels(stream, p->conv2, A, cout, cout, k, 1)) != BLA_OK) return st;
+	bla_conv_bf16_epilogue ep = {};
+	ep.gate = p2; ep.out_f32 = sc->g_out_a;
+	if ((st = bla_conv2d_gathered_bf16_chained(stream, A, cout, Q2, batch, Lq.hp, Lq.wp, cpo, k, 1, h, w, &ep)) != BLA_OK) return st;
+	// (its A / B scratch is the workspace's first bytes: Q2 is consumed by then)
+	if ((st = bla_group_norm_ddx_bf16_map(stream, batch, sc->g_out_a, ws->c1, ws->mu2, ws->sd2, cout, group_size, h, w, sc->g_out_b, &q1)) != BLA_OK) return st;
+	// time-embedding projection, as the fp32 block forms it: per image the channel sums, their sum over the images, temb^T . dtb
+	if ((st = bla_col_sum_f32(stream, sc->g_out_b, batch * cout, hw, d_dtb, BLA_COLSUM_INTENDED)) != BLA_OK) return st;
+	if ((st = batch_sum(stream, d_dtb, g->time_b, batch, (size_t)cout)) != BLA_OK) return st;
+	if ((st = bla_gemm_f32(stream, 1, 0, tdim, cout, batch, d_temb, tdim, d_dtb, cout, g->time_w, cout, nullptr)) != BLA_OK) return st;
+	// first chunk
+	if ((st = slots()) != BLA_OK) return st;
+	if ((st = launch_wgrad_implicit(s, q1.d, Lq.hp, Lq.wp, cpo, Lq.top, Lq.left, Lq.dilate, p1.d, Lp.hp, Lp.wp, cpi, batch, k, 1, h, w, cout, cin, g->conv1, partial, plan1)) != BLA_OK)
+		return st;
+	const float* addend = d_del_out;
+	if (cin != cout) {   // the residual 1 x 1: its weight gradient always, its data gradient (the last norm gradient's addend) when del_x is wanted
+		void* g_res = nullptr;
+		if (d_del_x && (st = ensure_workspace2((size_t)batch * cin * hw * sizeof(float), &g_res)) != BLA_OK) return st;
+		if ((st = bla_conv2d_backward_gathered_f32_as_bf16(stream, d_del_out, d_x, p->res, g->res, (float*)g_res, batch, h, w, 1, cin, cout, 1, splits)) != BLA_OK) return st;
+		addend = (const float*)g_res;
+	}
+	if (!d_del_x) return BLA_OK;
+	if ((st = slots()) != BLA_OK) return st;
+	if ((st = bla_conv_bf16_prepare_kernels(stream, p->conv1, A, cout, cin, k, 1)) != BLA_OK) return st;
+	ep.gate = p1; ep.out_f32 = sc->g_in;
+	if ((st = bla_conv2d_gathered_bf16_chained(stream, A, cin, q1.d, batch, Lq.hp, Lq.wp, cpo, k, 1, h, w, &ep)) != BLA_OK) return st;
+	return bla_group_norm_ddx_gated_batched_f32(stream, batch, sc->g_in, d_del_x, d_x, ws->mu1, ws->sd1, cin, group_size, hw, nullptr, addend);
 }
 
 }  // extern "C"

@@ -165,6 +165,9 @@ bla_status resnet_backward_batched(void* stream, int batch, const float* d_del_o
                                    const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc, float* d_dtb, float* d_del_x, int h, int w,
                                    int cin, int cout, int k, int tdim, int group_size, int flags, const ResnetPads* pads);
 
+// bla_unet.hip: dst[i] = sum over the images of src[b][i], added in image order (the bf16 block of bla_conv_bf16.hip forms its time_b gradient with it too)
+bla_status batch_sum(void* stream, const float* src, float* dst, int batch, size_t n);
+
 // bla_unet_model.hip: the configuration a U-Net was created with (bla_diffusion.hip's sampler sizes its embeddings from it)
 const bla_unet_config* unet_config(const bla_unet* m);
 // bla_guidance.hip: true when the runtime does not know p as device memory (class labels handed in from the host are checked there); the Bernoulli

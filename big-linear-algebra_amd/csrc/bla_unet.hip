@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(kT) batch_sum_kernel(const float* __restrict__
 		dst[i] = acc;
 	}
 }
-static bla_status batch_sum(void* stream, const float* src, float* dst, int batch, size_t n) {
+bla_status batch_sum(void* stream, const float* src, float* dst, int batch, size_t n) {   // bla_internal.h
 	hipLaunchKernelGGL(batch_sum_kernel, dim3(blocks_for(n)), dim3(kT), 0, pick_stream(stream), src, dst, batch, n);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;

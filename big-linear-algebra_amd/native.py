@@ -57,6 +57,7 @@ ResnetParams = _ptr_struct("bla_resnet_params", ("conv1", "conv2", "time_w", "ti
 ResnetGrads = _ptr_struct("bla_resnet_grads", ("conv1", "conv2", "time_w", "time_b", "res"))
 ResnetWs = _ptr_struct("bla_resnet_ws", ("mu1", "sd1", "relu1", "c1", "tdense", "mu2", "sd2", "relu2", "dp", "c2", "res"))
 ResnetScratch = _ptr_struct("bla_resnet_scratch", ("g_out_a", "g_out_b", "g_in", "flip"))
+ResnetBf16Maps = _ptr_struct("bla_resnet_bf16_maps", ("p1", "p2", "q1"))
 
 _VP, _I, _F, _SZ, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_ulonglong
 # name -> (restype, argtypes); every symbol include/bla.h declares must appear here (tests check both ways)
@@ -149,6 +150,10 @@ SIGNATURES = {
     "bla_group_norm_ddx_gated_batched_f32": (_I, [_VP, _I] + [_VP] * 5 + [_I] * 3 + [_VP] * 2),
     "bla_attention_forward_batched_f32": (_I, [_VP, _I] + [_VP] * 8 + [_I] * 3), "bla_attention_backward_batched_f32": (_I, [_VP, _I] + [_VP] * 14 + [_I] * 4),
     "bla_resnet_forward_batched_f32": (_I, [_VP, _I] + [_VP] * 6 + [_I] * 7), "bla_resnet_backward_batched_f32": (_I, [_VP, _I] + [_VP] * 9 + [_I] * 7),
+    "bla_group_norm_relu_bf16_map": (_I, [_VP, _I, _VP] + [_I] * 4 + [_VP] * 4 + [C.POINTER(ConvBf16Map)]),
+    "bla_group_norm_ddx_bf16_map": (_I, [_VP, _I] + [_VP] * 4 + [_I] * 4 + [_VP, C.POINTER(ConvBf16Map)]),
+    "bla_resnet_forward_batched_bf16": (_I, [_VP, _I] + [_VP] * 6 + [_I] * 7 + [C.POINTER(ResnetBf16Maps)]),
+    "bla_resnet_backward_batched_bf16": (_I, [_VP, _I] + [_VP] * 9 + [_I] * 7 + [C.POINTER(ResnetBf16Maps), _I]),
     "bla_gemm_pair_f32": (_I, [_VP, _VP, _VP]), "bla_gemm_group_f32": (_I, [_VP, _VP, _I]),
     "bla_diag_mfma_rate": (_I, [_VP, _I, _I, _I, _VP]),
     "bla_graph_begin": (_I, [_VP]), "bla_graph_end": (_I, [_VP, C.POINTER(_VP)]), "bla_graph_launch": (_I, [_VP, _VP]),
@@ -488,3 +493,37 @@ def conv2d_weight_gradient_gathered_bf16(q, hq, wq, fp, top, left, dilate, p, hp
 def conv2d_backward_gathered_as_bf16(del_y, x, kern, del_kern, del_x, batch, h, w, k, c_in, f_n, stride, splits=0, stream=None):
     """Both gradients in bf16 (either output may be None) with del_y padded once for both: the implicit weight gradient, the gathered data gradient."""
     check(lib().bla_conv2d_backward_gathered_f32_as_bf16(stream, _ptr(del_y), _ptr(x), _ptr(kern), _ptr(del_kern), _ptr(del_x), batch, h, w, k, c_in, f_n, stride, splits))
+
+
+# ---- group norm into a bf16 map and the bf16 ResNet block (include/bla.h, DESIGN 3.25) -------------------------------------------------------------------
+def group_norm_relu_bf16_map(x, batch, channels, group_size, h, w, stdevs, means, dst=None, out_f32=None, drop=None, stream=None):
+    """Group norm + ReLU (+ dropout: drop is a uint8 device array, non-zero = dropped) of fp32 [batch][channels][h][w], written channel-last in bf16 into
+    dst = conv_bf16_map(...) and / or planar in fp32 into out_f32; means / stdevs [batch][groups] are outputs."""
+    m = dst or ConvBf16Map()
+    check(lib().bla_group_norm_relu_bf16_map(stream, batch, _ptr(x), channels, group_size, h, w, _ptr(drop), _ptr(stdevs), _ptr(means), _ptr(out_f32), C.byref(m)))
+    return dst
+
+
+def group_norm_ddx_bf16_map(source, data, means, stdevs, batch, channels, group_size, h, w, dst=None, dest_f32=None, stream=None):
+    """The group-norm gradient (no gate, no addend) of `source` at the forward input `data`, into dst = conv_bf16_map(...) and / or dest_f32."""
+    m = dst or ConvBf16Map()
+    check(lib().bla_group_norm_ddx_bf16_map(stream, batch, _ptr(source), _ptr(data), _ptr(means), _ptr(stdevs), channels, group_size, h, w, _ptr(dest_f32), C.byref(m)))
+    return dst
+
+
+def resnet_bf16_maps(p1, p2, q1=None):
+    """struct bla_resnet_bf16_maps around three zero-filled padded channel-last bf16 device arrays."""
+    return ResnetBf16Maps(_ptr(p1), _ptr(p2), _ptr(q1))
+
+
+def resnet_forward_batched_bf16(x, temb, params, drop, ws, result, batch, h, w, cin, cout, k, tdim, group_size, maps, stream=None):
+    """bla_resnet_forward_batched_f32's arguments (params: ResnetParams, ws: ResnetWs) with bf16 products inside; maps: resnet_bf16_maps(...)."""
+    check(lib().bla_resnet_forward_batched_bf16(stream, batch, _ptr(x), _ptr(temb), C.byref(params), _ptr(drop), C.byref(ws), _ptr(result), h, w, cin, cout, k, tdim,
+                                                group_size, C.byref(maps)))
+    return result
+
+
+def resnet_backward_batched_bf16(del_out, x, temb, params, ws, grads, scratch, dtb, del_x, batch, h, w, cin, cout, k, tdim, group_size, maps, splits=0, stream=None):
+    """bla_resnet_backward_batched_f32's arguments (del_x may be None) with bf16 products inside; splits: the weight gradients' K-split (0 = automatic)."""
+    check(lib().bla_resnet_backward_batched_bf16(stream, batch, _ptr(del_out), _ptr(x), _ptr(temb), C.byref(params), C.byref(ws), C.byref(grads), C.byref(scratch),
+                                                 _ptr(dtb), _ptr(del_x), h, w, cin, cout, k, tdim, group_size, C.byref(maps), splits))

@@ -462,6 +462,34 @@ BLA_API bla_status bla_conv2d_weight_gradient_gathered_bf16(void* stream, const 
  * d_del_x is given.  An addition: the backward entry above is not changed.  May grow the workspace (the capture rule above applies). */
 BLA_API bla_status bla_conv2d_backward_gathered_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern,
                                                             float* d_del_x, int batch, int h, int w, int k, int c_in, int f_n, int stride, int splits);
+/* ---- group norm into a bf16 map (csrc/bla_norm_bf16.hip) ---------------------------------------------------------------------------------
+ * Inside a ResNet block a convolution's input is the output of a group norm + ReLU (+ dropout), not of another convolution.  These two entries run the fp32
+ * group norm family's arithmetic and write the result where the bf16 product gathers it: a bla_conv_bf16_map, with the store contract of
+ * bla_conv2d_gathered_bf16_chained.  An addition: no fp32 norm entry or kernel changes.
+ * bla_group_norm_relu_bf16_map: d_in fp32 [batch][channels][h][w]; d_drop optional [batch][channels][h w], non-zero = dropped; d_means / d_stdevs
+ * [batch][groups], groups = ceil(channels / group_size) -- the layout bla_group_norm_relu_batched_f32 leaves; the last group of an image may be short and a
+ * group never reaches into the next image; d_out_f32 optional [batch][channels][h][w].  Per group of n elements (quirk Q3 kept: `stdevs` holds the variance
+ * and the output is divided by it):
+ *   m = (float)(sum x / n), fp64 sums;  v = (float) of the variance about that float m, fp64 sums;  y = (x - m) / v, one fp32 subtraction and one IEEE fp32
+ *   division;  y = y < 0 ? +0 : y;  y = drop ? +0 : y;  out_f32[b][c][y][x] = y (if given);  dst(b, y, x, c) = rne(y), bla_f32_to_bf16's rounding (if dst.d).
+ * The fp64 sums run in a fixed order: the same call gives the same bits every time.
+ * In dst, for every pixel ALL dst.cp channels of position (top + y dilate, left + x dilate) are written -- channels `channels` .. dst.cp - 1 as +0 -- in
+ * 16-byte stores of whole aligned 8-channel chunks, and nothing else is touched: halo, holes of a dilation and guards keep their bits.  A caller zero-fills
+ * a map once; its halo stays valid for every later pass.
+ * Two launches: a statistics kernel (one workgroup per image and group), then an apply kernel that reads 16 bytes at a time when w % 4 == 0 and d_in and
+ * d_out_f32 are 16-byte aligned and d_drop is 4-byte aligned, 4 bytes at a time otherwise (the same bits either way).
+ * BLA_ERR_INVALID, before the device is asked for and with every output untouched: a NULL d_in, d_means, d_stdevs or dst; dst->d and d_out_f32 both NULL; an
+ * extent <= 0; batch or h above 65,535; and, with dst->d: dst->cp != channels rounded up to 8, a map base off 16-byte alignment, top or left < 0,
+ * dilate < 1, a map the tensor does not fit (top + (h-1) dilate >= hp, left + (w-1) dilate >= wp), a map of 2^31 elements or more.  No workspace. */
+BLA_API bla_status bla_group_norm_relu_bf16_map(void* stream, int batch, const float* d_in, int channels, int group_size, int h, int w, const unsigned char* d_drop,
+                                                float* d_stdevs, float* d_means, float* d_out_f32, const bla_conv_bf16_map* dst);
+/* group_norm_ddx (lib/norm.c:52-93) as the fp32 kernels compute it, with no gate and no addend, into a bf16 map.  Per group, m and v from d_means / d_stdevs:
+ *   nv = (data - m) / v;  A = (float)(sum source / n), B = (float)(sum nv source / n), fp64 sums in a fixed order;  r = (source - A - nv B) / v;
+ *   dest_f32[b][c][y][x] = r (if given);  dst(b, y, x, c) = rne(r) (if dst.d); at least one of the two.
+ * dst is typically the data-gradient layout of the convolution below (bla_conv_bf16_layout(.., data_gradient = 1), dilate = its stride).  The store
+ * contract, the apply kernel and the refusals (plus a NULL d_source or d_data) are those of the entry above.  Workspace: 8 bytes per (image, group). */
+BLA_API bla_status bla_group_norm_ddx_bf16_map(void* stream, int batch, const float* d_source, const float* d_data, const float* d_means, const float* d_stdevs,
+                                               int channels, int group_size, int h, int w, float* d_dest_f32, const bla_conv_bf16_map* dst);
 /* What the last bla_conv2d_* call launched (host side only, as bla_gemm_last_kernel): reset on entry to every forward / backward call, one token per product
  * in launch order, separated by spaces.  A token is <role>:<path>[/<attribute>...]:
  *   role   fwd, wgrad, dgrad, dgrad.dil (the data gradient on a zero-dilated del_y); pair (both gradients in one launch of the tiled kernels, weight
@@ -574,6 +602,41 @@ BLA_API bla_status bla_resnet_forward_batched_f32(void* stream, int batch, const
 BLA_API bla_status bla_resnet_backward_batched_f32(void* stream, int batch, const float* d_del_out, const float* d_x, const float* d_temb,
                                                    const bla_resnet_params* p, const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc,
                                                    float* d_dtb, float* d_del_x, int h, int w, int cin, int cout, int k, int tdim, int group_size);
+/* The batched ResNet block with bf16 products inside: bla_resnet_{forward,backward}_batched_f32's arguments, every tensor with the same
+ * meaning, layout and type (x, temb, parameters, d_drop, result, del_out, gradients, d_dtb, del_x -- which may be NULL), plus the three padded channel-last
+ * bf16 maps that take the role of ws->relu1, ws->relu2 and ws->dp (those three are not written and may be NULL; mu1 / sd1, c1, tdense, mu2 / sd2, c2 and
+ * res keep their meaning).  With (hp, wp, top, left) = bla_conv_bf16_layout(h, w, k, 1, 0) and (hq, wq, ..) = bla_conv_bf16_layout(h, w, k, 1, 1):
+ *   maps->p1 [B][hp][wp][round8(cin)], maps->p2 [B][hp][wp][round8(cout)] in the forward layout, maps->q1 [B][hq][wq][round8(cout)] in the data-gradient
+ *   layout; 16-byte aligned; the caller zero-fills each ONCE -- the entries write pixel positions only, so the halos stay valid for every later pass.
+ * The kernel matrices and Q2 live in the context workspace: these calls may grow it (the capture rule of the _as_bf16 entries applies).  Any batch >= 1.
+ * Forward, exactly this composition of public entries, bit for bit:
+ *   (1) bla_group_norm_relu_bf16_map(x -> p1; mu1, sd1);  (2) tdense = temb . W_t + b_t by bla_gemm_f32 (bias_col), as the fp32 block;
+ *   (3) bla_conv_bf16_prepare_kernels(conv1, 0); c1 = bla_conv2d_gathered_bf16(A1, p1) with ep_bias = tdense, stride cout;
+ *   (4) bla_group_norm_relu_bf16_map(c1, d_drop -> p2; mu2, sd2);  (5) prepare_kernels(conv2, 0); c2 = bla_conv2d_gathered_bf16(A2, p2);
+ *   (6) r = x, or for cin != cout  ws->res = bla_conv2d_forward_batched_f32_as_bf16(x, res, k = 1);  (7) result = bla_sum_f32(c2, r).
+ * Backward (splits: the weight gradients' K-split, 0 = the automatic rule), exactly this composition, bit for bit:
+ *   (1) Q2 = bla_conv_bf16_pad(del_out) in conv2's data-gradient layout;  (2) g->conv2 = bla_conv2d_weight_gradient_gathered_bf16(Q2, p2, splits);
+ *   (3) prepare_kernels(conv2, 1); sc->g_out_a = bla_conv2d_gathered_bf16_chained(A2', Q2, stride 1, gate = p2, out_f32) -- the gate on the bf16 map is the
+ *       dropout mask and ReLU's derivative at once, as dp <= 0 is in the fp32 block;
+ *   (4) bla_group_norm_ddx_bf16_map(g_out_a, c1, mu2, sd2 -> dest_f32 = sc->g_out_b, dst = q1);
+ *   (5) d_dtb = bla_col_sum_f32(g_out_b, B cout, h w, INTENDED); g->time_b = the sum of d_dtb's rows in image order; g->time_w = temb^T . d_dtb (bla_gemm_f32);
+ *   (6) g->conv1 = bla_conv2d_weight_gradient_gathered_bf16(q1, p1, splits);
+ *   (7) with d_del_x: for cin != cout first bla_conv2d_backward_gathered_f32_as_bf16(del_out, x, res, g->res, g_res, k = 1, splits), g_res in the context's
+ *       second scratch; prepare_kernels(conv1, 1); sc->g_in = chained(A1', q1, gate = p1, out_f32);
+ *       del_x = bla_group_norm_ddx_gated_batched_f32(g_in, x, mu1, sd1, gate NULL, addend = del_out or g_res);
+ *   (8) with d_del_x == NULL the two data gradients and the last norm gradient are skipped; the weight gradients, the residual kernel's included, are formed.
+ * The gates read the bf16 activation the forward product actually multiplied: the derivative of the mixed-precision forward pass.  It differs from the fp32
+ * block's gate only where a positive fp32 activation rounds to bf16 zero.  sc->flip is not used.
+ * BLA_ERR_INVALID, before the device is asked for and with every output untouched: a NULL tensor, parameter, gradient, workspace field named above, scratch or
+ * map; an extent <= 0; splits < 0; a map off 16-byte alignment; cin != cout without the residual kernels (their gradient, ws->res). */
+typedef struct bla_resnet_bf16_maps { uint16_t *p1, *p2, *q1; } bla_resnet_bf16_maps;
+BLA_API bla_status bla_resnet_forward_batched_bf16(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p,
+                                                   const unsigned char* d_drop, const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k,
+                                                   int tdim, int group_size, const bla_resnet_bf16_maps* maps);
+BLA_API bla_status bla_resnet_backward_batched_bf16(void* stream, int batch, const float* d_del_out, const float* d_x, const float* d_temb,
+                                                    const bla_resnet_params* p, const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc,
+                                                    float* d_dtb, float* d_del_x, int h, int w, int cin, int cout, int k, int tdim, int group_size,
+                                                    const bla_resnet_bf16_maps* maps, int splits);
 
 /* ---- lib/layer.h on the device, batched: feed_forward (lib/layer.c:6-20) and back_propagate_errors with its recursion
  * (:48-107) for `batch` samples (columns) at once, parameters resident in one bucket (W_1, b_1, W_2, b_2, ...; W_l is n_l x n_{l-1}).  The
