@@ -11,7 +11,8 @@ from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilo
                      conv2d_backward_as_bf16, gemm_bf16_splitk_plan, gemm_bf16_splitk, conv2d_weight_gradient_as_bf16,
                      conv2d_weight_gradient_gathered_bf16, conv2d_backward_gathered_as_bf16, conv_bf16_map,
                      conv2d_gathered_bf16_chained, group_norm_relu_bf16_map, group_norm_ddx_bf16_map, resnet_bf16_maps,
-                     resnet_forward_batched_bf16, resnet_backward_batched_bf16)
+                     resnet_forward_batched_bf16, resnet_backward_batched_bf16, conv_bf16_prepare_kernels_table,
+                     conv_bf16_prep_chunks, unet_create_mixed, unet_products, UNET_PRODUCTS_F32, UNET_PRODUCTS_BF16)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
@@ -21,4 +22,5 @@ __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Ep
            "conv_bf16_layout", "conv_bf16_pad", "conv_bf16_prepare_kernels", "conv2d_gathered_bf16", "conv2d_forward_as_bf16",
            "conv2d_backward_as_bf16", "gemm_bf16_splitk_plan", "gemm_bf16_splitk", "conv2d_weight_gradient_as_bf16",
            "conv2d_weight_gradient_gathered_bf16", "conv2d_backward_gathered_as_bf16", "conv_bf16_map", "conv2d_gathered_bf16_chained",
-           "group_norm_relu_bf16_map", "group_norm_ddx_bf16_map", "resnet_bf16_maps", "resnet_forward_batched_bf16", "resnet_backward_batched_bf16"]
+           "group_norm_relu_bf16_map", "group_norm_ddx_bf16_map", "resnet_bf16_maps", "resnet_forward_batched_bf16", "resnet_backward_batched_bf16",
+           "conv_bf16_prepare_kernels_table", "conv_bf16_prep_chunks", "unet_create_mixed", "unet_products", "UNET_PRODUCTS_F32", "UNET_PRODUCTS_BF16"]

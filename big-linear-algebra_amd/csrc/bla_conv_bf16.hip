@@ -189,9 +189,9 @@ __global__ __launch_bounds__(256) void conv_bf16_pad_kernel(PadArgs16 a) {
 // ---- kernel matrices, tap-major: one thread per 8-element chunk of a destination row ------------------------------------------------------------------
 //   forward:        dst [f][(p k + q) Cp + c]                 = kern[f][c][p][q]          rows = F, inner = C
 //   data gradient:  dst [c][((k-1-p) k + (k-1-q)) Fp + f]     = kern[f][c][p][q]          rows = C, inner = F
-__global__ __launch_bounds__(256) void conv_bf16_kernels_kernel(const float* __restrict__ kern, uint16_t* __restrict__ dst, int f_n, int c_n, int k, int dgrad) {
+// (one chunk; both launches below run this body, so a table launch and a single launch cannot diverge)
+__device__ __forceinline__ void conv_bf16_kernels_chunk(const float* __restrict__ kern, uint16_t* __restrict__ dst, int f_n, int c_n, int k, int dgrad, long id) {
 	const int inner = dgrad ? f_n : c_n, rows = dgrad ? c_n : f_n, ip = (inner + 7) & ~7, chunks = k * k * (ip >> 3);
-	const long id = (long)blockIdx.x * 256 + threadIdx.x;
 	if (id >= (long)rows * chunks) return;
 	const int row = (int)(id / chunks), ch = (int)(id % chunks), tap = ch / (ip >> 3), i0 = (ch % (ip >> 3)) * 8;
 	const int tp = dgrad ? k - 1 - tap / k : tap / k, tq = dgrad ? k - 1 - tap % k : tap % k;
@@ -202,6 +202,17 @@ __global__ __launch_bounds__(256) void conv_bf16_kernels_kernel(const float* __r
 		v[j] = in < inner ? kern[(((size_t)f * c_n + c) * k + tp) * k + tq] : 0.f;
 	}
 	*(uint4*)(dst + (size_t)row * k * k * ip + (size_t)ch * 8) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+}
+
+__global__ __launch_bounds__(256) void conv_bf16_kernels_kernel(const float* __restrict__ kern, uint16_t* __restrict__ dst, int f_n, int c_n, int k, int dgrad) {
+	conv_bf16_kernels_chunk(kern, dst, f_n, c_n, k, dgrad, (long)blockIdx.x * 256 + threadIdx.x);
+}
+
+// Many matrices in one launch: grid (chunks of the largest job / 256, jobs).  A workgroup reads its job -- blockIdx.y is uniform, so the 32
+// bytes come through scalar loads -- and the threads past that job's extent return inside the chunk body.
+__global__ __launch_bounds__(256) void conv_bf16_kernels_table_kernel(const bla_conv_bf16_prep_job* __restrict__ jobs) {
+	const bla_conv_bf16_prep_job j = jobs[blockIdx.y];
+	conv_bf16_kernels_chunk(j.kern, j.dst, j.f_n, j.c_n, j.k, j.data_gradient != 0, (long)blockIdx.x * 256 + threadIdx.x);
 }
 
 // ---- the weight gradient's operands, both [row][n] with n = (image, i, j) at a pitch np = B Ho Wo rounded up to 8, the tail zero ----------------------
@@ -596,10 +607,50 @@ bla_status bla_conv2d_gathered_bf16_chained(void* stream, const uint16_t* d_a, i
 	return launch_gathered_chained(pick_stream(stream), d_a, rows, d_p, batch, hp, wp, cp, k, stride, ho, wo, *ep);
 }
 
+bla_status bla_conv_bf16_prepare_kernels_table(void* stream, const bla_conv_bf16_prep_job* d_jobs, int n_jobs, size_t max_chunks) {
+	const char* who = "bla_conv_bf16_prepare_kernels_table";
+	BLA_REQUIRE(n_jobs >= 0, BLA_ERR_INVALID, "%s: n_jobs %d", who, n_jobs);
+	if (n_jobs == 0) return BLA_OK;
+	BLA_REQUIRE(d_jobs, BLA_ERR_INVALID, "%s: NULL table with %d jobs", who, n_jobs);
+	BLA_REQUIRE(max_chunks > 0, BLA_ERR_INVALID, "%s: max_chunks 0 with %d jobs", who, n_jobs);
+	BLA_REQUIRE(n_jobs <= 65535 && (max_chunks + 255) / 256 < ((size_t)1 << 31), BLA_ERR_INVALID, "%s: %d jobs of up to %zu chunks exceed the grid", who, n_jobs, max_chunks);
+	bla_status st = require_ready();
+	if (st != BLA_OK) return st;
+	hipLaunchKernelGGL(conv_bf16_kernels_table_kernel, dim3((unsigned)((max_chunks + 255) / 256), (unsigned)n_jobs), dim3(256), 0, pick_stream(stream), d_jobs);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
 bla_status bla_conv2d_forward_batched_f32_as_bf16(void* stream, const float* d_x, const float* d_kern, float* d_out, int batch, int h, int w, int k, int c_in, int f_n,
                                                   int stride, const float* ep_bias, int ep_bias_stride) {
+	return conv2d_forward_as_bf16(stream, d_x, d_kern, d_out, batch, h, w, k, c_in, f_n, stride, ep_bias, ep_bias_stride, nullptr);
+}
+
+bla_status bla_conv2d_backward_gathered_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x, int batch,
+                                                    int h, int w, int k, int c_in, int f_n, int stride, int splits) {
+	return conv2d_backward_gathered_as_bf16(stream, d_del_y, d_x, d_kern, d_del_kern, d_del_x, batch, h, w, k, c_in, f_n, stride, splits, nullptr);
+}
+
+bla_status bla_resnet_forward_batched_bf16(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p, const unsigned char* d_drop,
+                                           const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k, int tdim, int group_size,
+                                           const bla_resnet_bf16_maps* maps) {
+	return resnet_forward_bf16(stream, batch, d_x, d_temb, p, d_drop, ws, d_result, h, w, cin, cout, k, tdim, group_size, maps, 0, nullptr);
+}
+
+bla_status bla_resnet_backward_batched_bf16(void* stream, int batch, const float* d_del_out, const float* d_x, const float* d_temb, const bla_resnet_params* p,
+                                            const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc, float* d_dtb, float* d_del_x, int h, int w,
+                                            int cin, int cout, int k, int tdim, int group_size, const bla_resnet_bf16_maps* maps, int splits) {
+	return resnet_backward_bf16(stream, batch, d_del_out, d_x, d_temb, p, ws, g, sc, d_dtb, d_del_x, h, w, cin, cout, k, tdim, group_size, maps, splits, 0, nullptr);
+}
+
+}  // extern "C"
+
+// ---- the internal forms (bla_internal.h): the public compositions above with an optional prepared kernel matrix; NULL = prepare it here, as always -------
+bla_status bla::conv2d_forward_as_bf16(void* stream, const float* d_x, const float* d_kern, float* d_out, int batch, int h, int w, int k, int c_in, int f_n, int stride,
+                                       const float* ep_bias, int ep_bias_stride, const uint16_t* prepared) {
 	const char* who = "bla_conv2d_forward_batched_f32_as_bf16";
 	BLA_REQUIRE(d_x && d_kern && d_out, BLA_ERR_INVALID, "%s: NULL pointer", who);
+	BLA_REQUIRE(aligned16(prepared), BLA_ERR_INVALID, "%s: the prepared matrix is not 16-byte aligned", who);
 	bla_status st = check_conv(who, batch, h, w, k, c_in, f_n, stride);
 	if (st != BLA_OK) return st;
 	const Geometry g = same_geometry(h, w, k, stride);
@@ -619,9 +670,11 @@ bla_status bla_conv2d_forward_batched_f32_as_bf16(void* stream, const float* d_x
 	uint16_t* A = (uint16_t*)(base + p_bytes);
 	hipStream_t s = pick_stream(stream);
 	if ((st = launch_pad(s, d_x, P, batch, c_in, h, w, L.hp, L.wp, L.top, L.left, 1)) != BLA_OK) return st;
-	if ((st = launch_kernels(s, d_kern, A, f_n, c_in, k, 0)) != BLA_OK) return st;
-	return launch_gathered(s, A, f_n, P, batch, L.hp, L.wp, cp, k, stride, g.ho, g.wo, d_out, ep_bias, ep_bias_stride);
+	if (!prepared && (st = launch_kernels(s, d_kern, A, f_n, c_in, k, 0)) != BLA_OK) return st;
+	return launch_gathered(s, prepared ? prepared : A, f_n, P, batch, L.hp, L.wp, cp, k, stride, g.ho, g.wo, d_out, ep_bias, ep_bias_stride);
 }
+
+extern "C" {
 
 bla_status bla_conv2d_backward_batched_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x, int batch,
                                                    int h, int w, int k, int c_in, int f_n, int stride) {
@@ -701,10 +754,14 @@ bla_status bla_conv2d_weight_gradient_gathered_bf16(void* stream, const uint16_t
 	return launch_wgrad_implicit(pick_stream(stream), d_q, hq, wq, fp, top, left, dilate, d_p, hp, wp, cp, batch, k, stride, ho, wo, f_n, c_n, d_del_kern, (float*)ws, plan);
 }
 
-bla_status bla_conv2d_backward_gathered_f32_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x, int batch,
-                                                    int h, int w, int k, int c_in, int f_n, int stride, int splits) {
+}  // extern "C"
+
+// prepared: the DATA-GRADIENT matrix (bla_conv_bf16_prepare_kernels(.., 1))
+bla_status bla::conv2d_backward_gathered_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x, int batch,
+                                                 int h, int w, int k, int c_in, int f_n, int stride, int splits, const uint16_t* prepared) {
 	const char* who = "bla_conv2d_backward_gathered_f32_as_bf16";
 	BLA_REQUIRE(d_del_y, BLA_ERR_INVALID, "%s: NULL del_y", who);
+	BLA_REQUIRE(aligned16(prepared), BLA_ERR_INVALID, "%s: the prepared matrix is not 16-byte aligned", who);
 	BLA_REQUIRE(!d_del_kern || d_x, BLA_ERR_INVALID, "%s: the weight gradient needs the forward input", who);
 	BLA_REQUIRE(!d_del_x || d_kern, BLA_ERR_INVALID, "%s: the data gradient needs the kernels", who);
 	BLA_REQUIRE(splits >= 0, BLA_ERR_INVALID, "%s: splits %d", who, splits);
@@ -746,8 +803,8 @@ bla_status bla_conv2d_backward_gathered_f32_as_bf16(void* stream, const float* d
 	if (d_del_kern && (st = launch_wgrad_implicit(s, Q, Lq.hp, Lq.wp, fp, Lq.top, Lq.left, Lq.dilate, P, Lp.hp, Lp.wp, cp, batch, k, stride, g.ho, g.wo, f_n, c_in, d_del_kern,
 	                                              partial, plan)) != BLA_OK) return st;
 	if (d_del_x) {
-		if ((st = launch_kernels(s, d_kern, A, f_n, c_in, k, 1)) != BLA_OK) return st;
-		if ((st = launch_gathered(s, A, c_in, Q, batch, Lq.hp, Lq.wp, fp, k, 1, h, w, d_del_x, nullptr, 0)) != BLA_OK) return st;
+		if (!prepared && (st = launch_kernels(s, d_kern, A, f_n, c_in, k, 1)) != BLA_OK) return st;
+		if ((st = launch_gathered(s, prepared ? prepared : A, c_in, Q, batch, Lq.hp, Lq.wp, fp, k, 1, h, w, d_del_x, nullptr, 0)) != BLA_OK) return st;
 	}
 	return BLA_OK;
 }
@@ -756,10 +813,15 @@ bla_status bla_conv2d_backward_gathered_f32_as_bf16(void* stream, const float* d
 // Everything in the context workspace is consumed by a launch that is already on the stream before the next step writes there, so the steps share it from
 // its base: forward [A]; backward [Q2 | A | partials].  The two 1 x 1 residual entries size and lay out the workspace themselves (they may grow it, which
 // waits for the device first); nothing of the block's is live in it across those calls, and the base is asked for again behind them.
-bla_status bla_resnet_forward_batched_bf16(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p, const unsigned char* d_drop,
-                                           const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k, int tdim, int group_size,
-                                           const bla_resnet_bf16_maps* maps) {
+// The internal form (bla_internal.h): the fp32 internal block's two flags -- RESNET_TDENSE_READY: ws->tdense is already filled; RESNET_DEFER_TIME_GRADS: d_dtb
+// receives the per-image channel sums and the caller forms the time gradients -- and optional prepared kernel matrices (prep NULL, or a NULL field: the
+// block prepares that matrix itself in the workspace).  The public entries pass no flags and no matrices.
+bla_status bla::resnet_forward_bf16(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p, const unsigned char* d_drop,
+                                    const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k, int tdim, int group_size,
+                                    const bla_resnet_bf16_maps* maps, int flags, const ResnetBf16Prep* prep) {
 	const char* who = "bla_resnet_forward_batched_bf16";
+	const ResnetBf16Prep none = {};
+	const ResnetBf16Prep& pr = prep ? *prep : none;
 	BLA_REQUIRE(batch > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && k > 0 && tdim > 0 && group_size > 0, BLA_ERR_INVALID, "%s: extent <= 0", who);
 	BLA_REQUIRE(d_x && d_temb && p && d_drop && ws && d_result && maps && p->conv1 && p->conv2 && p->time_w && p->time_b, BLA_ERR_INVALID, "%s: NULL operand", who);
 	BLA_REQUIRE(ws->mu1 && ws->sd1 && ws->c1 && ws->tdense && ws->mu2 && ws->sd2 && ws->c2, BLA_ERR_INVALID, "%s: NULL workspace field", who);
@@ -773,29 +835,34 @@ bla_status bla_resnet_forward_batched_bf16(void* stream, int batch, const float*
 	if ((st = check_gathered_shape(cout, batch, L.hp, L.wp, cpi, k, 1, h, w, cout)) != BLA_OK || (st = check_gathered_shape(cout, batch, L.hp, L.wp, cpo, k, 1, h, w, 0)) != BLA_OK) return st;
 	if ((st = require_ready()) != BLA_OK) return st;
 	if ((st = bla_group_norm_relu_bf16_map(stream, batch, d_x, cin, group_size, h, w, nullptr, ws->sd1, ws->mu1, nullptr, &p1)) != BLA_OK) return st;
-	bla_gemm_epilogue tep = {};
-	tep.alpha = 1.f; tep.bias_col = p->time_b;
-	if ((st = bla_gemm_f32(stream, 0, 0, batch, cout, tdim, d_temb, tdim, p->time_w, cout, ws->tdense, cout, &tep)) != BLA_OK) return st;
+	if (!(flags & RESNET_TDENSE_READY)) {
+		bla_gemm_epilogue tep = {};
+		tep.alpha = 1.f; tep.bias_col = p->time_b;
+		if ((st = bla_gemm_f32(stream, 0, 0, batch, cout, tdim, d_temb, tdim, p->time_w, cout, ws->tdense, cout, &tep)) != BLA_OK) return st;
+	}
 	void* base = nullptr;
 	if ((st = ensure_workspace(kernels_bytes(cout, k, cpi > cpo ? cpi : cpo), &base)) != BLA_OK) return st;
 	uint16_t* A = (uint16_t*)base;
-	if ((st = bla_conv_bf16_prepare_kernels(stream, p->conv1, A, cout, cin, k, 0)) != BLA_OK) return st;
-	if ((st = bla_conv2d_gathered_bf16(stream, A, cout, p1.d, batch, L.hp, L.wp, cpi, k, 1, h, w, ws->c1, ws->tdense, cout)) != BLA_OK) return st;
+	if (!pr.k1_fwd && (st = bla_conv_bf16_prepare_kernels(stream, p->conv1, A, cout, cin, k, 0)) != BLA_OK) return st;
+	if ((st = bla_conv2d_gathered_bf16(stream, pr.k1_fwd ? pr.k1_fwd : A, cout, p1.d, batch, L.hp, L.wp, cpi, k, 1, h, w, ws->c1, ws->tdense, cout)) != BLA_OK) return st;
 	if ((st = bla_group_norm_relu_bf16_map(stream, batch, ws->c1, cout, group_size, h, w, d_drop, ws->sd2, ws->mu2, nullptr, &p2)) != BLA_OK) return st;
-	if ((st = bla_conv_bf16_prepare_kernels(stream, p->conv2, A, cout, cout, k, 0)) != BLA_OK) return st;
-	if ((st = bla_conv2d_gathered_bf16(stream, A, cout, p2.d, batch, L.hp, L.wp, cpo, k, 1, h, w, ws->c2, nullptr, 0)) != BLA_OK) return st;
+	if (!pr.k2_fwd && (st = bla_conv_bf16_prepare_kernels(stream, p->conv2, A, cout, cout, k, 0)) != BLA_OK) return st;
+	if ((st = bla_conv2d_gathered_bf16(stream, pr.k2_fwd ? pr.k2_fwd : A, cout, p2.d, batch, L.hp, L.wp, cpo, k, 1, h, w, ws->c2, nullptr, 0)) != BLA_OK) return st;
 	const float* r = d_x;
 	if (cin != cout) {
-		if ((st = bla_conv2d_forward_batched_f32_as_bf16(stream, d_x, p->res, ws->res, batch, h, w, 1, cin, cout, 1, nullptr, 0)) != BLA_OK) return st;
+		if ((st = conv2d_forward_as_bf16(stream, d_x, p->res, ws->res, batch, h, w, 1, cin, cout, 1, nullptr, 0, pr.res_fwd)) != BLA_OK) return st;
 		r = ws->res;
 	}
 	return bla_sum_f32(stream, d_result, ws->c2, r, (size_t)batch * cout * h * w);
 }
 
-bla_status bla_resnet_backward_batched_bf16(void* stream, int batch, const float* d_del_out, const float* d_x, const float* d_temb, const bla_resnet_params* p,
-                                            const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc, float* d_dtb, float* d_del_x, int h, int w,
-                                            int cin, int cout, int k, int tdim, int group_size, const bla_resnet_bf16_maps* maps, int splits) {
+bla_status bla::resnet_backward_bf16(void* stream, int batch, const float* d_del_out, const float* d_x, const float* d_temb, const bla_resnet_params* p,
+                                     const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc, float* d_dtb, float* d_del_x, int h, int w,
+                                     int cin, int cout, int k, int tdim, int group_size, const bla_resnet_bf16_maps* maps, int splits, int flags,
+                                     const ResnetBf16Prep* prep) {
 	const char* who = "bla_resnet_backward_batched_bf16";
+	const ResnetBf16Prep none = {};
+	const ResnetBf16Prep& pr = prep ? *prep : none;
 	BLA_REQUIRE(batch > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && k > 0 && tdim > 0 && group_size > 0, BLA_ERR_INVALID, "%s: extent <= 0", who);
 	BLA_REQUIRE(splits >= 0, BLA_ERR_INVALID, "%s: splits %d", who, splits);
 	BLA_REQUIRE(d_del_out && d_x && d_temb && p && ws && g && sc && d_dtb && maps && p->conv1 && p->conv2 && g->conv1 && g->conv2 && g->time_w && g->time_b && sc->g_out_a &&
@@ -834,16 +901,18 @@ bla_status bla_resnet_backward_batched_bf16(void* stream, int batch, const float
 	if ((st = bla_conv_bf16_pad(stream, d_del_out, Q2, batch, cout, h, w, Lq.hp, Lq.wp, Lq.top, Lq.left, Lq.dilate)) != BLA_OK) return st;
 	if ((st = launch_wgrad_implicit(s, Q2, Lq.hp, Lq.wp, cpo, Lq.top, Lq.left, Lq.dilate, p2.d, Lp.hp, Lp.wp, cpo, batch, k, 1, h, w, cout, cout, g->conv2, partial, plan2)) != BLA_OK)
 		return st;
-	if ((st = bla_conv_bf16_prepare_kernels(stream, p->conv2, A, cout, cout, k, 1)) != BLA_OK) return st;
+	if (!pr.k2_bwd && (st = bla_conv_bf16_prepare_kernels(stream, p->conv2, A, cout, cout, k, 1)) != BLA_OK) return st;
 	bla_conv_bf16_epilogue ep = {};
 	ep.gate = p2; ep.out_f32 = sc->g_out_a;
-	if ((st = bla_conv2d_gathered_bf16_chained(stream, A, cout, Q2, batch, Lq.hp, Lq.wp, cpo, k, 1, h, w, &ep)) != BLA_OK) return st;
+	if ((st = bla_conv2d_gathered_bf16_chained(stream, pr.k2_bwd ? pr.k2_bwd : A, cout, Q2, batch, Lq.hp, Lq.wp, cpo, k, 1, h, w, &ep)) != BLA_OK) return st;
 	// (its A / B scratch is the workspace's first bytes: Q2 is consumed by then)
 	if ((st = bla_group_norm_ddx_bf16_map(stream, batch, sc->g_out_a, ws->c1, ws->mu2, ws->sd2, cout, group_size, h, w, sc->g_out_b, &q1)) != BLA_OK) return st;
 	// time-embedding projection, as the fp32 block forms it: per image the channel sums, their sum over the images, temb^T . dtb
 	if ((st = bla_col_sum_f32(stream, sc->g_out_b, batch * cout, hw, d_dtb, BLA_COLSUM_INTENDED)) != BLA_OK) return st;
-	if ((st = batch_sum(stream, d_dtb, g->time_b, batch, (size_t)cout)) != BLA_OK) return st;
-	if ((st = bla_gemm_f32(stream, 1, 0, tdim, cout, batch, d_temb, tdim, d_dtb, cout, g->time_w, cout, nullptr)) != BLA_OK) return st;
+	if (!(flags & RESNET_DEFER_TIME_GRADS)) {
+		if ((st = batch_sum(stream, d_dtb, g->time_b, batch, (size_t)cout)) != BLA_OK) return st;
+		if ((st = bla_gemm_f32(stream, 1, 0, tdim, cout, batch, d_temb, tdim, d_dtb, cout, g->time_w, cout, nullptr)) != BLA_OK) return st;
+	}
 	// first chunk
 	if ((st = slots()) != BLA_OK) return st;
 	if ((st = launch_wgrad_implicit(s, q1.d, Lq.hp, Lq.wp, cpo, Lq.top, Lq.left, Lq.dilate, p1.d, Lp.hp, Lp.wp, cpi, batch, k, 1, h, w, cout, cin, g->conv1, partial, plan1)) != BLA_OK)
@@ -852,15 +921,13 @@ bla_status bla_resnet_backward_batched_bf16(void* stream, int batch, const float
 	if (cin != cout) {   // the residual 1 x 1: its weight gradient always, its data gradient (the last norm gradient's addend) when del_x is wanted
 		void* g_res = nullptr;
 		if (d_del_x && (st = ensure_workspace2((size_t)batch * cin * hw * sizeof(float), &g_res)) != BLA_OK) return st;
-		if ((st = bla_conv2d_backward_gathered_f32_as_bf16(stream, d_del_out, d_x, p->res, g->res, (float*)g_res, batch, h, w, 1, cin, cout, 1, splits)) != BLA_OK) return st;
+		if ((st = conv2d_backward_gathered_as_bf16(stream, d_del_out, d_x, p->res, g->res, (float*)g_res, batch, h, w, 1, cin, cout, 1, splits, pr.res_bwd)) != BLA_OK) return st;
 		addend = (const float*)g_res;
 	}
 	if (!d_del_x) return BLA_OK;
 	if ((st = slots()) != BLA_OK) return st;
-	if ((st = bla_conv_bf16_prepare_kernels(stream, p->conv1, A, cout, cin, k, 1)) != BLA_OK) return st;
+	if (!pr.k1_bwd && (st = bla_conv_bf16_prepare_kernels(stream, p->conv1, A, cout, cin, k, 1)) != BLA_OK) return st;
 	ep.gate = p1; ep.out_f32 = sc->g_in;
-	if ((st = bla_conv2d_gathered_bf16_chained(stream, A, cin, q1.d, batch, Lq.hp, Lq.wp, cpo, k, 1, h, w, &ep)) != BLA_OK) return st;
+	if ((st = bla_conv2d_gathered_bf16_chained(stream, pr.k1_bwd ? pr.k1_bwd : A, cin, q1.d, batch, Lq.hp, Lq.wp, cpo, k, 1, h, w, &ep)) != BLA_OK) return st;
 	return bla_group_norm_ddx_gated_batched_f32(stream, batch, sc->g_in, d_del_x, d_x, ws->mu1, ws->sd1, cin, group_size, hw, nullptr, addend);
 }
-
-}  // extern "C"

@@ -165,6 +165,23 @@ bla_status resnet_backward_batched(void* stream, int batch, const float* d_del_o
                                    const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc, float* d_dtb, float* d_del_x, int h, int w,
                                    int cin, int cout, int k, int tdim, int group_size, int flags, const ResnetPads* pads);
 
+// bla_conv_bf16.hip: the bf16 compositions as the mixed-precision U-Net calls them.  `prepared` / the fields of ResnetBf16Prep: the kernel
+// matrix in the form the product reads (bla_conv_bf16_prepare_kernels' output, 16-byte aligned), made by the caller for MANY convolutions in one
+// bla_conv_bf16_prepare_kernels_table launch; NULL = the composition prepares it in the workspace, as the public entry does.  flags: RESNET_TDENSE_READY and
+// RESNET_DEFER_TIME_GRADS, with the fp32 block's meaning.  The public entries are these with no flags and no matrices.
+struct ResnetBf16Prep { const uint16_t *k1_fwd, *k2_fwd, *res_fwd, *k1_bwd, *k2_bwd, *res_bwd; };
+bla_status conv2d_forward_as_bf16(void* stream, const float* d_x, const float* d_kern, float* d_out, int batch, int h, int w, int k, int c_in, int f_n, int stride,
+                                  const float* ep_bias, int ep_bias_stride, const uint16_t* prepared);
+bla_status conv2d_backward_gathered_as_bf16(void* stream, const float* d_del_y, const float* d_x, const float* d_kern, float* d_del_kern, float* d_del_x, int batch,
+                                            int h, int w, int k, int c_in, int f_n, int stride, int splits, const uint16_t* prepared);
+bla_status resnet_forward_bf16(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p, const unsigned char* d_drop,
+                               const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k, int tdim, int group_size,
+                               const bla_resnet_bf16_maps* maps, int flags, const ResnetBf16Prep* prep);
+bla_status resnet_backward_bf16(void* stream, int batch, const float* d_del_out, const float* d_x, const float* d_temb, const bla_resnet_params* p,
+                                const bla_resnet_ws* ws, const bla_resnet_grads* g, const bla_resnet_scratch* sc, float* d_dtb, float* d_del_x, int h, int w,
+                                int cin, int cout, int k, int tdim, int group_size, const bla_resnet_bf16_maps* maps, int splits, int flags,
+                                const ResnetBf16Prep* prep);
+
 // bla_unet.hip: dst[i] = sum over the images of src[b][i], added in image order (the bf16 block of bla_conv_bf16.hip forms its time_b gradient with it too)
 bla_status batch_sum(void* stream, const float* src, float* dst, int batch, size_t n);
 

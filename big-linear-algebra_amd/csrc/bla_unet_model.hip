@@ -19,6 +19,8 @@
 //   * convolution gradients land in the gradient bucket (as written :1203,1216 hand conv_ddx the parameters as the sink).
 // Every block is pinned on its own against the reference's functions (tests/test_resnet.py, test_attention.py, test_conv_gpu.py,
 // test_unet_glue.py); the composition is pinned against the same composition of the oracle's blocks (tests/test_unet_model.py).
+// bla_unet_create_mixed(.., BLA_UNET_PRODUCTS_BF16) is the same composition with the ResNet blocks and the stand-alone convolutions on the bf16 stack:
+// same buckets, same entries, one stream; pinned against a float64 restatement with the compositions' roundings (tests/test_unet_bf16_{host,gpu}.py).
 #include "bla_internal.h"
 #include <cstring>
 #include <string>
@@ -36,6 +38,8 @@ struct Res {
 	ResnetPads pads = {nullptr, nullptr, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // batched: zero-haloed padded copies of the two convolution inputs, filled by the norm kernels
 	float* dtb = nullptr;                 // batched: per-image channel sums of the time-projection gradient [B][cout], kept until the pass's last launch
 	size_t drop_off;                      // offset of this block's dropout decisions in the caller's mask
+	bla_resnet_bf16_maps maps = {nullptr, nullptr, nullptr};   // bf16 products: the block's own padded channel-last maps (p1, p2: the gates, kept from forward to backward)
+	ResnetBf16Prep prep16 = {};           // bf16 products: the block's kernel matrices in the model's table launches (all NULL: the block prepares them itself)
 };
 // one ResNet block's time-embedding projection (model/cifar_unet.c:1051-1052) and its gradients (:1191-1199); all 18 run as one launch each way
 struct TimeJob { const float* w; const float* bias; float* tdense; const float* dtb; float* g_tw; float* g_tb; int cout; };
@@ -51,6 +55,7 @@ struct Conv {
 	float* out;
 	bool present;
 	const float *prep_fwd = nullptr, *prep_bwd = nullptr;   // batched: the kernel matrix as the forward / data-gradient product reads it (KernelPrepJob outputs)
+	const uint16_t *prep16_fwd = nullptr, *prep16_bwd = nullptr;   // bf16 products: the same from the bf16 table launches
 };
 constexpr size_t kNone = (size_t)-1;
 }  // namespace
@@ -58,6 +63,7 @@ constexpr size_t kNone = (size_t)-1;
 struct bla_unet {
 	bla_unet_config cfg;
 	int batch = 1;
+	int products = BLA_UNET_PRODUCTS_F32;   // BLA_UNET_PRODUCTS_BF16: the blocks and the stand-alone convolutions on the bf16 stack, one stream
 	int H[4], W[4];
 	std::vector<Tensor> tensors;
 	size_t count = 0, drop_count = 0;
@@ -84,6 +90,9 @@ struct bla_unet {
 	KernelPrepJob *prep_fwd = nullptr, *prep_bwd = nullptr;   // device: every convolution's kernel matrix re-ordered / flipped in ONE launch per pass
 	int n_prep_fwd = 0, n_prep_bwd = 0;
 	size_t prep_max = 0;
+	bla_conv_bf16_prep_job *prep16_fwd = nullptr, *prep16_bwd = nullptr;   // device, bf16 products: every bf16 kernel matrix of a pass in ONE launch
+	int n_prep16_fwd = 0, n_prep16_bwd = 0;
+	size_t prep16_max_fwd = 0, prep16_max_bwd = 0;                         // the largest job's 8-element chunks
 	float *dtb = nullptr, *partials = nullptr;   // batched blocks: per-image time-bias sums [B][Cout], per-image attention weight gradients [B][C*d]
 	bla_resnet_scratch sc = {};
 	bla_attention_ws agrad = {};
@@ -135,7 +144,36 @@ bool keep_relu2(const bla_unet* m, const Res& r) {
 	const int gs = m->cfg.group_size;
 	return !(m->batch > 1 && (r.h * r.w) % 4 == 0 && (r.cout % gs == 0 || r.cout < gs));
 }
+// a zero-filled padded channel-last bf16 map [B][hp][wp][round8(c)] in the layout bla_conv_bf16_layout states (the blocks write pixel positions only: the halo stays)
+bla_status alloc_map(bla_unet* m, uint16_t** p, int c, int h, int w, bool data_gradient) {
+	int hp, wp, top, left, dilate;
+	bla_status st = bla_conv_bf16_layout(h, w, m->cfg.kernel, 1, data_gradient, &hp, &wp, &top, &left, &dilate);
+	if (st) return st;
+	const size_t bytes = (size_t)m->batch * hp * wp * round8(c) * sizeof(uint16_t);
+	float* q = nullptr;
+	if ((st = dalloc(m, &q, (bytes + 3) / 4))) return st;
+	BLA_HIP(hipMemsetAsync(q, 0, bytes, ctx().stream));
+	*p = (uint16_t*)q;
+	return BLA_OK;
+}
+// bf16 products: relu1, relu2, dp, the fp32 padded copies and the fp32 prepared kernels have no reader; the three maps take their place.  Every block its own
+// p1 / p2 (the gates of its backward pass) and its own q1.  The per-image channel sums (dtb) at every batch: the time gradients are always deferred here.
+bla_status alloc_res_bf16(bla_unet* m, Res& r) {
+	const size_t hw = (size_t)r.h * r.w * m->batch;
+	const int gs = m->cfg.group_size, g1 = (r.cin + gs - 1) / gs * m->batch, g2 = (r.cout + gs - 1) / gs * m->batch;
+	bla_status st;
+	r.ws = bla_resnet_ws{};
+	if ((st = dalloc(m, &r.ws.mu1, g1)) || (st = dalloc(m, &r.ws.sd1, g1)) || (st = dalloc(m, &r.ws.c1, r.cout * hw)) || (st = dalloc(m, &r.ws.tdense, (size_t)r.cout * m->batch)) ||
+	    (st = dalloc(m, &r.ws.mu2, g2)) || (st = dalloc(m, &r.ws.sd2, g2)) || (st = dalloc(m, &r.ws.c2, r.cout * hw)) || (st = dalloc(m, &r.result, r.cout * hw)) ||
+	    (st = dalloc(m, &r.dtb, (size_t)r.cout * m->batch)))
+		return st;
+	if (r.cin != r.cout && (st = dalloc(m, &r.ws.res, r.cout * hw))) return st;
+	if ((st = alloc_map(m, &r.maps.p1, r.cin, r.h, r.w, false)) || (st = alloc_map(m, &r.maps.p2, r.cout, r.h, r.w, false)) || (st = alloc_map(m, &r.maps.q1, r.cout, r.h, r.w, true)))
+		return st;
+	return BLA_OK;
+}
 bla_status alloc_res(bla_unet* m, Res& r) {
+	if (m->products == BLA_UNET_PRODUCTS_BF16) return alloc_res_bf16(m, r);
 	const size_t hw = (size_t)r.h * r.w * m->batch;   // (every buffer of the block: B times its single-image size)
 	const int gs = m->cfg.group_size, g1 = (r.cin + gs - 1) / gs * m->batch, g2 = (r.cout + gs - 1) / gs * m->batch;
 	bla_status st;
@@ -318,7 +356,13 @@ extern "C" {
 
 bla_status bla_unet_create(bla_unet** out, const bla_unet_config* cfg) { return bla_unet_create_batched(out, cfg, 1); }
 
-bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, int batch) {
+bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, int batch) { return bla_unet_create_mixed(out, cfg, batch, BLA_UNET_PRODUCTS_F32); }
+
+int bla_unet_products(const bla_unet* m) { return m ? m->products : BLA_UNET_PRODUCTS_F32; }
+
+bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int batch, int products) {
+	BLA_REQUIRE(products == BLA_UNET_PRODUCTS_F32 || products == BLA_UNET_PRODUCTS_BF16, BLA_ERR_INVALID, "bla_unet_create_mixed: products %d (BLA_UNET_PRODUCTS_F32 or _BF16)", products);
+	const bool bf16 = products == BLA_UNET_PRODUCTS_BF16;
 	bla_status st = require_ready();
 	if (st) return st;
 	BLA_REQUIRE(out && cfg, BLA_ERR_INVALID, "null argument");
@@ -329,6 +373,7 @@ bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, i
 	bla_unet* m = new bla_unet();
 	m->cfg = *cfg;
 	m->batch = batch;
+	m->products = products;
 	const size_t B = (size_t)batch;
 	const int* D = cfg->dims;
 	m->H[0] = cfg->image_h; m->W[0] = cfg->image_w;
@@ -409,7 +454,7 @@ bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, i
 		return fail(st);
 	max_flip = std::max(max_flip, (size_t)cfg->in_channels * D[0] * cfg->kernel * cfg->kernel);
 	static const bool side_on = [] { const char* e = getenv("BLA_UNET_SIDE"); return !(e && e[0] == '0'); }();
-	m->side = side_on && batch > 1 && 48 * max_act * sizeof(float) <= ((size_t)16 << 30);   // (the write-once pool: at most 16 GiB of it -- beyond that, one stream and three rotating buffers)
+	m->side = side_on && !bf16 && batch > 1 && 48 * max_act * sizeof(float) <= ((size_t)16 << 30);   // (the write-once pool: at most 16 GiB of it -- beyond that, one stream and three rotating buffers; bf16 products: one stream)
 	if (m->side) {
 		for (int i = 0; i < 48; i++) { float* q; if ((st = dalloc(m, &q, max_act))) return fail(st); m->gpool.push_back(q); }
 		for (Res& r : m->res) if ((st = dalloc(m, &r.pads.g_out_b, (size_t)r.cout * r.h * r.w * B))) return fail(st);
@@ -440,7 +485,7 @@ bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, i
 		TimeJob jobs[18];
 		for (int i = 0; i < 18; i++) {
 			const Res& r = m->res[i];
-			jobs[i] = TimeJob{m->params + r.tw, m->params + r.tb, r.ws.tdense, batch > 1 ? r.dtb : m->grads + r.tb, m->grads + r.tw, m->grads + r.tb, r.cout};
+			jobs[i] = TimeJob{m->params + r.tw, m->params + r.tb, r.ws.tdense, batch > 1 || bf16 ? r.dtb : m->grads + r.tb, m->grads + r.tw, m->grads + r.tb, r.cout};
 		}
 		void* ej = nullptr;
 		BLA_HIP(hipMalloc(&ej, sizeof jobs));
@@ -449,7 +494,53 @@ bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, i
 		BLA_HIP(hipMemcpy(ej, jobs, sizeof jobs, hipMemcpyHostToDevice));
 	}
 	static const bool prep_on = [] { const char* e = getenv("BLA_UNET_PREP"); return !(e && e[0] == '0'); }();
-	if (batch > 1 && prep_on) {
+	if (bf16) {
+		// One table launch at the head of each pass writes every bf16 kernel matrix of that pass into a matrix the model owns: the forward set is
+		// every convolution, the data-gradient set the same minus block 0's conv1 (nothing consumes the gradient of the image; its residual 1 x 1 likewise).
+		// BLA_UNET_BF16_PREP=0, read HERE at every create call: no tables, every composition prepares its own matrix in the workspace -- the same bits.
+		const char* e = getenv("BLA_UNET_BF16_PREP");
+		if (!(e && e[0] == '0')) {
+			std::vector<bla_conv_bf16_prep_job> jf, jb;
+			auto add = [&](size_t kern_off, int k, int cin, int cout, bool dgrad, const uint16_t** dst_out) -> bla_status {
+				const int rows = dgrad ? cin : cout, ip = round8(dgrad ? cout : cin);
+				const size_t chunks = (size_t)rows * k * k * (ip / 8);
+				float* q = nullptr;
+				bla_status s2 = dalloc(m, &q, chunks * 4);      // 8 bf16 elements = 4 floats a chunk; hipMalloc: 16-byte aligned
+				if (s2) return s2;
+				(dgrad ? jb : jf).push_back(bla_conv_bf16_prep_job{m->params + kern_off, (uint16_t*)q, cout, cin, k, dgrad ? 1 : 0});
+				size_t& mx = dgrad ? m->prep16_max_bwd : m->prep16_max_fwd;
+				mx = std::max(mx, chunks);
+				*dst_out = (uint16_t*)q;
+				return BLA_OK;
+			};
+			for (int i = 0; i < 18; i++) {
+				Res& r = m->res[i];
+				if ((st = add(r.conv1, cfg->kernel, r.cin, r.cout, false, &r.prep16.k1_fwd)) || (st = add(r.conv2, cfg->kernel, r.cout, r.cout, false, &r.prep16.k2_fwd)) ||
+				    (st = add(r.conv2, cfg->kernel, r.cout, r.cout, true, &r.prep16.k2_bwd)))
+					return fail(st);
+				if (i != 0 && (st = add(r.conv1, cfg->kernel, r.cin, r.cout, true, &r.prep16.k1_bwd))) return fail(st);
+				if (r.res != kNone && ((st = add(r.res, 1, r.cin, r.cout, false, &r.prep16.res_fwd)) || (i != 0 && (st = add(r.res, 1, r.cin, r.cout, true, &r.prep16.res_bwd)))))
+					return fail(st);
+			}
+			auto add_conv = [&](Conv& c) -> bla_status {
+				if (!c.present) return BLA_OK;
+				bla_status s2 = add(c.kern, c.k, c.cin, c.cout, false, &c.prep16_fwd);
+				return s2 ? s2 : add(c.kern, c.k, c.cin, c.cout, true, &c.prep16_bwd);
+			};
+			for (int i = 0; i < 3; i++) if ((st = add_conv(m->down[i])) || (st = add_conv(m->up[i]))) return fail(st);
+			if ((st = add_conv(m->outc))) return fail(st);
+			auto upload = [&](const std::vector<bla_conv_bf16_prep_job>& v, bla_conv_bf16_prep_job** d, int* n) -> bla_status {
+				void* q = nullptr;
+				BLA_HIP(hipMalloc(&q, v.size() * sizeof(bla_conv_bf16_prep_job)));
+				m->owned.push_back(q);
+				BLA_HIP(hipMemcpy(q, v.data(), v.size() * sizeof(bla_conv_bf16_prep_job), hipMemcpyHostToDevice));
+				*d = (bla_conv_bf16_prep_job*)q;
+				*n = (int)v.size();
+				return BLA_OK;
+			};
+			if ((st = upload(jf, &m->prep16_fwd, &m->n_prep16_fwd)) || (st = upload(jb, &m->prep16_bwd, &m->n_prep16_bwd))) return fail(st);
+		}
+	} else if (batch > 1 && prep_on) {
 		// One launch at the head of forward() and one at the head of backward() put every convolution's kernels into the form its product reads (window order,
 		// flipped): 49 five-microsecond launches per pass become 2.  The parameters do not change inside a pass, so the prepared copies are valid for it.
 		std::vector<KernelPrepJob> jf, jb;
@@ -527,6 +618,7 @@ bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* d_x, con
 	const int* D = c.dims; const int* H = m->H; const int* W = m->W;
 	const float* P = m->params;
 	const int B = m->batch;
+	const bool bf16 = m->products == BLA_UNET_PRODUCTS_BF16;
 	hipStream_t s = pick_stream(stream);
 	m->last_x = d_x; m->last_temb = d_time_embedding; m->last_drop = d_drop;
 	m->have_grads = false;
@@ -534,6 +626,9 @@ bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* d_x, con
 		Res& r = m->res[i];
 		bla_resnet_params p = {P + r.conv1, P + r.conv2, P + r.tw, P + r.tb, r.res != kNone ? P + r.res : nullptr};
 		// the dropout decisions: block by block in forward order, inside a block image by image
+		if (bf16)
+			return resnet_forward_bf16(stream, B, in, d_time_embedding, &p, (d_drop ? d_drop : m->zero_drop) + r.drop_off * B, &r.ws, r.result, r.h, r.w, r.cin, r.cout,
+			                           c.kernel, c.time_dim, c.group_size, &r.maps, m->time_jobs ? RESNET_TDENSE_READY : 0, &r.prep16);
 		return resnet_forward_batched(stream, B, in, d_time_embedding, &p, (d_drop ? d_drop : m->zero_drop) + r.drop_off * B, &r.ws, r.result, r.h, r.w, r.cin,
 		                              r.cout, c.kernel, c.time_dim, c.group_size, m->time_jobs ? RESNET_TDENSE_READY : 0, B > 1 ? &r.pads : nullptr);
 	};
@@ -549,9 +644,11 @@ bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* d_x, con
 		return bla_attention_forward_batched_f32(stream, B, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, c.key_dim);
 	};
 	auto conv = [&](Conv& k, const float* in) -> bla_status {
+		if (bf16) return conv2d_forward_as_bf16(stream, in, P + k.kern, k.out, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, 0, k.prep16_fwd);
 		return conv2d_forward_epilogue(stream, in, P + k.kern, k.out, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, nullptr, nullptr, B, 0, nullptr, k.prep_fwd);
 	};
 	if (m->n_prep_fwd) { st = conv_prepare_kernels(stream, m->prep_fwd, m->n_prep_fwd, m->prep_max); if (st) return st; }
+	if (m->n_prep16_fwd) { st = bla_conv_bf16_prepare_kernels_table(stream, m->prep16_fwd, m->n_prep16_fwd, m->prep16_max_fwd); if (st) return st; }
 	auto concat = [&](int stage, const float* a, const float* skip, size_t n) -> bla_status {   // _concat_skip, :1088-1097 (n: floats per image and half)
 		if (n % 4 == 0 && ((uintptr_t)a | (uintptr_t)skip | (uintptr_t)m->cat[stage]) % 16 == 0)
 			hipLaunchKernelGGL(unet_concat4_kernel, dim3(grid_of(n / 2 * B)), dim3(256), 0, s, (const float4*)a, (const float4*)skip, (float4*)m->cat[stage], n / 4, n / 2 * B);
@@ -609,12 +706,16 @@ static bla_status unet_backward(bla_unet* m, void* stream, const float* d_noise,
 	const float* P = m->params; float* G = m->grads;
 	const float* temb = m->last_temb;
 	const int B = m->batch;
+	const bool bf16 = m->products == BLA_UNET_PRODUCTS_BF16;
 	hipStream_t s = pick_stream(stream);
 	// ResNet block i: gradient `g` of its result -> `out` (gradient of its input `x`)
 	auto res = [&](int i, const float* g, const float* x, float* out) -> bla_status {
 		Res& r = m->res[i];
 		bla_resnet_params p = {P + r.conv1, P + r.conv2, P + r.tw, P + r.tb, r.res != kNone ? P + r.res : nullptr};
 		bla_resnet_grads gr = {G + r.conv1, G + r.conv2, G + r.tw, G + r.tb, r.res != kNone ? G + r.res : nullptr};
+		if (bf16)   // (the channel sums go to r.dtb at every batch: bla_unet_embedding_grad_f32 reads them there)
+			return resnet_backward_bf16(stream, B, g, x, temb, &p, &r.ws, &gr, &m->sc, r.dtb, out, r.h, r.w, r.cin, r.cout, c.kernel, c.time_dim, c.group_size, &r.maps, 0,
+			                            m->time_jobs ? RESNET_DEFER_TIME_GRADS : 0, &r.prep16);
 		return resnet_backward_batched(stream, B, g, x, temb, &p, &r.ws, &gr, &m->sc, B > 1 ? r.dtb : m->dtb, out, r.h, r.w, r.cin, r.cout, c.kernel, c.time_dim,
 		                               c.group_size, (B > 1 && m->time_jobs ? RESNET_DEFER_TIME_GRADS : 0) | (m->side ? RESNET_WGRAD_SIDE : 0), B > 1 ? &r.pads : nullptr);
 	};
@@ -624,6 +725,7 @@ static bla_status unet_backward(bla_unet* m, void* stream, const float* d_noise,
 		                                          G + a.wo, out, a.c, a.h * a.w, c.key_dim, 0);
 	};
 	auto conv = [&](Conv& k, const float* g, const float* x, float* out) -> bla_status {
+		if (bf16) return conv2d_backward_gathered_as_bf16(stream, g, x, P + k.kern, G + k.kern, out, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, 0, k.prep16_bwd);
 		if (m->side) {      // weight gradient on the side lane (g and x stay intact until the join below), data gradient here
 			hipStream_t lane;
 			bla_status s2 = side_lane_fork(s, &lane);
@@ -636,6 +738,7 @@ static bla_status unet_backward(bla_unet* m, void* stream, const float* d_noise,
 		return conv2d_backward_batched(stream, g, x, P + k.kern, G + k.kern, out, m->sc.flip, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, k.prep_bwd);
 	};
 	if (m->n_prep_bwd) { st = conv_prepare_kernels(stream, m->prep_bwd, m->n_prep_bwd, m->prep_max); if (st) return st; }
+	if (m->n_prep16_bwd) { st = bla_conv_bf16_prepare_kernels_table(stream, m->prep16_bwd, m->n_prep16_bwd, m->prep16_max_bwd); if (st) return st; }
 	// up-sampling stage i backwards: gradient of (the optional convolution's output | the resized map) -> gradient of the map before resizing;
 	// g, tmp and out are three different buffers
 	auto upsample = [&](int i, const float* g, float* tmp, float* out) -> bla_status {
@@ -703,7 +806,7 @@ static bla_status unet_backward(bla_unet* m, void* stream, const float* d_noise,
 	TRY(bla_add_f32(stream, a, m->gskip[3], n0 * B));
 	TRY(res(1, a, m->res[0].result, F(b)));
 	TRY(res(0, b, m->last_x, nullptr));   // nothing consumes the gradient of the image: the first block forms its weight gradients only
-	if (B > 1 && m->time_jobs) {   // the 18 blocks' time-weight / time-bias gradients from the channel sums each block left behind (:1191-1199)
+	if ((B > 1 || bf16) && m->time_jobs) {   // the 18 blocks' time-weight / time-bias gradients from the channel sums each block left behind (:1191-1199)
 		hipLaunchKernelGGL(time_grads_all_kernel, dim3(18, (unsigned)((c.time_dim + 7) / 8)), dim3(256), 0, s, m->time_jobs, temb, B, c.time_dim);
 		BLA_HIP(hipGetLastError());
 	}

@@ -131,6 +131,8 @@ SIGNATURES = {
     "bla_layer_net_biases": (_VP, [_VP, _I]), "bla_layer_net_nodes": (_VP, [_VP, _I]), "bla_layer_net_raw_nodes": (_VP, [_VP, _I]),
     "bla_layer_net_forward_f32": (_I, [_VP, _VP, _VP]), "bla_layer_net_backward_f32": (_I, [_VP, _VP, _VP, _F]),
     "bla_unet_create_batched": (_I, [C.POINTER(_VP), _VP, _I]), "bla_unet_batch": (_I, [_VP]),
+    "bla_unet_create_mixed": (_I, [C.POINTER(_VP), _VP, _I, _I]), "bla_unet_products": (_I, [_VP]),
+    "bla_conv_bf16_prepare_kernels_table": (_I, [_VP, _VP, _I, _SZ]),
     "bla_unet_create": (_I, [C.POINTER(_VP), _VP]), "bla_unet_destroy": (_I, [_VP]), "bla_unet_param_count": (_SZ, [_VP]),
     "bla_unet_params": (_VP, [_VP]), "bla_unet_grads": (_VP, [_VP]), "bla_unet_output": (_VP, [_VP]), "bla_unet_tensor_count": (_I, [_VP]),
     "bla_unet_tensor_info": (_I, [_VP, _I, C.POINTER(_SZ), C.POINTER(_SZ), C.c_char_p, _I]), "bla_unet_dropout_count": (_SZ, [_VP]),
@@ -444,6 +446,42 @@ def conv_bf16_prepare_kernels(kern, dst, f_n, c_n, k, data_gradient=False, strea
     """fp32 [f_n][c_n][k][k] -> the tap-major bf16 matrix: forward [f_n][k*k*Cp], or (data_gradient) flipped and transposed [c_n][k*k*Fp]."""
     check(lib().bla_conv_bf16_prepare_kernels(stream, _ptr(kern), _ptr(dst), f_n, c_n, k, int(data_gradient)))
     return dst
+
+
+class ConvBf16PrepJob(C.Structure):
+    """struct bla_conv_bf16_prep_job (include/bla.h): one kernel tensor of a bla_conv_bf16_prepare_kernels_table launch."""
+    _fields_ = [("kern", C.c_void_p), ("dst", C.c_void_p), ("f_n", C.c_int), ("c_n", C.c_int), ("k", C.c_int), ("data_gradient", C.c_int)]
+
+
+def conv_bf16_prep_chunks(f_n, c_n, k, data_gradient=False):
+    """8-element chunks of one job's destination matrix (the largest of a table is the launch's max_chunks)."""
+    rows, inner = (c_n, f_n) if data_gradient else (f_n, c_n)
+    return rows * k * k * ((inner + 7) // 8)
+
+
+def conv_bf16_prepare_kernels_table(jobs, stream=None):
+    """One launch for many conv_bf16_prepare_kernels calls: jobs = [(kern, dst, f_n, c_n, k, data_gradient), ...] on device arrays (or addresses).  The table is
+    uploaded here; the fields are the caller's responsibility (include/bla.h).  Returns the device table (keep it until the stream has passed the launch)."""
+    arr = (ConvBf16PrepJob * max(len(jobs), 1))(*[ConvBf16PrepJob(_ptr(kn), _ptr(d), f, c, k, int(dg)) for kn, d, f, c, k, dg in jobs])
+    table = DeviceArray((max(len(jobs), 1) * C.sizeof(ConvBf16PrepJob),), np.uint8)
+    check(lib().bla_memcpy_h2d(table.ptr, C.addressof(arr), len(jobs) * C.sizeof(ConvBf16PrepJob), stream))
+    sync(stream)
+    check(lib().bla_conv_bf16_prepare_kernels_table(stream, table.ptr, len(jobs), max([conv_bf16_prep_chunks(f, c, k, dg) for _, _, f, c, k, dg in jobs], default=0)))
+    return table
+
+
+UNET_PRODUCTS_F32, UNET_PRODUCTS_BF16 = 0, 1
+
+
+def unet_create_mixed(cfg, batch=1, products=UNET_PRODUCTS_F32):
+    """bla_unet_create_mixed: cfg is a ctypes struct bla_unet_config; returns the model handle (a c_void_p) for the bla_unet_* entries of lib()."""
+    h = C.c_void_p()
+    check(lib().bla_unet_create_mixed(C.byref(h), C.byref(cfg), batch, products))
+    return h
+
+
+def unet_products(model):
+    return lib().bla_unet_products(model)
 
 
 def conv2d_gathered_bf16(a, rows, p, batch, hp, wp, cp, k, stride, ho, wo, out, ep_bias=None, ep_bias_stride=0, stream=None):

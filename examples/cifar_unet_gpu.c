@@ -405,11 +405,20 @@ typedef struct Device {
 	unsigned char* drop;
 	float* bucket;     /* host image of the parameter bucket */
 } Device;
+/* BLA_UNET_PRODUCTS=f32|bf16 (default f32): the precision of the model's convolution products (bla_unet_create_mixed).  The parameter files are fp32 in
+ * both modes: weights trained in one load in the other. */
+static int g_products = BLA_UNET_PRODUCTS_F32;
+static void products_from_env(void) {
+	const char* v = env_or("BLA_UNET_PRODUCTS", "f32");
+	if (strcmp(v, "f32") == 0) g_products = BLA_UNET_PRODUCTS_F32;
+	else if (strcmp(v, "bf16") == 0) g_products = BLA_UNET_PRODUCTS_BF16;
+	else { fprintf(stderr, "BLA_UNET_PRODUCTS=%s: expected f32 or bf16\n", v); exit(1); }
+}
 static Device device_open(int batch, size_t drop_per_image) {
 	Device dv; memset(&dv, 0, sizeof dv); dv.batch = batch;
 	CHECK(bla_init(atoi(env_or("BLA_DEVICE", "0"))));
 	bla_unet_config cfg = {IMAGE_SIDE, IMAGE_SIDE, IMAGE_CHANNELS, {kDims[0], kDims[1], kDims[2], kDims[3]}, TIME_EMBED_DIM, KERNEL_SIZE, GROUP_SIZE, KEY_DIM};
-	CHECK(bla_unet_create_batched(&dv.net, &cfg, batch));
+	CHECK(bla_unet_create_mixed(&dv.net, &cfg, batch, g_products));
 	if (bla_unet_dropout_count(dv.net) != drop_per_image * batch) { fprintf(stderr, "dropout layout: device %zu, host %zu\n", bla_unet_dropout_count(dv.net), drop_per_image * batch); exit(1); }
 	CHECK(bla_malloc((void**)&dv.x, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
 	CHECK(bla_malloc((void**)&dv.noise, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
@@ -1284,6 +1293,7 @@ int main(int argc, char** argv) {
 		printf("Please supply an argument, options:\n\trun [<num samples> (default 1)]\n\ttrain <num epochs>\n\tinit\n");
 		exit(1);
 	}
+	products_from_env();   /* before any sub-command opens the device: a bad value stops every one of them */
 	plan_model();
 	if (strncmp(argv[1], "run", 3) == 0) {
 		run(argc < 3 ? 1 : atoi(argv[2]));

@@ -375,6 +375,16 @@ BLA_API bla_status bla_conv_bf16_layout(int h, int w, int k, int stride, int dat
 BLA_API bla_status bla_conv_bf16_pad(void* stream, const float* d_src, uint16_t* d_dst, int batch, int c, int h, int w, int hp, int wp, int top, int left, int dilate);
 /* kern fp32 [f_n][c_n][k][k] -> the forward matrix [f_n][k k Cp] (data_gradient = 0) or the data gradient's [c_n][k k Fp] (1), every element written */
 BLA_API bla_status bla_conv_bf16_prepare_kernels(void* stream, const float* d_kern, uint16_t* d_dst, int f_n, int c_n, int k, int data_gradient);
+/* The same for MANY kernel tensors in ONE launch: job i is bla_conv_bf16_prepare_kernels(kern, dst, f_n, c_n, k, data_gradient), and every
+ * destination gets exactly the bits that call writes (one chunk body behind both kernels), every element in 16-byte stores.  d_jobs is a DEVICE array of
+ * n_jobs jobs; max_chunks = the largest job's count of 8-element destination chunks, rows k k round8(inner) / 8 with (rows, inner) = (f_n, c_n) forward and
+ * (c_n, f_n) for the data gradient: it sizes the grid (ceil(max_chunks / 256), n_jobs), and the threads past a job's own extent do nothing.
+ * The jobs live in device memory, so the library cannot look at them: every field is the CALLER'S responsibility -- kern holds f_n c_n k k floats, dst is
+ * 16-byte aligned and holds the whole matrix, extents > 0, no job needs more than max_chunks chunks (a larger one is left partly unwritten), destinations
+ * do not overlap.  n_jobs == 0 does nothing.  BLA_ERR_INVALID, before the device is asked for: n_jobs < 0, a NULL table or max_chunks == 0 with n_jobs > 0,
+ * more than 65535 jobs. */
+typedef struct bla_conv_bf16_prep_job { const float* kern; uint16_t* dst; int f_n, c_n, k, data_gradient; } bla_conv_bf16_prep_job;
+BLA_API bla_status bla_conv_bf16_prepare_kernels_table(void* stream, const bla_conv_bf16_prep_job* d_jobs, int n_jobs, size_t max_chunks);
 /*   out[b][r][i][j] = sum_{p,q,c} A[r][(p k + q) cp + c] * P[b][i stride + p][j stride + q][c]  (+ ep_bias[b * ep_bias_stride + r], in fp32, if ep_bias)
  * A [rows][k k cp], P [batch][hp][wp][cp], out fp32 [batch][rows][ho][wo] (the project's layout).  One product for the forward pass (A = the forward matrix,
  * P = the padded input) and for the data gradient (A = the flipped matrix, P = the dilated padded del_y, stride 1, ho x wo = the input's h x w).
@@ -672,6 +682,19 @@ BLA_API bla_status bla_unet_create(bla_unet** out, const bla_unet_config* cfg);
  * time step), the gradients are summed over the images (what `batch` passes of the reference's one-image loop accumulate).  d_drop: the blocks
  * in forward order, inside a block image by image.  bla_unet_create = batch 1. */
 BLA_API bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, int batch);
+/* The same network with its convolutions multiplied in bf16.  products = BLA_UNET_PRODUCTS_F32: exactly bla_unet_create_batched (which, like
+ * bla_unet_create, is this call).  BLA_UNET_PRODUCTS_BF16, any batch >= 1: the 18 ResNet blocks run bla_resnet_{forward,backward}_batched_bf16's arithmetic
+ * (each block owns its maps p1, p2, q1, laid out as stated there, zero-filled once here and freed with the model), the stride-2, up-sampling and output
+ * convolutions run bla_conv2d_forward_batched_f32_as_bf16 / bla_conv2d_backward_gathered_f32_as_bf16 (splits 0); attention, the output norm, resizing,
+ * concatenation, the skip additions and the loss seed stay fp32, on one stream.  Parameters, gradients, the tensor table, the dropout layout and the output
+ * are fp32 with the same order and layout in both modes, so bla_unet_forward_f32, bla_unet_backward_f32, bla_unet_backward_from_f32,
+ * bla_unet_embedding_grad_f32, every sampler, bla_unet_evaluate_f32 and the optimiser entries take either model, and parameters trained in one mode load in
+ * the other.  All bf16 kernel matrices of a pass are prepared by ONE bla_conv_bf16_prepare_kernels_table launch at its head, into matrices the model owns
+ * (not the context workspace); BLA_UNET_BF16_PREP=0 in the environment, read at every create call, makes a model created afterwards prepare each matrix in
+ * front of its product instead (the same bits).  Any other `products` value: BLA_ERR_INVALID before the device is asked for, *out untouched. */
+enum { BLA_UNET_PRODUCTS_F32 = 0, BLA_UNET_PRODUCTS_BF16 = 1 };
+BLA_API bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int batch, int products);
+BLA_API int bla_unet_products(const bla_unet* m);               /* the mode the model was created with */
 BLA_API int bla_unet_batch(const bla_unet* m);
 BLA_API bla_status bla_unet_destroy(bla_unet* m);
 BLA_API size_t bla_unet_param_count(const bla_unet* m);         /* floats in each bucket (every tensor starts 16-byte aligned) */
