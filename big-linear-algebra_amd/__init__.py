@@ -12,7 +12,9 @@ from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilo
                      conv2d_weight_gradient_gathered_bf16, conv2d_backward_gathered_as_bf16, conv_bf16_map,
                      conv2d_gathered_bf16_chained, group_norm_relu_bf16_map, group_norm_ddx_bf16_map, resnet_bf16_maps,
                      resnet_forward_batched_bf16, resnet_backward_batched_bf16, conv_bf16_prepare_kernels_table,
-                     conv_bf16_prep_chunks, unet_create_mixed, unet_products, UNET_PRODUCTS_F32, UNET_PRODUCTS_BF16)
+                     conv_bf16_prep_chunks, unet_create_mixed, unet_products, UNET_PRODUCTS_F32, UNET_PRODUCTS_BF16,
+                     unet_set_attention, unet_attention, UNET_ATTENTION_F32, UNET_ATTENTION_BF16, attention_bf16_applies, attention_ws,
+                     attention_forward_batched_bf16, attention_backward_batched_bf16)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
@@ -23,4 +25,6 @@ __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Ep
            "conv2d_backward_as_bf16", "gemm_bf16_splitk_plan", "gemm_bf16_splitk", "conv2d_weight_gradient_as_bf16",
            "conv2d_weight_gradient_gathered_bf16", "conv2d_backward_gathered_as_bf16", "conv_bf16_map", "conv2d_gathered_bf16_chained",
            "group_norm_relu_bf16_map", "group_norm_ddx_bf16_map", "resnet_bf16_maps", "resnet_forward_batched_bf16", "resnet_backward_batched_bf16",
-           "conv_bf16_prepare_kernels_table", "conv_bf16_prep_chunks", "unet_create_mixed", "unet_products", "UNET_PRODUCTS_F32", "UNET_PRODUCTS_BF16"]
+           "conv_bf16_prepare_kernels_table", "conv_bf16_prep_chunks", "unet_create_mixed", "unet_products", "UNET_PRODUCTS_F32", "UNET_PRODUCTS_BF16",
+           "unet_set_attention", "unet_attention", "UNET_ATTENTION_F32", "UNET_ATTENTION_BF16", "attention_bf16_applies", "attention_ws",
+           "attention_forward_batched_bf16", "attention_backward_batched_bf16"]

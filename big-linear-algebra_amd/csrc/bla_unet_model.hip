@@ -63,6 +63,7 @@ constexpr size_t kNone = (size_t)-1;
 struct bla_unet {
 	bla_unet_config cfg;
 	int batch = 1;
+	int attention = BLA_UNET_ATTENTION_F32;   // BLA_UNET_ATTENTION_BF16: the attention blocks that qualify on bla_attention_{forward,backward}_batched_bf16
 	int products = BLA_UNET_PRODUCTS_F32;   // BLA_UNET_PRODUCTS_BF16: the blocks and the stand-alone convolutions on the bf16 stack, one stream
 	int H[4], W[4];
 	std::vector<Tensor> tensors;
@@ -360,6 +361,15 @@ bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config* cfg, i
 
 int bla_unet_products(const bla_unet* m) { return m ? m->products : BLA_UNET_PRODUCTS_F32; }
 
+int bla_unet_attention(const bla_unet* m) { return m ? m->attention : BLA_UNET_ATTENTION_F32; }
+
+bla_status bla_unet_set_attention(bla_unet* m, int mode) {
+	BLA_REQUIRE(mode == BLA_UNET_ATTENTION_F32 || mode == BLA_UNET_ATTENTION_BF16, BLA_ERR_INVALID, "bla_unet_set_attention: mode %d (BLA_UNET_ATTENTION_F32 or _BF16)", mode);
+	BLA_REQUIRE(m, BLA_ERR_INVALID, "null argument");
+	m->attention = mode;
+	return BLA_OK;
+}
+
 bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int batch, int products) {
 	BLA_REQUIRE(products == BLA_UNET_PRODUCTS_F32 || products == BLA_UNET_PRODUCTS_BF16, BLA_ERR_INVALID, "bla_unet_create_mixed: products %d (BLA_UNET_PRODUCTS_F32 or _BF16)", products);
 	const bool bf16 = products == BLA_UNET_PRODUCTS_BF16;
@@ -461,7 +471,7 @@ bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int
 	}
 	if ((st = dalloc(m, &m->t1, max_act)) || (st = dalloc(m, &m->t2, max_act)) || (st = dalloc(m, &m->t3, max_act)) || (st = dalloc(m, &m->sc.g_out_a, max_cout_hw)) ||
 	    (st = dalloc(m, &m->sc.g_out_b, max_cout_hw)) || (st = dalloc(m, &m->sc.g_in, max_cin_hw)) || (st = dalloc(m, &m->sc.flip, max_flip)) ||
-	    (st = alloc_att_ws(m, m->agrad, max_s, cfg->key_dim)) || (st = dalloc(m, &m->dtb, B * max_cout)) || (st = dalloc(m, &m->partials, B * max_cd)))
+	    (st = alloc_att_ws(m, m->agrad, max_s, cfg->key_dim)) || (st = dalloc(m, &m->dtb, B * max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
 		return fail(st);
 	void* z = nullptr;
 	const size_t zero_bytes = m->drop_count ? B * m->drop_count : 1;
@@ -641,6 +651,8 @@ bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* d_x, con
 	}
 	auto att = [&](int i, const float* in) -> bla_status {
 		Att& a = m->att[i];
+		if (m->attention == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(a.c, a.h * a.w, c.key_dim))
+			return bla_attention_forward_batched_bf16(stream, B, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, c.key_dim);
 		return bla_attention_forward_batched_f32(stream, B, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, c.key_dim);
 	};
 	auto conv = [&](Conv& k, const float* in) -> bla_status {
@@ -721,6 +733,9 @@ static bla_status unet_backward(bla_unet* m, void* stream, const float* d_noise,
 	};
 	auto att = [&](int i, const float* g, const float* x, float* out) -> bla_status {
 		Att& a = m->att[i];
+		if (m->attention == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(a.c, a.h * a.w, c.key_dim))
+			return bla_attention_backward_batched_bf16(stream, B, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk,
+			                                           G + a.wv, G + a.wo, out, a.c, a.h * a.w, c.key_dim);
 		return bla_attention_backward_batched_f32(stream, B, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv,
 		                                          G + a.wo, out, a.c, a.h * a.w, c.key_dim, 0);
 	};

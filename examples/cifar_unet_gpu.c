@@ -414,11 +414,20 @@ static void products_from_env(void) {
 	else if (strcmp(v, "bf16") == 0) g_products = BLA_UNET_PRODUCTS_BF16;
 	else { fprintf(stderr, "BLA_UNET_PRODUCTS=%s: expected f32 or bf16\n", v); exit(1); }
 }
+/* BLA_UNET_ATTENTION=f32|bf16 (default f32): where the model's attention blocks multiply (bla_unet_set_attention); orthogonal to the above. */
+static int g_attention = BLA_UNET_ATTENTION_F32;
+static void attention_from_env(void) {
+	const char* v = env_or("BLA_UNET_ATTENTION", "f32");
+	if (strcmp(v, "f32") == 0) g_attention = BLA_UNET_ATTENTION_F32;
+	else if (strcmp(v, "bf16") == 0) g_attention = BLA_UNET_ATTENTION_BF16;
+	else { fprintf(stderr, "BLA_UNET_ATTENTION=%s: expected f32 or bf16\n", v); exit(1); }
+}
 static Device device_open(int batch, size_t drop_per_image) {
 	Device dv; memset(&dv, 0, sizeof dv); dv.batch = batch;
 	CHECK(bla_init(atoi(env_or("BLA_DEVICE", "0"))));
 	bla_unet_config cfg = {IMAGE_SIDE, IMAGE_SIDE, IMAGE_CHANNELS, {kDims[0], kDims[1], kDims[2], kDims[3]}, TIME_EMBED_DIM, KERNEL_SIZE, GROUP_SIZE, KEY_DIM};
 	CHECK(bla_unet_create_mixed(&dv.net, &cfg, batch, g_products));
+	CHECK(bla_unet_set_attention(dv.net, g_attention));
 	if (bla_unet_dropout_count(dv.net) != drop_per_image * batch) { fprintf(stderr, "dropout layout: device %zu, host %zu\n", bla_unet_dropout_count(dv.net), drop_per_image * batch); exit(1); }
 	CHECK(bla_malloc((void**)&dv.x, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
 	CHECK(bla_malloc((void**)&dv.noise, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
@@ -1294,6 +1303,7 @@ int main(int argc, char** argv) {
 		exit(1);
 	}
 	products_from_env();   /* before any sub-command opens the device: a bad value stops every one of them */
+	attention_from_env();
 	plan_model();
 	if (strncmp(argv[1], "run", 3) == 0) {
 		run(argc < 3 ? 1 : atoi(argv[2]));

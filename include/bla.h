@@ -606,6 +606,30 @@ BLA_API bla_status bla_attention_backward_batched_f32(void* stream, int batch, c
                                                       const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
                                                       float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w, float* d_del_x,
                                                       int c, int s, int d, int jacobian_from_raw);
+/* The batched attention block with bf16 products inside: the fp32 entries' tensors, layouts and bla_attention_ws.  One rule: BOTH OPERANDS
+ * OF EVERY MATRIX PRODUCT ARE ROUNDED TO bf16 WITH bla_f32_to_bf16's ROUNDING (r) IMMEDIATELY BEFORE THE PRODUCT; accumulation, softmax, its derivative,
+ * bias, scaling and every stored tensor are fp32.  Per image, Z = X^T (S x C), inv = (float)(1 / sqrt((double)d)):
+ *   forward:  Q = r(Z) r(Wq), K = r(Z) r(Wk), V = r(Z) r(Wv);  T = inv (r(Q) r(K)^T);  P = softmax of T's rows, the row maximum subtracted;
+ *             A = r(P) r(V);  out [C][S] = (r(A) r(W) + bias)^T.
+ *             Written: ws->q, k, v, weights (= P), attention (= A), all fp32, and d_out; ws->scores_raw is not written and may be NULL.
+ *   backward (the intended composition only, no jacobian_from_raw):
+ *             del_W = sum_b r(A)^T r(del_Y');  del_P = r(del_Y') r(W)^T;  del_S = r(del_P) r(V)^T;  del_V = r(P)^T r(del_P);
+ *             del_I = inv P o (del_S - <P, del_S> per row);  del_Q = r(del_I) r(K);  del_K = r(del_I)^T r(Q);
+ *             del_Wq/k/v = sum_b r(Z)^T r(del_Q/K/V);  del_X = r(Wq) r(del_Q)^T + r(Wk) r(del_K)^T + r(Wv) r(del_V)^T.
+ *             grad->q, k, v receive del_Q, del_K, del_V; the other grad fields may be NULL and are not written.  d_partials: caller-owned scratch of
+ *             [batch][4 c d] floats.  Of the S x S tensors only `weights` is in memory: T, del_S and del_I never leave the chip.
+ * Sums over the batch and across waves have a fixed order: no atomics, the same bits on every run, and image b of a batch equals a batch-1 run of it.
+ * bla_attention_bf16_applies (host only, no device needed) is 1 exactly when s % 32 == 0, 32 <= s <= 256, d % 8 == 0, 8 <= d <= 64 and c % 8 == 0 (a d
+ * that is no multiple of 16 contracts over zero padding); outside that set both entries return BLA_ERR_INVALID before any launch, outputs untouched.  A
+ * wave holds a query's whole row of scores in registers, which is what bounds s: longer sequences need an online softmax and are out of scope.
+ * Any batch in 1 .. 65535; no workspace growth, so the entries can be captured without a warm-up rule. */
+BLA_API int bla_attention_bf16_applies(int c, int s, int d);
+BLA_API bla_status bla_attention_forward_batched_bf16(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv,
+                                                      const float* d_w, const float* d_bias, const bla_attention_ws* ws, float* d_out, int c, int s, int d);
+BLA_API bla_status bla_attention_backward_batched_bf16(void* stream, int batch, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk,
+                                                       const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
+                                                       float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w, float* d_del_x,
+                                                       int c, int s, int d);
 BLA_API bla_status bla_resnet_forward_batched_f32(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p,
                                                   const unsigned char* d_drop, const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k,
                                                   int tdim, int group_size);
@@ -695,6 +719,15 @@ BLA_API bla_status bla_unet_create_batched(bla_unet** out, const bla_unet_config
 enum { BLA_UNET_PRODUCTS_F32 = 0, BLA_UNET_PRODUCTS_BF16 = 1 };
 BLA_API bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int batch, int products);
 BLA_API int bla_unet_products(const bla_unet* m);               /* the mode the model was created with */
+/* Where the model's self-attention blocks multiply; orthogonal to `products`.  BLA_UNET_ATTENTION_F32 (the default after every create entry):
+ * bla_attention_{forward,backward}_batched_f32, as always -- a model never switched is bit-equal to before in both `products` modes.
+ * BLA_UNET_ATTENTION_BF16: an attention block whose shape bla_attention_bf16_applies accepts runs bla_attention_{forward,backward}_batched_bf16, bit for
+ * bit those entries; a block it refuses (at the reference's constants the 4 x 4 mid block, S = 16) keeps the fp32 entries.  Both paths share the block's
+ * bla_attention_ws, so the setter is legal between passes (not between a forward pass and its backward pass).  Any other mode: BLA_ERR_INVALID, the
+ * model unchanged. */
+enum { BLA_UNET_ATTENTION_F32 = 0, BLA_UNET_ATTENTION_BF16 = 1 };
+BLA_API bla_status bla_unet_set_attention(bla_unet* m, int mode);
+BLA_API int bla_unet_attention(const bla_unet* m);
 BLA_API int bla_unet_batch(const bla_unet* m);
 BLA_API bla_status bla_unet_destroy(bla_unet* m);
 BLA_API size_t bla_unet_param_count(const bla_unet* m);         /* floats in each bucket (every tensor starts 16-byte aligned) */
