@@ -14,7 +14,8 @@ from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilo
                      resnet_forward_batched_bf16, resnet_backward_batched_bf16, conv_bf16_prepare_kernels_table,
                      conv_bf16_prep_chunks, unet_create_mixed, unet_products, UNET_PRODUCTS_F32, UNET_PRODUCTS_BF16,
                      unet_set_attention, unet_attention, UNET_ATTENTION_F32, UNET_ATTENTION_BF16, attention_bf16_applies, attention_ws,
-                     attention_forward_batched_bf16, attention_backward_batched_bf16)
+                     attention_forward_batched_bf16, attention_backward_batched_bf16, to_mxfp8, from_mxfp8, f32_to_mxfp8, mxfp8_to_f32,
+                     gemm_mxfp8, gemm_f32_as_mxfp8)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
@@ -27,4 +28,5 @@ __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Ep
            "group_norm_relu_bf16_map", "group_norm_ddx_bf16_map", "resnet_bf16_maps", "resnet_forward_batched_bf16", "resnet_backward_batched_bf16",
            "conv_bf16_prepare_kernels_table", "conv_bf16_prep_chunks", "unet_create_mixed", "unet_products", "UNET_PRODUCTS_F32", "UNET_PRODUCTS_BF16",
            "unet_set_attention", "unet_attention", "UNET_ATTENTION_F32", "UNET_ATTENTION_BF16", "attention_bf16_applies", "attention_ws",
-           "attention_forward_batched_bf16", "attention_backward_batched_bf16"]
+           "attention_forward_batched_bf16", "attention_backward_batched_bf16", "to_mxfp8", "from_mxfp8", "f32_to_mxfp8", "mxfp8_to_f32", "gemm_mxfp8",
+           "gemm_f32_as_mxfp8"]

@@ -80,6 +80,9 @@ SIGNATURES = {
     "bla_gemm_f32_as_bf16": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, C.POINTER(Epilogue)]),
     "bla_gemm_bf16_splitk_plan": (_I, [_I] * 5 + [C.POINTER(_I), C.POINTER(_I), C.POINTER(_SZ)]),
     "bla_gemm_bf16_splitk": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, C.POINTER(Epilogue), _I]),
+    "bla_f32_to_mxfp8": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _I]), "bla_mxfp8_to_f32": (_I, [_VP, _VP, _I, _VP, _I, _VP, _I, _I, _I]),
+    "bla_gemm_mxfp8": (_I, [_VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, C.POINTER(Epilogue)]),
+    "bla_gemm_f32_as_mxfp8": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, C.POINTER(Epilogue)]),
     "bla_conv2d_weight_gradient_batched_f32_as_bf16": (_I, [_VP] * 4 + [_I] * 8),
     "bla_conv2d_weight_gradient_gathered_bf16": (_I, [_VP, _VP] + [_I] * 6 + [_VP] + [_I] * 10 + [_VP, _I]),
     "bla_conv2d_backward_gathered_f32_as_bf16": (_I, [_VP] * 6 + [_I] * 8),
@@ -428,6 +431,120 @@ def gemm_bf16_splitk(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, b
     c_type = C_BF16 if c.dtype == np.uint16 else C_F32
     check(lib().bla_gemm_bf16_splitk(stream, int(transa), int(transb), m, n, k, _ptr(a), lda or a.ld, _ptr(b), ldb or b.ld, _ptr(c), ldc or c.ld,
                                      c_type, C.byref(ep), splits))
+    return c
+
+
+# ---- MXFP8 (include/bla.h: e4m3 elements, one E8M0 scale byte per 32 elements of the contraction) -------------------------------------------------------
+def _mx_round_e4m3(a):
+    """fp32 magnitude bits (|x| < 512) -> the e4m3 magnitude byte: round to nearest even in integer arithmetic, saturating at 448 (0x7E)."""
+    a = a.astype(np.int64)
+    e = a >> 23
+    normal = np.minimum(((a + 0x7FFFF + ((a >> 20) & 1)) >> 20) - (120 << 3), 0x7E)
+    sh = np.clip(141 - e, 21, 40)                      # a multiple of 2^-9: mantissa >> sh; sh >= 25 is below half of 2^-9
+    mant = (a & 0x7FFFFF) | 0x800000
+    q, rem, half = mant >> sh, mant & ((np.int64(1) << sh) - 1), np.int64(1) << (sh - 1)
+    sub = np.where(sh >= 25, 0, q + ((rem > half) | ((rem == half) & ((q & 1) == 1))))
+    return np.where(e >= 121, normal, sub).astype(np.uint8)
+
+
+def e4m3_round(x):
+    """fp32 values with |x| < 512 -> e4m3fn bytes: round to nearest even, saturating at +-448, the sign of zero kept (the element rounding of to_mxfp8)."""
+    xu = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    return _mx_round_e4m3(xu & np.uint32(0x7FFFFFFF)) | ((xu >> np.uint32(24)) & np.uint32(0x80)).astype(np.uint8)
+
+
+def to_mxfp8(a, trans=False):
+    """fp32 [rows][cols] (trans: [cols][rows]) -> (elements u8 [rows][cols rounded up to 32], scales u8 [rows][ceil(cols / 32)]) on the host: what
+    bla_f32_to_mxfp8 computes, bit for bit."""
+    a = np.asarray(a, np.float32)
+    if a.ndim == 1:
+        a = a[None, :]
+    if trans:
+        a = a.T
+    rows, cols = a.shape
+    nb = -(-cols // 32)
+    v = np.zeros((rows, nb * 32), np.float32)
+    v[:, :cols] = a
+    v = v.reshape(rows, nb, 32)
+    u = v.view(np.uint32)
+    amax = (u & np.uint32(0x7FFFFFFF)).max(axis=2).astype(np.int64)
+    bad = amax >= 0x7F800000
+    sbyte = np.where(amax == 0, 127, np.maximum((amax >> 23) - 8, 0))
+    mult = ((254 - np.where(bad, 127, sbyte)) << 23).astype(np.uint32).view(np.float32)
+    with np.errstate(all="ignore"):
+        x = (v * mult[:, :, None]).astype(np.float32)
+    el = np.where(bad[:, :, None], np.uint8(0x7F), e4m3_round(x)).astype(np.uint8)
+    return el.reshape(rows, nb * 32), np.where(bad, 255, sbyte).astype(np.uint8)
+
+
+def e4m3_decode(b):
+    """e4m3fn bytes -> fp32 (NaN 0x7FC00000 for 0x7F / 0xFF)."""
+    b = np.asarray(b, np.uint8).astype(np.uint32)
+    e, m = (b >> np.uint32(3)) & np.uint32(15), b & np.uint32(7)
+    mag = np.where(e > 0, (((e + np.uint32(120)) << np.uint32(23)) | (m << np.uint32(20))).view(np.float32), m.astype(np.float32) * np.float32(2.0 ** -9))
+    out = (mag.astype(np.float32).view(np.uint32) | ((b & np.uint32(0x80)) << np.uint32(24)))
+    return np.where((b & np.uint32(0x7F)) == 0x7F, np.uint32(0x7FC00000), out).astype(np.uint32).view(np.float32)
+
+
+def e8m0_decode(s):
+    """E8M0 bytes -> fp32: 2^(s - 127), the subnormal 2^-127 for s = 0, NaN for 0xFF."""
+    s = np.asarray(s, np.uint8).astype(np.uint32)
+    bits = np.where(s == 0, np.uint32(0x00400000), s << np.uint32(23))
+    return np.where(s == 255, np.uint32(0x7FC00000), bits).astype(np.uint32).view(np.float32)
+
+
+def from_mxfp8(elems, scales):
+    """(elements [rows][cols], scales [rows][>= ceil(cols / 32)]) -> fp32 [rows][cols]: decode(elem) 2^(s - 127) in fp32, what bla_mxfp8_to_f32 computes."""
+    elems, scales = np.asarray(elems, np.uint8), np.asarray(scales, np.uint8)
+    rows, cols = elems.shape
+    sc = np.repeat(scales[:, :-(-cols // 32)], 32, axis=1)[:, :cols]
+    with np.errstate(all="ignore"):
+        out = (e4m3_decode(elems) * e8m0_decode(sc)).astype(np.float32)
+    nan = ((elems & 0x7F) == 0x7F) | (sc == 255)
+    return np.where(nan, np.uint32(0x7FC00000), out.view(np.uint32)).astype(np.uint32).view(np.float32)
+
+
+def f32_to_mxfp8(src, elems, scales, rows, cols, trans=False, ld_src=None, ld=None, ld_s=None, stream=None):
+    """bla_f32_to_mxfp8 on device arrays (or addresses)."""
+    check(lib().bla_f32_to_mxfp8(stream, _ptr(src), ld_src or src.ld, int(trans), rows, cols, _ptr(elems), ld or elems.ld, _ptr(scales), ld_s or scales.ld))
+    return elems, scales
+
+
+def mxfp8_to_f32(elems, scales, dst, rows, cols, ld=None, ld_s=None, ld_dst=None, stream=None):
+    """bla_mxfp8_to_f32 on device arrays (or addresses)."""
+    check(lib().bla_mxfp8_to_f32(stream, _ptr(elems), ld or elems.ld, _ptr(scales), ld_s or scales.ld, _ptr(dst), ld_dst or dst.ld, rows, cols))
+    return dst
+
+
+def gemm_mxfp8(a, sa, b, sb, c, alpha=1.0, beta=0.0, bias_row=None, bias_col=None, act=ACT_NONE, stream=None, m=None, n=None, k=None,
+               lda=None, ldsa=None, ldb=None, ldsb=None, ldc=None, c_type=None, epilogue=None):
+    """C = epilogue(alpha * A B^T) with MXFP8 operands (np.uint8 device arrays: elements [m][k] / [n][k], scales [m][k / 32] / [n][k / 32]) and fp32
+    accumulation; C is fp32 or bf16 by c's dtype (or c_type).  `epilogue` replaces the Epilogue built from the keyword fields."""
+    if m is None:
+        m = a.shape[0]
+    if k is None:
+        k = a.shape[1]
+    if n is None:
+        n = b.shape[0]
+    ep = epilogue if epilogue is not None else Epilogue(alpha=alpha, beta=beta, bias_row=_ptr(bias_row), bias_col=_ptr(bias_col), act=act)
+    if c_type is None:
+        c_type = C_BF16 if c.dtype == np.uint16 else C_F32
+    check(lib().bla_gemm_mxfp8(stream, m, n, k, _ptr(a), lda or a.ld, _ptr(sa), ldsa or sa.ld, _ptr(b), ldb or b.ld, _ptr(sb), ldsb or sb.ld,
+                               _ptr(c), ldc or c.ld, c_type, C.byref(ep)))
+    return c
+
+
+def gemm_f32_as_mxfp8(a, b, c, transa=False, transb=False, alpha=1.0, beta=0.0, bias_row=None, bias_col=None, act=ACT_NONE, stream=None,
+                      m=None, n=None, k=None, lda=None, ldb=None, ldc=None, epilogue=None):
+    """bla_gemm_f32's arguments, fp32 in memory, multiplied in MXFP8: both operands quantised into the workspace, then gemm_mxfp8."""
+    if m is None:
+        m = a.shape[1] if transa else a.shape[0]
+    if k is None:
+        k = a.shape[0] if transa else a.shape[1]
+    if n is None:
+        n = b.shape[0] if transb else b.shape[1]
+    ep = epilogue if epilogue is not None else Epilogue(alpha=alpha, beta=beta, bias_row=_ptr(bias_row), bias_col=_ptr(bias_col), act=act)
+    check(lib().bla_gemm_f32_as_mxfp8(stream, int(transa), int(transb), m, n, k, _ptr(a), lda or a.ld, _ptr(b), ldb or b.ld, _ptr(c), ldc or c.ld, C.byref(ep)))
     return c
 
 

@@ -255,6 +255,54 @@ BLA_API bla_status bla_gemm_bf16_splitk_plan(int m, int n, int k, int splits, in
 BLA_API bla_status bla_gemm_bf16_splitk(void* stream, int transa, int transb, int m, int n, int k, const uint16_t* d_a, int lda, const uint16_t* d_b, int ldb,
                                         void* d_c, int ldc, int c_type, const bla_gemm_epilogue* ep, int splits);
 
+/* ---- MXFP8: OCP microscaling fp8 operands, fp32 accumulation, on v_mfma_scale_f32_32x32x64_f8f6f4 (csrc/bla_gemm_mxfp8.hip) -----------
+ * An addition beside the fp32 and bf16 entries: no existing entry, kernel or dispatcher decision changes.
+ *
+ * Element.  OCP e4m3fn in a uint8_t: 1 sign, 4 exponent (bias 7), 3 mantissa bits; largest finite value 448 (0x7E); 0x7F / 0xFF are NaN; no infinities;
+ * subnormals are multiples of 2^-9.  This is NOT MI300's fnuz encoding.
+ * Scale.  E8M0 in a uint8_t: byte s means 2^(s - 127); 0xFF is NaN.
+ * MX operand of rows x k values, k % 32 == 0: elements [rows][ld] bytes with the contraction contiguous (ld >= k) and scales [rows][ld_s] bytes, byte
+ * [r][g] scaling elements [r][32 g .. 32 g + 31] (ld_s >= k / 32).  Both GEMM operands are stored this way (A is m x k, B is n x k: bla_gemm_bf16's nt
+ * form); other storage orders are the quantiser's business (trans), not the product's.
+ *
+ * Quantisation of a block of 32 fp32 values v (OCP MX v1.0 section 6.3, with the choices it leaves open fixed):
+ *     e = clamp(floor(log2(max|v|)) - 8, -127, 127), scale byte e + 127;  max|v| == 0: byte 127.
+ *     element = v 2^-e (exact in fp32 barring underflow) rounded to nearest even onto the e4m3 grid; a magnitude above 448 after rounding SATURATES to
+ *     +-448; the sign of zero is kept; nothing is flushed on the fp32 side.
+ *     A block that contains a NaN or an infinity: scale byte 0xFF and all 32 elements 0x7F.
+ *     A partial last block (cols % 32 != 0) is completed with +0 VALUES, which are quantised with the block and written up to the next multiple of 32.
+ * Dequantisation: decode(elem) 2^(s - 127), one fp32 multiplication (2^-127 is the fp32 subnormal; 448 2^127 overflows to inf as that multiplication
+ * does); NaN with the bits 0x7FC00000 if either byte is NaN.
+ *
+ * bla_f32_to_mxfp8: trans = 0: the source is [rows][cols] fp32 (ld_src >= cols) and the blocks run along a source row.  trans = 1: the source is stored
+ * [cols][rows] (ld_src >= rows), the contraction index is the slow one and the blocks run down a source column (through an LDS tile).  The output is
+ * the MX operand above in both cases: this is how nn / tn / tt products reach the one nt kernel.  Only the window is written: elements up to cols
+ * rounded up to 32 (ld at least that), ceil(cols / 32) scale bytes per row.  16-byte loads / 4- or 16-byte stores where bases and pitches allow.
+ * bla_mxfp8_to_f32: the dequantisation over a rows x cols window (ld >= cols, ld_s >= ceil(cols / 32), ld_dst >= cols; cols need not be a multiple of 32). */
+BLA_API bla_status bla_f32_to_mxfp8(void* stream, const float* d_src, int ld_src, int trans, int rows, int cols, uint8_t* d_elems, int ld, uint8_t* d_scales, int ld_s);
+BLA_API bla_status bla_mxfp8_to_f32(void* stream, const uint8_t* d_elems, int ld, const uint8_t* d_scales, int ld_s, float* d_dst, int ld_dst, int rows, int cols);
+/*   C[m x n] = epilogue( alpha * A[m x k] . B[n x k]^T )  on the dequantised values, accumulation and epilogue in fp32
+ * c_type and ep are bla_gemm_bf16's (BLA_C_F32 / BLA_C_BF16; alpha, beta, bias_row, bias_col, act) and the same fields are refused in the same way.
+ * k % 32 != 0, a negative extent, a NULL operand or scale array, a pitch below its window: BLA_ERR_INVALID before any launch, C untouched.
+ * Dispatch.  The fast path is a 128 x 128 x 128 tile kernel on the scaled MFMA; it takes any m, n and k (k % 32 == 0, k > 0) when
+ *     d_a and d_b are 16-byte aligned with lda % 16 == 0 and ldb % 16 == 0, and d_sa and d_sb are 4-byte aligned with ldsa % 4 == 0 and ldsb % 4 == 0.
+ * It reads the scales as aligned dwords: the up to 3 bytes of pitch padding behind a row's k / 32 scale bytes may be read (never past the aligned dword
+ * of a valid byte) and are replaced by 127 before use, whatever they hold.  Every other call goes to a bounds-checked kernel that decodes in software
+ * and accumulates a k-ascending fmaf chain of dequantised values: correct, not fast.  bla_gemm_last_kernel() answers
+ *     gemm_mxfp8_mfma128x128x128_<f32|bf16>     the fast path
+ *     gemm_mxfp8_general_<f32|bf16>             the general path
+ * Error.  Products of two dequantised values are exact in fp32 unless they leave its range, so the error is that of the accumulation.
+ * NaN elements and 0xFF scales in a GEMM operand are UNSPECIFIED beyond "no fault, and only the affected rows or columns of C": the conversions define
+ * them, the product documents what was observed (NaN in exactly those rows / columns, on both paths). */
+BLA_API bla_status bla_gemm_mxfp8(void* stream, int m, int n, int k, const uint8_t* d_a, int lda, const uint8_t* d_sa, int ldsa, const uint8_t* d_b, int ldb,
+                                  const uint8_t* d_sb, int ldsb, void* d_c, int ldc, int c_type, const bla_gemm_epilogue* ep /* NULL = plain product */);
+/* bla_gemm_f32_as_bf16's argument list, fp32 A, B and C in memory: both operands are quantised (bla_f32_to_mxfp8, trans chosen so that each comes out
+ * contraction-contiguous: A with trans = transa, B with trans = !transb) into the context workspace at 16-byte aligned bases, an element pitch of k rounded
+ * up to 32 and a scale pitch rounded up to 4, and multiplied by bla_gemm_mxfp8 with k rounded up to 32 and BLA_C_F32 -- exactly that composition, bit
+ * for bit, always on the fast path.  Any k >= 1 (and k = 0) is accepted.  Epilogue: bla_gemm_mxfp8's.  Workspace: bla_gemm_bf16's capture rule. */
+BLA_API bla_status bla_gemm_f32_as_mxfp8(void* stream, int transa, int transb, int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb,
+                                         float* d_c, int ldc, const bla_gemm_epilogue* ep);
+
 /* ---- elementwise / broadcast / transpose / reductions: lib/matrix.c:59-205, lib/util.c:7-55 -------------
  * All operate in place on device memory exactly like their reference counterparts operate on host
  * memory; n = rows*cols.  HBM-bound; sums accumulate in fp64 and are rounded to fp32 once. */
