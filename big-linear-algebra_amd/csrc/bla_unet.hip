@@ -323,7 +323,13 @@ bla_status bla_attention_backward_batched_f32(void* stream, int batch, const flo
 	st = batch_sum(stream, d_partials, d_del_wv, batch, (size_t)ws_); if (st) return st;
 	if (gemm_thin_applies(c, s, d, batch)) {   // the three d-deep terms of del_Z^T accumulate in registers (q, then k, then v) and are stored once  :1322-1334
 		const ThinPart parts[3] = {{d_wq, del_q, 0, qs, d, d}, {d_wk, del_k, 0, qs, d, d}, {d_wv, del_v, 0, qs, d, d}};
-		return gemm_thin_parts(stream, 0, 1, c, s, d, parts, 3, d_del_x, s, xs, batch, 1.f, 0.f, nullptr, nullptr, 0, 0);
+		st = gemm_thin_parts(stream, 0, 1, c, s, d, parts, 3, d_del_x, s, xs, batch, 1.f, 0.f, nullptr, nullptr, 0, 0);
+		if (st == BLA_OK) {   // (gemm_thin_parts is below bla_gemm_batched_f32, which names its own launches: without this bla_gemm_last_kernel() still showed del_Wv's product)
+			char name[64];
+			snprintf(name, sizeof(name), "gemm_f32_thin_nt_x%d_parts3", batch);
+			gemm_note_last_kernel(name);
+		}
+		return st;
 	}
 	st = bgemm(stream, 0, 1, c, s, d, d_wq, d, 0, del_q, d, qs, d_del_x, s, xs, batch); if (st) return st;                      // del_Z^T, same add order :1322-1334
 	st = bgemm(stream, 0, 1, c, s, d, d_wk, d, 0, del_k, d, qs, d_del_x, s, xs, batch, 1.f, 1.f); if (st) return st;

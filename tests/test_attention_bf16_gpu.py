@@ -86,8 +86,8 @@ def passes(dev):
 
 @pytest.mark.parametrize("case", host.CASES, ids=str)
 def test_against_the_unrounded_float64_block(passes, case):
-    """Measured on an MI355X (profiles/r21_attention_bf16_tests.txt): device / recorded 1.00 in all 30 tensors, and the device within 2e-4
-    normwise of the rounded restatement itself."""
+    """Measured on an MI355X (profiles/r21_attention_bf16_tests.txt; the nine cases, nine of the backward core's sixteen instantiations:
+    profiles/r23_unet_paths_tests.txt): device / recorded 1.00 in all 54 tensors, and the device within 2e-4 normwise of the rounded restatement itself."""
     I, exact, rounded, diff = host.recorded(case)
     got = passes(case)
     for n in host.OUTPUTS:

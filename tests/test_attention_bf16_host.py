@@ -15,7 +15,11 @@ Two host-only requirements on the recorded values, as in tests/test_unet_bf16_ho
   (a) they are a property of the arithmetic, not of one draw of the roundings: a relative 2^-23 perturbation of every product's result in front of its
       next rounding moves no recorded value by more than half of itself;
   (b) they catch wiring errors: each of six wrong blocks puts some tensor more than 4 times its recorded value away from exact.
-The exact forward case (Wq = 0, small integers) has the same bits in float32 and in float64, whatever the order of summation: the device must hit them."""
+The exact forward case (Wq = 0, small integers) has the same bits in float32 and in float64, whatever the order of summation: the device must hit them.
+
+The nine CASES reach nine of the backward core's sixteen instantiations att_bf16_bwd_core_kernel<S / 32, ceil(d / 32)>: <1, 1>, <2, 1>, <3, 1>, <4, 1>, <5, 1>,
+<8, 1> and <6, 2>, <7, 2>, <8, 2> -- among them every S / 32 in {5, 6, 7}, where the second round of row blocks has active and parked waves side by side, d = 32
+(the last on one d tile) and d = 40, 48 (two d tiles, off and on a multiple of 16); batch 11 takes the fold's unrolled loop and its tail."""
 import ctypes as C
 import functools
 import os
@@ -33,7 +37,13 @@ CASES = [(2, 24, 32, 8),       # one wave, padded contraction, C off 16 and 32
          (3, 64, 96, 16),      # three row blocks, S not a power of two
          (2, 40, 64, 24),      # d off 16
          (1, 256, 256, 16),    # the model's shape, largest S
-         (2, 32, 256, 64)]     # largest d
+         (2, 32, 256, 64),     # largest d
+         # appended (seeds go by index; CASES[1] is named elsewhere): S / 32 in {5, 6, 7} -- the second round of row blocks of the backward core has some waves
+         # active and the others parked on row block 0 -- and the d classes the five above leave out
+         (11, 16, 160, 8),     # S / 32 = 5: one wave active in the second round; batch 8 + 3 through the fold's unrolled loop and its tail; C < 32
+         (2, 72, 128, 32),     # S / 32 = 4; d = 32, the last d on one 32-wide d tile; C off 16 and 32
+         (1, 48, 192, 48),     # S / 32 = 6, two d tiles
+         (1, 8, 224, 40)]      # S / 32 = 7, two d tiles, d off 16, smallest C
 OUTPUTS = ["out", "del_x", "del_wq", "del_wk", "del_wv", "del_w"]
 EX = os.path.join(ROOT, "examples")
 
