@@ -21,7 +21,13 @@
 // test_unet_glue.py); the composition is pinned against the same composition of the oracle's blocks (tests/test_unet_model.py).
 // bla_unet_create_mixed(.., BLA_UNET_PRODUCTS_BF16) is the same composition with the ResNet blocks and the stand-alone convolutions on the bf16 stack:
 // same buckets, same entries, one stream; pinned against a float64 restatement with the compositions' roundings (tests/test_unet_bf16_{host,gpu}.py).
+//
+// The wiring stands in ONE place, the step list kNetwork, and three walkers read it: bla_unet_create_mixed forwards (parameter bucket, tensor names, dropout
+// offsets; then every step's buffers and its input / output / skip pointers), bla_unet_forward_f32 forwards, unet_backward in reverse.  A change of topology is
+// an edit of kNetwork (and of res[18] / att[5] / kEmbSplit if the number of blocks changes).  What the two product stacks do differently is one table of calls
+// (Stack), chosen at create; attention is chosen per call (bla_unet_set_attention).
 #include "bla_internal.h"
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -33,6 +39,8 @@ struct Tensor { size_t off, count; std::string name; };
 struct Res {
 	int cin, cout, h, w;
 	size_t conv1, conv2, tw, tb, res;   // offsets in the buckets (res = SIZE_MAX when cin == cout)
+	bla_resnet_params p;                // the same as addresses in the parameter bucket
+	bla_resnet_grads g;                 // ... and in the gradient bucket
 	bla_resnet_ws ws;
 	float* result;
 	ResnetPads pads = {nullptr, nullptr, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // batched: zero-haloed padded copies of the two convolution inputs, filled by the norm kernels
@@ -58,6 +66,39 @@ struct Conv {
 	const uint16_t *prep16_fwd = nullptr, *prep16_bwd = nullptr;   // bf16 products: the same from the bf16 table launches
 };
 constexpr size_t kNone = (size_t)-1;
+
+// THE NETWORK, stated once: its steps in forward order.  index: into res[] / att[] / down[] / up[] (RESIZE: the up-sampling stage, CONCAT: the skip connection
+// it reads); level: the resolution 0..3 of the step's output; tap: the step's output is also skip connection `tap` (-1: none); name: of its parameter tensors.
+// A step reads the previous step's output -- the first one the model's input (in == NULL), the one behind a CONCAT the concatenation -- and an UP whose two
+// widths are equal is absent: it passes its input on.  create fills in / out / skip (a resized map, a concatenation and the output ReLU live in `out` alone).
+enum StepKind { RES, ATT, DOWN, RESIZE, UP, CONCAT, OUT_NORM, OUT_CONV };
+struct Step { StepKind kind; int index, level, tap; const char* name; const float* in; float* out; const float* skip; };
+const Step kNetwork[] = {
+	{RES, 0, 0, -1, "down_1_resnet_1"}, {RES, 1, 0, 3, "down_1_resnet_2"}, {DOWN, 0, 1, -1, "down_1_conv_kernels"},
+	{RES, 2, 1, -1, "down_2_resnet_1"}, {ATT, 0, 1, -1, "down_2_self_attention_1"}, {RES, 3, 1, 2, "down_2_resnet_2"}, {ATT, 1, 1, -1, "down_2_self_attention_2"},
+	{DOWN, 1, 2, -1, "down_2_conv_kernels"},
+	{RES, 4, 2, -1, "down_3_resnet_1"}, {RES, 5, 2, 1, "down_3_resnet_2"}, {DOWN, 2, 3, -1, "down_3_conv_kernels"},
+	{RES, 6, 3, -1, "down_4_resnet_1"}, {RES, 7, 3, 0, "down_4_resnet_2"},
+	{RES, 8, 3, -1, "mid_resnet_1"}, {ATT, 2, 3, -1, "mid_self_attention"}, {RES, 9, 3, -1, "mid_resnet_2"},
+	{CONCAT, 0, 3, -1, nullptr}, {RES, 10, 3, -1, "up_1_resnet_1"}, {RES, 11, 3, -1, "up_1_resnet_2"}, {RESIZE, 0, 2, -1, nullptr}, {UP, 0, 2, -1, "up_1_conv_kernels"},
+	{CONCAT, 1, 2, -1, nullptr}, {RES, 12, 2, -1, "up_2_resnet_1"}, {RES, 13, 2, -1, "up_2_resnet_2"}, {RESIZE, 1, 1, -1, nullptr}, {UP, 1, 1, -1, "up_2_conv_kernels"},
+	{CONCAT, 2, 1, -1, nullptr}, {RES, 14, 1, -1, "up_3_resnet_1"}, {ATT, 3, 1, -1, "up_3_self_attention_1"}, {RES, 15, 1, -1, "up_3_resnet_2"},
+	{ATT, 4, 1, -1, "up_3_self_attention_2"}, {RESIZE, 2, 0, -1, nullptr}, {UP, 2, 0, -1, "up_3_conv_kernels"},
+	{CONCAT, 3, 0, -1, nullptr}, {RES, 16, 0, -1, "up_4_resnet_1"}, {RES, 17, 0, -1, "up_4_resnet_2"},
+	{OUT_NORM, 0, 0, -1, nullptr}, {OUT_CONV, 0, 0, -1, "output_conv_kernels"},   // :1163-1165
+};
+
+// What differs between the two product stacks (fp32: bla_unet.hip / bla_conv.hip; bf16: bla_conv_bf16.hip), chosen once per model from its
+// `products`: a block's buffers, the kernel-matrix tables of the two passes, a block and a stand-alone convolution each way.  Nothing else asks which stack it is.
+struct Stack {
+	bla_status (*alloc_block)(bla_unet*, Res&);
+	bla_status (*plan_tables)(bla_unet*);
+	bla_status (*block_forward)(bla_unet*, void* stream, Res&, const float* in, const float* temb, const unsigned char* drop);
+	bla_status (*block_backward)(bla_unet*, void* stream, Res&, const float* g, const float* x, float* out);      // g: gradient of the result, out: of the input x
+	bla_status (*conv_forward)(bla_unet*, void* stream, const Conv&, const float* in);
+	bla_status (*conv_backward)(bla_unet*, void* stream, const Conv&, const float* g, const float* x, float* out);
+};
+constexpr size_t kGradPool = 48;   // side lane: the write-once gradient buffers of a backward pass
 }  // namespace
 
 struct bla_unet {
@@ -65,23 +106,25 @@ struct bla_unet {
 	int batch = 1;
 	int attention = BLA_UNET_ATTENTION_F32;   // BLA_UNET_ATTENTION_BF16: the attention blocks that qualify on bla_attention_{forward,backward}_batched_bf16
 	int products = BLA_UNET_PRODUCTS_F32;   // BLA_UNET_PRODUCTS_BF16: the blocks and the stand-alone convolutions on the bf16 stack, one stream
-	int H[4], W[4];
+	const Stack* stack = nullptr;           // the calls of `products`
+	int H[4], W[4], max_cout = 1;           // the four resolutions; the widest block output
+	std::vector<Step> steps;               // kNetwork with in / out / skip resolved against this model's buffers
 	std::vector<Tensor> tensors;
 	size_t count = 0, drop_count = 0;
 	float *params = nullptr, *grads = nullptr;
 	Res res[18];
 	Att att[5];
 	Conv down[3], up[3], outc;
-	float *cat[4] = {nullptr, nullptr, nullptr, nullptr};      // skip concatenations, stage order up_1 .. up_4
-	float *nn[3] = {nullptr, nullptr, nullptr};                // nearest-neighbour outputs
-	float *out_relu = nullptr, *out_mu = nullptr, *out_sd = nullptr;
+	float *out_mu = nullptr, *out_sd = nullptr;                // the output norm's statistics (the resized maps, the concatenations and the output ReLU: their steps' `out`)
 	unsigned char* zero_drop = nullptr;
 	// backward
-	float *t1 = nullptr, *t2 = nullptr, *t3 = nullptr, *gskip[4] = {nullptr, nullptr, nullptr, nullptr};
+	float *ring[3] = {nullptr, nullptr, nullptr}, *gskip[4] = {nullptr, nullptr, nullptr, nullptr};   // the rotating gradient buffers; the skip connections' gradients
 	TimeJob* time_jobs = nullptr;                // device, one per ResNet block (batch > 1)
 	TimeJob* emb_jobs = nullptr;                 // device, one per ResNet block, every configuration: dtb = where the backward pass leaves the block's per-image
-	                                             // channel sums (r.dtb; at B = 1 the block's time-bias gradient itself) -- read by bla_unet_embedding_grad_f32
-	bool have_grads = false;                     // a backward pass has run since the last forward pass
+	                                             // channel sums (r.dtb: then this IS time_jobs; the fp32 single-image model: the block's time-bias gradient itself,
+	                                             // a table of its own) -- read by bla_unet_embedding_grad_f32
+	bool defer_time_grads = false;               // the blocks leave their per-image channel sums in r.dtb, time_grads_all_kernel ends the backward pass (time_jobs and: a batch, or bf16 products)
+	bool have_grads = false;                    // a backward pass has run since the last forward pass
 	float* g_res = nullptr;                                      // batched: the residual 1x1 convolutions' data gradient (largest block input)
 	// batched, weight gradients on the context's side lane (BLA_UNET_SIDE=0: off): every gradient buffer of a backward pass is written ONCE (a pool instead of
 	// three rotating buffers), every block has its own g_out_b -- what the lane reads stays intact until the pass's one join
@@ -97,16 +140,30 @@ struct bla_unet {
 	float *dtb = nullptr, *partials = nullptr;   // batched blocks: per-image time-bias sums [B][Cout], per-image attention weight gradients [B][C*d]
 	bla_resnet_scratch sc = {};
 	bla_attention_ws agrad = {};
-	const float* last_x = nullptr; const float* last_temb = nullptr; const unsigned char* last_drop = nullptr;
+	const float* last_x = nullptr; const float* last_temb = nullptr;   // the last forward pass's (the backward pass reads them)
 	std::vector<void*> owned;
 };
 
 namespace {
-bla_status dalloc(bla_unet* m, float** p, size_t floats) {
+// n elements of device memory that the model owns (freed by bla_unet_destroy)
+template <typename T> bla_status dalloc(bla_unet* m, T** p, size_t n) {
 	void* q = nullptr;
-	BLA_HIP(hipMalloc(&q, (floats ? floats : 1) * sizeof(float)));
+	BLA_HIP(hipMalloc(&q, (n ? n : 1) * sizeof(T)));
 	m->owned.push_back(q);
-	*p = (float*)q;
+	*p = (T*)q;
+	return BLA_OK;
+}
+template <typename T> bla_status dalloc_zeroed(bla_unet* m, T** p, size_t n) {
+	bla_status st = dalloc(m, p, n);
+	if (st) return st;
+	BLA_HIP(hipMemsetAsync(*p, 0, n * sizeof(T), ctx().stream));
+	return BLA_OK;
+}
+// a host table of jobs as a device table (none: *d stays NULL)
+template <typename T> bla_status upload_table(bla_unet* m, const T* v, size_t n, T** d) {
+	bla_status st = n ? dalloc(m, d, n) : BLA_OK;
+	if (st || !n) return st;
+	BLA_HIP(hipMemcpy(*d, v, n * sizeof(T), hipMemcpyHostToDevice));
 	return BLA_OK;
 }
 size_t add_tensor(bla_unet* m, const std::string& name, size_t count) {
@@ -149,13 +206,7 @@ bool keep_relu2(const bla_unet* m, const Res& r) {
 bla_status alloc_map(bla_unet* m, uint16_t** p, int c, int h, int w, bool data_gradient) {
 	int hp, wp, top, left, dilate;
 	bla_status st = bla_conv_bf16_layout(h, w, m->cfg.kernel, 1, data_gradient, &hp, &wp, &top, &left, &dilate);
-	if (st) return st;
-	const size_t bytes = (size_t)m->batch * hp * wp * round8(c) * sizeof(uint16_t);
-	float* q = nullptr;
-	if ((st = dalloc(m, &q, (bytes + 3) / 4))) return st;
-	BLA_HIP(hipMemsetAsync(q, 0, bytes, ctx().stream));
-	*p = (uint16_t*)q;
-	return BLA_OK;
+	return st ? st : dalloc_zeroed(m, p, (size_t)m->batch * hp * wp * round8(c));
 }
 // bf16 products: relu1, relu2, dp, the fp32 padded copies and the fp32 prepared kernels have no reader; the three maps take their place.  Every block its own
 // p1 / p2 (the gates of its backward pass) and its own q1.  The per-image channel sums (dtb) at every batch: the time gradients are always deferred here.
@@ -174,7 +225,6 @@ bla_status alloc_res_bf16(bla_unet* m, Res& r) {
 	return BLA_OK;
 }
 bla_status alloc_res(bla_unet* m, Res& r) {
-	if (m->products == BLA_UNET_PRODUCTS_BF16) return alloc_res_bf16(m, r);
 	const size_t hw = (size_t)r.h * r.w * m->batch;   // (every buffer of the block: B times its single-image size)
 	const int gs = m->cfg.group_size, g1 = (r.cin + gs - 1) / gs * m->batch, g2 = (r.cout + gs - 1) / gs * m->batch;
 	bla_status st;
@@ -198,17 +248,13 @@ bla_status alloc_res(bla_unet* m, Res& r) {
 	const PadLayout L = conv_padded_layout(r.h, r.w, m->cfg.kernel, 1);
 	if (pads_on && L.plane > 0) {
 		const size_t p1 = (size_t)m->batch * r.cin * L.plane, p2 = (size_t)m->batch * r.cout * L.plane;
-		if (r.cin > 4) { if ((st = dalloc(m, &r.pads.pad1, p1))) return st; BLA_HIP(hipMemsetAsync(r.pads.pad1, 0, p1 * sizeof(float), ctx().stream)); }
-		if ((st = dalloc(m, &r.pads.pad2, p2))) return st;
-		BLA_HIP(hipMemsetAsync(r.pads.pad2, 0, p2 * sizeof(float), ctx().stream));
+		if (r.cin > 4 && (st = dalloc_zeroed(m, &r.pads.pad1, p1))) return st;
+		if ((st = dalloc_zeroed(m, &r.pads.pad2, p2))) return st;
 		// one scratch per resolution for the padded gradient in front of conv_1's data gradient (all blocks of a resolution share layout and halo)
 		int res_i = 0;
 		while (res_i < 3 && m->H[res_i] != r.h) res_i++;
 		const size_t widest = (size_t)m->batch * std::max(std::max(m->cfg.dims[0], m->cfg.dims[1]), std::max(m->cfg.dims[2], m->cfg.dims[3])) * L.plane;
-		if (!m->dy_pad[res_i]) {
-			if ((st = dalloc(m, &m->dy_pad[res_i], widest))) return st;
-			BLA_HIP(hipMemsetAsync(m->dy_pad[res_i], 0, widest * sizeof(float), ctx().stream));
-		}
+		if (!m->dy_pad[res_i] && (st = dalloc_zeroed(m, &m->dy_pad[res_i], widest))) return st;
 		r.pads.dy_pad = m->dy_pad[res_i];
 	}
 	return BLA_OK;
@@ -349,6 +395,172 @@ __global__ void __launch_bounds__(256) unet_split_kernel(const float* __restrict
 	}
 }
 unsigned grid_of(size_t n) { size_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
+
+// ---- the steps' calls -------------------------------------------------------------------------------------------------------------------------------------
+Conv& conv_of(bla_unet* m, const Step& s) { return s.kind == DOWN ? m->down[s.index] : s.kind == UP ? m->up[s.index] : m->outc; }
+// an absent step launches nothing either way and writes no gradient
+bool step_runs(bla_unet* m, const Step& s) { return s.kind != UP || conv_of(m, s).present; }
+bla_status block_forward_f32(bla_unet* m, void* stream, Res& r, const float* in, const float* temb, const unsigned char* drop) {
+	const bla_unet_config& c = m->cfg;
+	return resnet_forward_batched(stream, m->batch, in, temb, &r.p, drop, &r.ws, r.result, r.h, r.w, r.cin, r.cout, c.kernel, c.time_dim, c.group_size,
+	                              m->time_jobs ? RESNET_TDENSE_READY : 0, m->batch > 1 ? &r.pads : nullptr);
+}
+bla_status block_forward_bf16(bla_unet* m, void* stream, Res& r, const float* in, const float* temb, const unsigned char* drop) {
+	const bla_unet_config& c = m->cfg;
+	return resnet_forward_bf16(stream, m->batch, in, temb, &r.p, drop, &r.ws, r.result, r.h, r.w, r.cin, r.cout, c.kernel, c.time_dim, c.group_size, &r.maps,
+	                           m->time_jobs ? RESNET_TDENSE_READY : 0, &r.prep16);
+}
+bla_status block_backward_f32(bla_unet* m, void* stream, Res& r, const float* g, const float* x, float* out) {
+	const bla_unet_config& c = m->cfg;
+	const int B = m->batch;
+	return resnet_backward_batched(stream, B, g, x, m->last_temb, &r.p, &r.ws, &r.g, &m->sc, B > 1 ? r.dtb : m->dtb, out, r.h, r.w, r.cin, r.cout, c.kernel, c.time_dim,
+	                               c.group_size, (m->defer_time_grads ? RESNET_DEFER_TIME_GRADS : 0) | (m->side ? RESNET_WGRAD_SIDE : 0), B > 1 ? &r.pads : nullptr);
+}
+bla_status block_backward_bf16(bla_unet* m, void* stream, Res& r, const float* g, const float* x, float* out) {
+	const bla_unet_config& c = m->cfg;   // (the channel sums go to r.dtb at every batch: bla_unet_embedding_grad_f32 reads them there)
+	return resnet_backward_bf16(stream, m->batch, g, x, m->last_temb, &r.p, &r.ws, &r.g, &m->sc, r.dtb, out, r.h, r.w, r.cin, r.cout, c.kernel, c.time_dim, c.group_size,
+	                            &r.maps, 0, m->defer_time_grads ? RESNET_DEFER_TIME_GRADS : 0, &r.prep16);
+}
+bla_status conv_forward_f32(bla_unet* m, void* stream, const Conv& k, const float* in) {
+	return conv2d_forward_epilogue(stream, in, m->params + k.kern, k.out, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, nullptr, nullptr, m->batch, 0, nullptr, k.prep_fwd);
+}
+bla_status conv_forward_bf16(bla_unet* m, void* stream, const Conv& k, const float* in) {
+	return conv2d_forward_as_bf16(stream, in, m->params + k.kern, k.out, m->batch, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, 0, k.prep16_fwd);
+}
+bla_status conv_backward_f32(bla_unet* m, void* stream, const Conv& k, const float* g, const float* x, float* out) {
+	const float* kern = m->params + k.kern;
+	float* g_kern = m->grads + k.kern;
+	const int B = m->batch;
+	if (m->side) {      // weight gradient on the side lane (g and x stay intact until the pass's join), data gradient here
+		hipStream_t lane;
+		bla_status st = side_lane_fork(pick_stream(stream), &lane);
+		if (st) return st;
+		st = conv2d_backward_batched(lane, g, x, kern, g_kern, nullptr, m->sc.flip, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, nullptr);
+		side_lane_done();
+		if (st) return st;
+		g_kern = nullptr;
+	}
+	return conv2d_backward_batched(stream, g, x, kern, g_kern, out, m->sc.flip, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, k.prep_bwd);
+}
+bla_status conv_backward_bf16(bla_unet* m, void* stream, const Conv& k, const float* g, const float* x, float* out) {
+	return conv2d_backward_gathered_as_bf16(stream, g, x, m->params + k.kern, m->grads + k.kern, out, m->batch, k.h, k.w, k.k, k.cin, k.cout, k.stride, 0, k.prep16_bwd);
+}
+// attention: by the model's mode and the block's shape, asked at every call (bla_unet_set_attention may come after create)
+bool att_on_bf16(const bla_unet* m, const Att& a) { return m->attention == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(a.c, a.h * a.w, m->cfg.key_dim); }
+bla_status att_forward(bla_unet* m, void* stream, Att& a, const float* in) {
+	const float* P = m->params;
+	return (att_on_bf16(m, a) ? bla_attention_forward_batched_bf16 : bla_attention_forward_batched_f32)(
+		stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, m->cfg.key_dim);
+}
+bla_status att_backward(bla_unet* m, void* stream, Att& a, const float* g, const float* x, float* out) {
+	const float* P = m->params; float* G = m->grads;
+	const int d = m->cfg.key_dim;
+	if (att_on_bf16(m, a))
+		return bla_attention_backward_batched_bf16(stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk,
+		                                           G + a.wv, G + a.wo, out, a.c, a.h * a.w, d);
+	return bla_attention_backward_batched_f32(stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv,
+	                                          G + a.wo, out, a.c, a.h * a.w, d, 0);
+}
+// floats per image of a map at the width and size of resolution `level`: a tapped output, one half of a concatenation
+size_t level_floats(const bla_unet* m, int level) { return (size_t)m->cfg.dims[level] * m->H[level] * m->W[level]; }
+// _concat_skip, model/cifar_unet.c:1088-1097: (the previous step's output, skip connection s.index) -> cat[s.index]
+bla_status concat(bla_unet* m, hipStream_t stream, const Step& s) {
+	const size_t n = level_floats(m, s.level), B = m->batch;
+	if (n % 4 == 0 && ((uintptr_t)s.in | (uintptr_t)s.skip | (uintptr_t)s.out) % 16 == 0)
+		hipLaunchKernelGGL(unet_concat4_kernel, dim3(grid_of(n / 2 * B)), dim3(256), 0, stream, (const float4*)s.in, (const float4*)s.skip, (float4*)s.out, n / 4, n / 2 * B);
+	else hipLaunchKernelGGL(unet_concat_kernel, dim3(grid_of(2 * n * B)), dim3(256), 0, stream, s.in, s.skip, s.out, n, 2 * n * B);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+// _split_concat, :1339-1349: the first half of a concatenation's gradient goes on along the main path, the second is skip connection s.index's
+bla_status split(bla_unet* m, hipStream_t stream, const Step& s, const float* g_cat, float* g_main) {
+	const size_t n = level_floats(m, s.level), B = m->batch;
+	float* g_skip = m->gskip[s.index];
+	if (n % 4 == 0 && ((uintptr_t)g_cat | (uintptr_t)g_main | (uintptr_t)g_skip) % 16 == 0)
+		hipLaunchKernelGGL(unet_split4_kernel, dim3(grid_of(n / 2 * B)), dim3(256), 0, stream, (const float4*)g_cat, (float4*)g_main, (float4*)g_skip, n / 4, n / 2 * B);
+	else hipLaunchKernelGGL(unet_split_kernel, dim3(grid_of(2 * n * B)), dim3(256), 0, stream, g_cat, g_main, g_skip, n, 2 * n * B);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+// gradient buffers one backward pass writes: the loss seed, then one per step that runs -- but the first, whose input gradient nobody consumes
+size_t backward_writes(bla_unet* m) { return 1 + std::count_if(m->steps.begin() + 1, m->steps.end(), [&](const Step& s) { return step_runs(m, s); }); }
+
+// ---- the kernel-matrix tables of the two passes -----------------------------------------------------------------------------------------------------------
+// fp32, batch > 1: one launch at the head of forward() and one at the head of backward() put every convolution's kernels into the form its product reads (window
+// order, flipped): 49 five-microsecond launches per pass become 2.  The parameters do not change inside a pass, so the prepared copies are valid for it.
+bla_status plan_tables_f32(bla_unet* m) {
+	std::vector<KernelPrepJob> jf, jb;
+	auto add = [&](size_t kern_off, int h, int w, int k, int cin, int cout, bool want_dgrad, const float** pf, const float** pb) -> bla_status {
+		const size_t n = (size_t)cout * cin * k * k;
+		const int mf = conv_kernel_prep_mode(m->batch, h, w, k, cin, cout, 1, false), mb = want_dgrad ? conv_kernel_prep_mode(m->batch, h, w, k, cin, cout, 1, true) : 0;
+		for (int which = 0; which < 2; which++) {
+			const int mode = which ? mb : mf;
+			if (!mode) continue;
+			float* dst;
+			bla_status st = dalloc(m, &dst, n);
+			if (st) return st;
+			(which ? jb : jf).push_back(KernelPrepJob{m->params + kern_off, dst, cout, cin, k, mode});
+			*(which ? pb : pf) = dst;
+			m->prep_max = std::max(m->prep_max, n);
+		}
+		return BLA_OK;
+	};
+	bla_status st;
+	for (int i = 0; i < 18; i++) {
+		Res& r = m->res[i];
+		if ((st = add(r.conv1, r.h, r.w, m->cfg.kernel, r.cin, r.cout, i != 0, &r.pads.k1_fwd, &r.pads.k1_bwd)) ||     // (block 0 forms no gradient of the image)
+		    (st = add(r.conv2, r.h, r.w, m->cfg.kernel, r.cout, r.cout, true, &r.pads.k2_fwd, &r.pads.k2_bwd)))
+			return st;
+	}
+	for (Conv& u : m->up)
+		if (u.present && (st = add(u.kern, u.h, u.w, u.k, u.cin, u.cout, true, &u.prep_fwd, &u.prep_bwd))) return st;
+	m->n_prep_fwd = (int)jf.size(); m->n_prep_bwd = (int)jb.size();
+	if ((st = upload_table(m, jf.data(), jf.size(), &m->prep_fwd))) return st;
+	return upload_table(m, jb.data(), jb.size(), &m->prep_bwd);
+}
+// bf16: one table launch at the head of each pass writes every bf16 kernel matrix of that pass into a matrix the model owns: the forward set is
+// every convolution, the data-gradient set the same minus block 0's conv1 (nothing consumes the gradient of the image; its residual 1 x 1 likewise).
+// BLA_UNET_BF16_PREP=0, read HERE at every create call: no tables, every composition prepares its own matrix in the workspace -- the same bits.
+bla_status plan_tables_bf16(bla_unet* m) {
+	const char* e = getenv("BLA_UNET_BF16_PREP");
+	if (e && e[0] == '0') return BLA_OK;
+	std::vector<bla_conv_bf16_prep_job> jf, jb;
+	auto add = [&](size_t kern_off, int k, int cin, int cout, bool dgrad, const uint16_t** dst_out) -> bla_status {
+		const int rows = dgrad ? cin : cout, ip = round8(dgrad ? cout : cin);
+		const size_t chunks = (size_t)rows * k * k * (ip / 8);
+		uint16_t* q = nullptr;
+		bla_status st = dalloc(m, &q, chunks * 8);      // (hipMalloc: 16-byte aligned)
+		if (st) return st;
+		(dgrad ? jb : jf).push_back(bla_conv_bf16_prep_job{m->params + kern_off, q, cout, cin, k, dgrad ? 1 : 0});
+		size_t& mx = dgrad ? m->prep16_max_bwd : m->prep16_max_fwd;
+		mx = std::max(mx, chunks);
+		*dst_out = q;
+		return BLA_OK;
+	};
+	bla_status st;
+	const int k = m->cfg.kernel;
+	for (int i = 0; i < 18; i++) {
+		Res& r = m->res[i];
+		if ((st = add(r.conv1, k, r.cin, r.cout, false, &r.prep16.k1_fwd)) || (st = add(r.conv2, k, r.cout, r.cout, false, &r.prep16.k2_fwd)) ||
+		    (st = add(r.conv2, k, r.cout, r.cout, true, &r.prep16.k2_bwd)))
+			return st;
+		if (i != 0 && (st = add(r.conv1, k, r.cin, r.cout, true, &r.prep16.k1_bwd))) return st;
+		if (r.res != kNone && ((st = add(r.res, 1, r.cin, r.cout, false, &r.prep16.res_fwd)) || (i != 0 && (st = add(r.res, 1, r.cin, r.cout, true, &r.prep16.res_bwd)))))
+			return st;
+	}
+	auto add_conv = [&](Conv& c) -> bla_status {
+		if (!c.present) return BLA_OK;
+		bla_status s2 = add(c.kern, c.k, c.cin, c.cout, false, &c.prep16_fwd);
+		return s2 ? s2 : add(c.kern, c.k, c.cin, c.cout, true, &c.prep16_bwd);
+	};
+	for (int i = 0; i < 3; i++) if ((st = add_conv(m->down[i])) || (st = add_conv(m->up[i]))) return st;
+	if ((st = add_conv(m->outc))) return st;
+	m->n_prep16_fwd = (int)jf.size(); m->n_prep16_bwd = (int)jb.size();
+	if ((st = upload_table(m, jf.data(), jf.size(), &m->prep16_fwd))) return st;
+	return upload_table(m, jb.data(), jb.size(), &m->prep16_bwd);
+}
+const Stack kStackF32 = {alloc_res, plan_tables_f32, block_forward_f32, block_backward_f32, conv_forward_f32, conv_backward_f32};
+const Stack kStackBf16 = {alloc_res_bf16, plan_tables_bf16, block_forward_bf16, block_backward_bf16, conv_forward_bf16, conv_backward_bf16};
 }  // namespace
 
 const bla_unet_config* bla::unet_config(const bla_unet* m) { return &m->cfg; }
@@ -384,211 +596,113 @@ bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int
 	m->cfg = *cfg;
 	m->batch = batch;
 	m->products = products;
+	m->stack = bf16 ? &kStackBf16 : &kStackF32;
 	const size_t B = (size_t)batch;
 	const int* D = cfg->dims;
 	m->H[0] = cfg->image_h; m->W[0] = cfg->image_w;
 	for (int i = 1; i < 4; i++) { m->H[i] = (m->H[i - 1] + 1) / 2; m->W[i] = (m->W[i - 1] + 1) / 2; }   // RESOLUTION_n_HEIGHT, :39-46
 	const int* H = m->H; const int* W = m->W;
-	// parameter bucket, in the order of first use by forward()
-	plan_res(m, m->res[0], "down_1_resnet_1", cfg->in_channels, D[0], H[0], W[0]);
-	plan_res(m, m->res[1], "down_1_resnet_2", D[0], D[0], H[0], W[0]);
-	plan_conv(m, m->down[0], "down_1_conv_kernels", D[0], D[1], H[0], W[0], 2);
-	plan_res(m, m->res[2], "down_2_resnet_1", D[1], D[1], H[1], W[1]);
-	plan_att(m, m->att[0], "down_2_self_attention_1", D[1], H[1], W[1]);
-	plan_res(m, m->res[3], "down_2_resnet_2", D[1], D[1], H[1], W[1]);
-	plan_att(m, m->att[1], "down_2_self_attention_2", D[1], H[1], W[1]);
-	plan_conv(m, m->down[1], "down_2_conv_kernels", D[1], D[2], H[1], W[1], 2);
-	plan_res(m, m->res[4], "down_3_resnet_1", D[2], D[2], H[2], W[2]);
-	plan_res(m, m->res[5], "down_3_resnet_2", D[2], D[2], H[2], W[2]);
-	plan_conv(m, m->down[2], "down_3_conv_kernels", D[2], D[3], H[2], W[2], 2);
-	plan_res(m, m->res[6], "down_4_resnet_1", D[3], D[3], H[3], W[3]);
-	plan_res(m, m->res[7], "down_4_resnet_2", D[3], D[3], H[3], W[3]);
-	plan_res(m, m->res[8], "mid_resnet_1", D[3], D[3], H[3], W[3]);
-	plan_att(m, m->att[2], "mid_self_attention", D[3], H[3], W[3]);
-	plan_res(m, m->res[9], "mid_resnet_2", D[3], D[3], H[3], W[3]);
-	plan_res(m, m->res[10], "up_1_resnet_1", 2 * D[3], D[3], H[3], W[3]);
-	plan_res(m, m->res[11], "up_1_resnet_2", D[3], D[3], H[3], W[3]);
-	plan_conv(m, m->up[0], "up_1_conv_kernels", D[3], D[2], H[2], W[2], 1, D[3] != D[2]);
-	plan_res(m, m->res[12], "up_2_resnet_1", 2 * D[2], D[2], H[2], W[2]);
-	plan_res(m, m->res[13], "up_2_resnet_2", D[2], D[2], H[2], W[2]);
-	plan_conv(m, m->up[1], "up_2_conv_kernels", D[2], D[1], H[1], W[1], 1, D[2] != D[1]);
-	plan_res(m, m->res[14], "up_3_resnet_1", 2 * D[1], D[1], H[1], W[1]);
-	plan_att(m, m->att[3], "up_3_self_attention_1", D[1], H[1], W[1]);
-	plan_res(m, m->res[15], "up_3_resnet_2", D[1], D[1], H[1], W[1]);
-	plan_att(m, m->att[4], "up_3_self_attention_2", D[1], H[1], W[1]);
-	plan_conv(m, m->up[2], "up_3_conv_kernels", D[1], D[0], H[0], W[0], 1, D[1] != D[0]);
-	plan_res(m, m->res[16], "up_4_resnet_1", 2 * D[0], D[0], H[0], W[0]);
-	plan_res(m, m->res[17], "up_4_resnet_2", D[0], D[0], H[0], W[0]);
-	plan_conv(m, m->outc, "output_conv_kernels", D[0], cfg->in_channels, H[0], W[0], 1);
+	// the parameter bucket, the tensor names and the dropout offsets: the steps in forward order, `ch` the channels that arrive at each
+	m->steps.assign(std::begin(kNetwork), std::end(kNetwork));
+	int ch = cfg->in_channels;
+	for (const Step& s : m->steps) {
+		const int l = s.level;
+		switch (s.kind) {
+		case RES: plan_res(m, m->res[s.index], s.name, ch, D[l], H[l], W[l]); ch = D[l]; break;
+		case ATT: plan_att(m, m->att[s.index], s.name, ch, H[l], W[l]); break;
+		case DOWN: plan_conv(m, m->down[s.index], s.name, ch, D[l], H[l - 1], W[l - 1], 2); ch = D[l]; break;
+		case UP: plan_conv(m, m->up[s.index], s.name, ch, D[l], H[l], W[l], 1, ch != D[l]); ch = D[l]; break;   // (:1131,1141,1151: only where the widths differ)
+		case CONCAT: ch *= 2; break;
+		case OUT_CONV: plan_conv(m, m->outc, s.name, ch, cfg->in_channels, H[l], W[l], 1); break;
+		case RESIZE: case OUT_NORM: break;
+		}
+	}
 
 	auto fail = [&](bla_status s) { (void)bla_unet_destroy(m); return s; };
-	if ((st = dalloc(m, &m->params, m->count)) || (st = dalloc(m, &m->grads, m->count))) return fail(st);
-	BLA_HIP(hipMemsetAsync(m->params, 0, m->count * sizeof(float), ctx().stream));
-	BLA_HIP(hipMemsetAsync(m->grads, 0, m->count * sizeof(float), ctx().stream));
-	size_t max_act = 0, max_s = 0, max_flip = 0, max_cout_hw = 0, max_cin_hw = 0, max_cd = 1, max_cout = 1;
+	if ((st = dalloc_zeroed(m, &m->params, m->count)) || (st = dalloc_zeroed(m, &m->grads, m->count))) return fail(st);
+	size_t max_act = 0, max_s = 0, max_flip = 0, max_cout_hw = 0, max_cin_hw = 0, max_cd = 1;
 	for (Res& r : m->res) {
-		if ((st = alloc_res(m, r))) return fail(st);
+		if ((st = m->stack->alloc_block(m, r))) return fail(st);
+		const float* P = m->params; float* G = m->grads;
+		r.p = {P + r.conv1, P + r.conv2, P + r.tw, P + r.tb, r.res != kNone ? P + r.res : nullptr};
+		r.g = {G + r.conv1, G + r.conv2, G + r.tw, G + r.tb, r.res != kNone ? G + r.res : nullptr};
 		const size_t hw = (size_t)r.h * r.w * B;
 		max_act = std::max(max_act, (size_t)std::max(r.cin, r.cout) * hw);
-		max_cout_hw = std::max(max_cout_hw, r.cout * hw); max_cin_hw = std::max(max_cin_hw, r.cin * hw); max_cout = std::max(max_cout, (size_t)r.cout);
+		max_cout_hw = std::max(max_cout_hw, r.cout * hw); max_cin_hw = std::max(max_cin_hw, r.cin * hw); m->max_cout = std::max(m->max_cout, r.cout);
 		max_flip = std::max(max_flip, (size_t)r.cout * std::max(r.cin, r.cout) * cfg->kernel * cfg->kernel);
 	}
-	for (Att& a : m->att) {
-		const size_t s = (size_t)a.h * a.w;
-		if ((st = alloc_att_ws(m, a.fwd, s, cfg->key_dim)) || (st = dalloc(m, &a.out, B * a.c * s))) return fail(st);
-		max_s = std::max(max_s, s);
-		max_cd = std::max(max_cd, (size_t)a.c * cfg->key_dim);
-	}
-	for (int i = 0; i < 3; i++) {
-		Conv& c = m->down[i];
-		if ((st = dalloc(m, &c.out, B * c.cout * H[i + 1] * W[i + 1]))) return fail(st);
-		max_flip = std::max(max_flip, (size_t)c.cout * c.cin * c.k * c.k);
-		Conv& u = m->up[i];
-		if ((st = dalloc(m, &m->nn[i], B * u.cin * u.h * u.w))) return fail(st);
-		if (u.present) {
-			if ((st = dalloc(m, &u.out, B * u.cout * u.h * u.w))) return fail(st);
-			max_flip = std::max(max_flip, (size_t)u.cout * u.cin * u.k * u.k);
+	// the other steps' buffers, and every step's input, output and skip: a step reads what the step before it wrote
+	float* prev = nullptr;   // the model's input
+	for (Step& s : m->steps) {
+		const int l = s.level;
+		const size_t n = B * level_floats(m, l);   // a map of the level's own width
+		s.in = prev;
+		switch (s.kind) {
+		case RES: s.out = m->res[s.index].result; break;
+		case ATT: {
+			Att& a = m->att[s.index];
+			const size_t sp = (size_t)a.h * a.w;
+			if ((st = alloc_att_ws(m, a.fwd, sp, cfg->key_dim)) || (st = dalloc(m, &a.out, B * a.c * sp))) return fail(st);
+			max_s = std::max(max_s, sp); max_cd = std::max(max_cd, (size_t)a.c * cfg->key_dim);
+			s.out = a.out;
+			break;
 		}
-		max_act = std::max(max_act, B * u.cin * u.h * u.w);
+		case DOWN: case UP: case OUT_CONV: {
+			Conv& k = conv_of(m, s);
+			if (k.present && (st = dalloc(m, &k.out, B * k.cout * H[l] * W[l]))) return fail(st);
+			if (k.present) max_flip = std::max(max_flip, (size_t)k.cout * k.cin * k.k * k.k);
+			s.out = k.present ? k.out : prev;   // an absent up-convolution passes the resized map on
+			break;
+		}
+		case RESIZE:   // (as wide as the input of the up-convolution behind it)
+			if ((st = dalloc(m, &s.out, B * m->up[s.index].cin * H[l] * W[l]))) return fail(st);
+			max_act = std::max(max_act, B * m->up[s.index].cin * H[l] * W[l]);
+			break;
+		case CONCAT:
+			if ((st = dalloc(m, &s.out, 2 * n)) || (st = dalloc(m, &m->gskip[s.index], n))) return fail(st);
+			max_act = std::max(max_act, 2 * n);
+			for (const Step& t : m->steps) if (t.tap == s.index) s.skip = t.out;   // (tapped further up: resolved already)
+			break;
+		case OUT_NORM: {
+			const int groups = (D[l] + cfg->group_size - 1) / cfg->group_size * batch;
+			if ((st = dalloc(m, &s.out, n)) || (st = dalloc(m, &m->out_mu, groups)) || (st = dalloc(m, &m->out_sd, groups))) return fail(st);
+			break;
+		}
+		}
+		prev = s.out;
 	}
-	const int stage_dim[4] = {D[3], D[2], D[1], D[0]}, stage_res[4] = {3, 2, 1, 0};
-	for (int i = 0; i < 4; i++) {
-		const size_t n = B * stage_dim[i] * H[stage_res[i]] * W[stage_res[i]];
-		if ((st = dalloc(m, &m->cat[i], 2 * n)) || (st = dalloc(m, &m->gskip[i], n))) return fail(st);
-		max_act = std::max(max_act, 2 * n);
-	}
-	const size_t hw0 = (size_t)H[0] * W[0] * B;
-	const int g0 = (D[0] + cfg->group_size - 1) / cfg->group_size * batch;
-	if ((st = dalloc(m, &m->outc.out, cfg->in_channels * hw0)) || (st = dalloc(m, &m->out_relu, D[0] * hw0)) || (st = dalloc(m, &m->out_mu, g0)) ||
-	    (st = dalloc(m, &m->out_sd, g0)))
-		return fail(st);
-	max_flip = std::max(max_flip, (size_t)cfg->in_channels * D[0] * cfg->kernel * cfg->kernel);
 	static const bool side_on = [] { const char* e = getenv("BLA_UNET_SIDE"); return !(e && e[0] == '0'); }();
-	m->side = side_on && !bf16 && batch > 1 && 48 * max_act * sizeof(float) <= ((size_t)16 << 30);   // (the write-once pool: at most 16 GiB of it -- beyond that, one stream and three rotating buffers; bf16 products: one stream)
+	m->side = side_on && !bf16 && batch > 1 && kGradPool * max_act * sizeof(float) <= ((size_t)16 << 30);   // (the write-once pool: at most 16 GiB of it -- beyond that, one stream and three rotating buffers; bf16 products: one stream)
 	if (m->side) {
-		for (int i = 0; i < 48; i++) { float* q; if ((st = dalloc(m, &q, max_act))) return fail(st); m->gpool.push_back(q); }
+		if (backward_writes(m) > kGradPool) {   // a buffer taken twice in a pass would be overwritten under the side lane's reads
+			set_error("bla_unet_create: a backward pass writes %zu gradient buffers, the side lane's pool holds %zu", backward_writes(m), kGradPool);
+			return fail(BLA_ERR_INVALID);
+		}
+		for (size_t i = 0; i < kGradPool; i++) { float* q; if ((st = dalloc(m, &q, max_act))) return fail(st); m->gpool.push_back(q); }
 		for (Res& r : m->res) if ((st = dalloc(m, &r.pads.g_out_b, (size_t)r.cout * r.h * r.w * B))) return fail(st);
 	}
-	if ((st = dalloc(m, &m->t1, max_act)) || (st = dalloc(m, &m->t2, max_act)) || (st = dalloc(m, &m->t3, max_act)) || (st = dalloc(m, &m->sc.g_out_a, max_cout_hw)) ||
+	if ((st = dalloc(m, &m->ring[0], max_act)) || (st = dalloc(m, &m->ring[1], max_act)) || (st = dalloc(m, &m->ring[2], max_act)) || (st = dalloc(m, &m->sc.g_out_a, max_cout_hw)) ||
 	    (st = dalloc(m, &m->sc.g_out_b, max_cout_hw)) || (st = dalloc(m, &m->sc.g_in, max_cin_hw)) || (st = dalloc(m, &m->sc.flip, max_flip)) ||
-	    (st = alloc_att_ws(m, m->agrad, max_s, cfg->key_dim)) || (st = dalloc(m, &m->dtb, B * max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
+	    (st = alloc_att_ws(m, m->agrad, max_s, cfg->key_dim)) || (st = dalloc(m, &m->dtb, B * m->max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
 		return fail(st);
-	void* z = nullptr;
-	const size_t zero_bytes = m->drop_count ? B * m->drop_count : 1;
-	BLA_HIP(hipMalloc(&z, zero_bytes));
-	m->owned.push_back(z);
-	m->zero_drop = (unsigned char*)z;
-	BLA_HIP(hipMemsetAsync(z, 0, zero_bytes, ctx().stream));
-	if (cfg->time_dim <= 1024) {   // the 18 time-embedding projections (and, for a batch, their gradients) as one launch each way (eight embedding rows in LDS): the jobs' addresses are fixed from here on
+	if ((st = dalloc_zeroed(m, &m->zero_drop, B * m->drop_count))) return fail(st);
+	{   // the 18 time-embedding projections (and, for a batch, their gradients) as one launch each way (eight embedding rows in LDS), and the embedding gradient's
+		// table (every configuration): the jobs' addresses are fixed from here on.  One table serves both wherever the backward pass leaves the per-image channel
+		// sums in r.dtb; the fp32 single-image model leaves them in the time-bias gradient (a single image's channel sums ARE that gradient)
 		TimeJob jobs[18];
 		for (int i = 0; i < 18; i++) {
 			const Res& r = m->res[i];
-			jobs[i] = TimeJob{m->params + r.tw, m->params + r.tb, r.ws.tdense, r.dtb, m->grads + r.tw, m->grads + r.tb, r.cout};
+			jobs[i] = TimeJob{r.p.time_w, r.p.time_b, r.ws.tdense, r.dtb, r.g.time_w, r.g.time_b, r.cout};
 		}
-		void* tj = nullptr;
-		BLA_HIP(hipMalloc(&tj, sizeof jobs));
-		m->owned.push_back(tj);
-		m->time_jobs = (TimeJob*)tj;
-		BLA_HIP(hipMemcpy(tj, jobs, sizeof jobs, hipMemcpyHostToDevice));
-	}
-	{   // the embedding gradient's table: every configuration (the backward pass leaves the per-image channel sums in r.dtb, or at B = 1 in the time-bias gradient)
-		TimeJob jobs[18];
-		for (int i = 0; i < 18; i++) {
-			const Res& r = m->res[i];
-			jobs[i] = TimeJob{m->params + r.tw, m->params + r.tb, r.ws.tdense, batch > 1 || bf16 ? r.dtb : m->grads + r.tb, m->grads + r.tw, m->grads + r.tb, r.cout};
-		}
-		void* ej = nullptr;
-		BLA_HIP(hipMalloc(&ej, sizeof jobs));
-		m->owned.push_back(ej);
-		m->emb_jobs = (TimeJob*)ej;
-		BLA_HIP(hipMemcpy(ej, jobs, sizeof jobs, hipMemcpyHostToDevice));
+		if (cfg->time_dim <= 1024 && (st = upload_table(m, jobs, 18, &m->time_jobs))) return fail(st);
+		const bool sums_in_dtb = batch > 1 || bf16;
+		m->defer_time_grads = sums_in_dtb && m->time_jobs;
+		m->emb_jobs = m->time_jobs;
+		if (!sums_in_dtb) for (int i = 0; i < 18; i++) jobs[i].dtb = m->res[i].g.time_b;
+		if ((!sums_in_dtb || !m->time_jobs) && (st = upload_table(m, jobs, 18, &m->emb_jobs))) return fail(st);
 	}
 	static const bool prep_on = [] { const char* e = getenv("BLA_UNET_PREP"); return !(e && e[0] == '0'); }();
-	if (bf16) {
-		// One table launch at the head of each pass writes every bf16 kernel matrix of that pass into a matrix the model owns: the forward set is
-		// every convolution, the data-gradient set the same minus block 0's conv1 (nothing consumes the gradient of the image; its residual 1 x 1 likewise).
-		// BLA_UNET_BF16_PREP=0, read HERE at every create call: no tables, every composition prepares its own matrix in the workspace -- the same bits.
-		const char* e = getenv("BLA_UNET_BF16_PREP");
-		if (!(e && e[0] == '0')) {
-			std::vector<bla_conv_bf16_prep_job> jf, jb;
-			auto add = [&](size_t kern_off, int k, int cin, int cout, bool dgrad, const uint16_t** dst_out) -> bla_status {
-				const int rows = dgrad ? cin : cout, ip = round8(dgrad ? cout : cin);
-				const size_t chunks = (size_t)rows * k * k * (ip / 8);
-				float* q = nullptr;
-				bla_status s2 = dalloc(m, &q, chunks * 4);      // 8 bf16 elements = 4 floats a chunk; hipMalloc: 16-byte aligned
-				if (s2) return s2;
-				(dgrad ? jb : jf).push_back(bla_conv_bf16_prep_job{m->params + kern_off, (uint16_t*)q, cout, cin, k, dgrad ? 1 : 0});
-				size_t& mx = dgrad ? m->prep16_max_bwd : m->prep16_max_fwd;
-				mx = std::max(mx, chunks);
-				*dst_out = (uint16_t*)q;
-				return BLA_OK;
-			};
-			for (int i = 0; i < 18; i++) {
-				Res& r = m->res[i];
-				if ((st = add(r.conv1, cfg->kernel, r.cin, r.cout, false, &r.prep16.k1_fwd)) || (st = add(r.conv2, cfg->kernel, r.cout, r.cout, false, &r.prep16.k2_fwd)) ||
-				    (st = add(r.conv2, cfg->kernel, r.cout, r.cout, true, &r.prep16.k2_bwd)))
-					return fail(st);
-				if (i != 0 && (st = add(r.conv1, cfg->kernel, r.cin, r.cout, true, &r.prep16.k1_bwd))) return fail(st);
-				if (r.res != kNone && ((st = add(r.res, 1, r.cin, r.cout, false, &r.prep16.res_fwd)) || (i != 0 && (st = add(r.res, 1, r.cin, r.cout, true, &r.prep16.res_bwd)))))
-					return fail(st);
-			}
-			auto add_conv = [&](Conv& c) -> bla_status {
-				if (!c.present) return BLA_OK;
-				bla_status s2 = add(c.kern, c.k, c.cin, c.cout, false, &c.prep16_fwd);
-				return s2 ? s2 : add(c.kern, c.k, c.cin, c.cout, true, &c.prep16_bwd);
-			};
-			for (int i = 0; i < 3; i++) if ((st = add_conv(m->down[i])) || (st = add_conv(m->up[i]))) return fail(st);
-			if ((st = add_conv(m->outc))) return fail(st);
-			auto upload = [&](const std::vector<bla_conv_bf16_prep_job>& v, bla_conv_bf16_prep_job** d, int* n) -> bla_status {
-				void* q = nullptr;
-				BLA_HIP(hipMalloc(&q, v.size() * sizeof(bla_conv_bf16_prep_job)));
-				m->owned.push_back(q);
-				BLA_HIP(hipMemcpy(q, v.data(), v.size() * sizeof(bla_conv_bf16_prep_job), hipMemcpyHostToDevice));
-				*d = (bla_conv_bf16_prep_job*)q;
-				*n = (int)v.size();
-				return BLA_OK;
-			};
-			if ((st = upload(jf, &m->prep16_fwd, &m->n_prep16_fwd)) || (st = upload(jb, &m->prep16_bwd, &m->n_prep16_bwd))) return fail(st);
-		}
-	} else if (batch > 1 && prep_on) {
-		// One launch at the head of forward() and one at the head of backward() put every convolution's kernels into the form its product reads (window order,
-		// flipped): 49 five-microsecond launches per pass become 2.  The parameters do not change inside a pass, so the prepared copies are valid for it.
-		std::vector<KernelPrepJob> jf, jb;
-		auto add = [&](size_t kern_off, int h, int w, int k, int cin, int cout, int stride, bool want_dgrad, const float** pf, const float** pb) -> bla_status {
-			const size_t n = (size_t)cout * cin * k * k;
-			const int mf = conv_kernel_prep_mode(batch, h, w, k, cin, cout, stride, false), mb = want_dgrad ? conv_kernel_prep_mode(batch, h, w, k, cin, cout, stride, true) : 0;
-			for (int which = 0; which < 2; which++) {
-				const int mode = which ? mb : mf;
-				if (!mode) continue;
-				float* dst;
-				bla_status s2 = dalloc(m, &dst, n);
-				if (s2) return s2;
-				(which ? jb : jf).push_back(KernelPrepJob{m->params + kern_off, dst, cout, cin, k, mode});
-				*(which ? pb : pf) = dst;
-				m->prep_max = std::max(m->prep_max, n);
-			}
-			return BLA_OK;
-		};
-		for (int i = 0; i < 18; i++) {
-			Res& r = m->res[i];
-			if ((st = add(r.conv1, r.h, r.w, cfg->kernel, r.cin, r.cout, 1, i != 0, &r.pads.k1_fwd, &r.pads.k1_bwd)) ||     // (block 0 forms no gradient of the image)
-			    (st = add(r.conv2, r.h, r.w, cfg->kernel, r.cout, r.cout, 1, true, &r.pads.k2_fwd, &r.pads.k2_bwd)))
-				return fail(st);
-		}
-		for (int i = 0; i < 3; i++)
-			if (m->up[i].present && (st = add(m->up[i].kern, m->up[i].h, m->up[i].w, m->up[i].k, m->up[i].cin, m->up[i].cout, 1, true, &m->up[i].prep_fwd, &m->up[i].prep_bwd))) return fail(st);
-		auto upload = [&](const std::vector<KernelPrepJob>& v, KernelPrepJob** d, int* n) -> bla_status {
-			*n = (int)v.size();
-			if (v.empty()) return BLA_OK;
-			void* q = nullptr;
-			BLA_HIP(hipMalloc(&q, v.size() * sizeof(KernelPrepJob)));
-			m->owned.push_back(q);
-			BLA_HIP(hipMemcpy(q, v.data(), v.size() * sizeof(KernelPrepJob), hipMemcpyHostToDevice));
-			*d = (KernelPrepJob*)q;
-			return BLA_OK;
-		};
-		if ((st = upload(jf, &m->prep_fwd, &m->n_prep_fwd)) || (st = upload(jb, &m->prep_bwd, &m->n_prep_bwd))) return fail(st);
-	}
+	if ((bf16 || (batch > 1 && prep_on)) && (st = m->stack->plan_tables(m))) return fail(st);
 	BLA_HIP(hipStreamSynchronize(ctx().stream));
 	*out = m;
 	return BLA_OK;
@@ -625,83 +739,33 @@ bla_status bla_unet_forward_f32(bla_unet* m, void* stream, const float* d_x, con
 	if (st) return st;
 	BLA_REQUIRE(m && d_x && d_time_embedding, BLA_ERR_INVALID, "null argument");
 	const bla_unet_config& c = m->cfg;
-	const int* D = c.dims; const int* H = m->H; const int* W = m->W;
-	const float* P = m->params;
+	const int* H = m->H; const int* W = m->W;
 	const int B = m->batch;
-	const bool bf16 = m->products == BLA_UNET_PRODUCTS_BF16;
 	hipStream_t s = pick_stream(stream);
-	m->last_x = d_x; m->last_temb = d_time_embedding; m->last_drop = d_drop;
+	m->last_x = d_x; m->last_temb = d_time_embedding;
 	m->have_grads = false;
-	auto res = [&](int i, const float* in) -> bla_status {
-		Res& r = m->res[i];
-		bla_resnet_params p = {P + r.conv1, P + r.conv2, P + r.tw, P + r.tb, r.res != kNone ? P + r.res : nullptr};
-		// the dropout decisions: block by block in forward order, inside a block image by image
-		if (bf16)
-			return resnet_forward_bf16(stream, B, in, d_time_embedding, &p, (d_drop ? d_drop : m->zero_drop) + r.drop_off * B, &r.ws, r.result, r.h, r.w, r.cin, r.cout,
-			                           c.kernel, c.time_dim, c.group_size, &r.maps, m->time_jobs ? RESNET_TDENSE_READY : 0, &r.prep16);
-		return resnet_forward_batched(stream, B, in, d_time_embedding, &p, (d_drop ? d_drop : m->zero_drop) + r.drop_off * B, &r.ws, r.result, r.h, r.w, r.cin,
-		                              r.cout, c.kernel, c.time_dim, c.group_size, m->time_jobs ? RESNET_TDENSE_READY : 0, B > 1 ? &r.pads : nullptr);
-	};
 	if (m->time_jobs) {   // every block's time-embedding projection depends on the embedding alone: one launch for the 18 of them
-		int max_cout = 0;
-		for (int i = 0; i < 18; i++) max_cout = std::max(max_cout, m->res[i].cout);
-		hipLaunchKernelGGL(time_dense_all_kernel, dim3(18, (unsigned)((B + 7) / 8), (unsigned)((max_cout + 63) / 64)), dim3(256),
+		hipLaunchKernelGGL(time_dense_all_kernel, dim3(18, (unsigned)((B + 7) / 8), (unsigned)((m->max_cout + 63) / 64)), dim3(256),
 		                   ((size_t)8 * c.time_dim + 4 * 8 * 64) * sizeof(float), s, m->time_jobs, d_time_embedding, B, c.time_dim);
 		BLA_HIP(hipGetLastError());
 	}
-	auto att = [&](int i, const float* in) -> bla_status {
-		Att& a = m->att[i];
-		if (m->attention == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(a.c, a.h * a.w, c.key_dim))
-			return bla_attention_forward_batched_bf16(stream, B, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, c.key_dim);
-		return bla_attention_forward_batched_f32(stream, B, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, c.key_dim);
-	};
-	auto conv = [&](Conv& k, const float* in) -> bla_status {
-		if (bf16) return conv2d_forward_as_bf16(stream, in, P + k.kern, k.out, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, 0, k.prep16_fwd);
-		return conv2d_forward_epilogue(stream, in, P + k.kern, k.out, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, nullptr, nullptr, B, 0, nullptr, k.prep_fwd);
-	};
 	if (m->n_prep_fwd) { st = conv_prepare_kernels(stream, m->prep_fwd, m->n_prep_fwd, m->prep_max); if (st) return st; }
 	if (m->n_prep16_fwd) { st = bla_conv_bf16_prepare_kernels_table(stream, m->prep16_fwd, m->n_prep16_fwd, m->prep16_max_fwd); if (st) return st; }
-	auto concat = [&](int stage, const float* a, const float* skip, size_t n) -> bla_status {   // _concat_skip, :1088-1097 (n: floats per image and half)
-		if (n % 4 == 0 && ((uintptr_t)a | (uintptr_t)skip | (uintptr_t)m->cat[stage]) % 16 == 0)
-			hipLaunchKernelGGL(unet_concat4_kernel, dim3(grid_of(n / 2 * B)), dim3(256), 0, s, (const float4*)a, (const float4*)skip, (float4*)m->cat[stage], n / 4, n / 2 * B);
-		else hipLaunchKernelGGL(unet_concat_kernel, dim3(grid_of(2 * n * B)), dim3(256), 0, s, a, skip, m->cat[stage], n, 2 * n * B);
-		BLA_HIP(hipGetLastError());
-		return BLA_OK;
-	};
-	auto upsample = [&](int i, const float* in, const float** next) -> bla_status {   // _nearest_neighbours (+ the optional convolution), :1125-1131
-		Conv& u = m->up[i];
-		bla_status s2 = bla_nearest_neighbours_f32(stream, in, m->nn[i], B * u.cin, H[3 - i], W[3 - i], u.h, u.w, 2);
-		*next = m->nn[i];
-		if (!s2 && u.present) { s2 = conv(u, m->nn[i]); *next = u.out; }
-		return s2;
-	};
-#define TRY(x) do { st = (x); if (st) return st; } while (0)
-	// down
-	TRY(res(0, d_x)); TRY(res(1, m->res[0].result));
-	TRY(conv(m->down[0], m->res[1].result));
-	TRY(res(2, m->down[0].out)); TRY(att(0, m->res[2].result)); TRY(res(3, m->att[0].out)); TRY(att(1, m->res[3].result));
-	TRY(conv(m->down[1], m->att[1].out));
-	TRY(res(4, m->down[1].out)); TRY(res(5, m->res[4].result));
-	TRY(conv(m->down[2], m->res[5].result));
-	TRY(res(6, m->down[2].out)); TRY(res(7, m->res[6].result));
-	// mid
-	TRY(res(8, m->res[7].result)); TRY(att(2, m->res[8].result)); TRY(res(9, m->att[2].out));
-	// up
-	const float* next;
-	TRY(concat(0, m->res[9].result, m->res[7].result, (size_t)D[3] * H[3] * W[3]));
-	TRY(res(10, m->cat[0])); TRY(res(11, m->res[10].result));
-	TRY(upsample(0, m->res[11].result, &next));
-	TRY(concat(1, next, m->res[5].result, (size_t)D[2] * H[2] * W[2]));
-	TRY(res(12, m->cat[1])); TRY(res(13, m->res[12].result));
-	TRY(upsample(1, m->res[13].result, &next));
-	TRY(concat(2, next, m->res[3].result, (size_t)D[1] * H[1] * W[1]));
-	TRY(res(14, m->cat[2])); TRY(att(3, m->res[14].result)); TRY(res(15, m->att[3].out)); TRY(att(4, m->res[15].result));
-	TRY(upsample(2, m->att[4].out, &next));
-	TRY(concat(3, next, m->res[1].result, (size_t)D[0] * H[0] * W[0]));
-	TRY(res(16, m->cat[3])); TRY(res(17, m->res[16].result));
-	// output, :1163-1165
-	TRY(bla_group_norm_relu_batched_f32(stream, B, m->res[17].result, m->out_relu, m->out_sd, m->out_mu, D[0], c.group_size, H[0] * W[0]));
-	TRY(conv(m->outc, m->out_relu));
+	const unsigned char* drop = d_drop ? d_drop : m->zero_drop;   // the dropout decisions: block by block in forward order, inside a block image by image
+	for (const Step& t : m->steps) {
+		if (!step_runs(m, t)) continue;
+		const float* in = t.in ? t.in : d_x;
+		const int l = t.level;
+		switch (t.kind) {
+		case RES: st = m->stack->block_forward(m, stream, m->res[t.index], in, d_time_embedding, drop + m->res[t.index].drop_off * B); break;
+		case ATT: st = att_forward(m, stream, m->att[t.index], in); break;
+		case DOWN: case UP: case OUT_CONV: st = m->stack->conv_forward(m, stream, conv_of(m, t), in); break;
+		case RESIZE: st = bla_nearest_neighbours_f32(stream, in, t.out, B * m->up[t.index].cin, H[l + 1], W[l + 1], H[l], W[l], 2); break;   // :1125-1131
+		case CONCAT: st = concat(m, s, t); break;
+		case OUT_NORM: st = bla_group_norm_relu_batched_f32(stream, B, in, t.out, m->out_sd, m->out_mu, c.dims[l], c.group_size, H[l] * W[l]); break;
+		}
+		if (st) return st;
+	}
 	return BLA_OK;
 }
 
@@ -714,122 +778,52 @@ static bla_status unet_backward(bla_unet* m, void* stream, const float* d_noise,
 	BLA_REQUIRE(m && (d_noise || d_del_y), BLA_ERR_INVALID, "null argument");
 	BLA_REQUIRE(m->last_x, BLA_ERR_INVALID, "bla_unet_forward_f32 has not run");
 	const bla_unet_config& c = m->cfg;
-	const int* D = c.dims; const int* H = m->H; const int* W = m->W;
-	const float* P = m->params; float* G = m->grads;
-	const float* temb = m->last_temb;
+	const int* H = m->H; const int* W = m->W;
 	const int B = m->batch;
-	const bool bf16 = m->products == BLA_UNET_PRODUCTS_BF16;
 	hipStream_t s = pick_stream(stream);
-	// ResNet block i: gradient `g` of its result -> `out` (gradient of its input `x`)
-	auto res = [&](int i, const float* g, const float* x, float* out) -> bla_status {
-		Res& r = m->res[i];
-		bla_resnet_params p = {P + r.conv1, P + r.conv2, P + r.tw, P + r.tb, r.res != kNone ? P + r.res : nullptr};
-		bla_resnet_grads gr = {G + r.conv1, G + r.conv2, G + r.tw, G + r.tb, r.res != kNone ? G + r.res : nullptr};
-		if (bf16)   // (the channel sums go to r.dtb at every batch: bla_unet_embedding_grad_f32 reads them there)
-			return resnet_backward_bf16(stream, B, g, x, temb, &p, &r.ws, &gr, &m->sc, r.dtb, out, r.h, r.w, r.cin, r.cout, c.kernel, c.time_dim, c.group_size, &r.maps, 0,
-			                            m->time_jobs ? RESNET_DEFER_TIME_GRADS : 0, &r.prep16);
-		return resnet_backward_batched(stream, B, g, x, temb, &p, &r.ws, &gr, &m->sc, B > 1 ? r.dtb : m->dtb, out, r.h, r.w, r.cin, r.cout, c.kernel, c.time_dim,
-		                               c.group_size, (B > 1 && m->time_jobs ? RESNET_DEFER_TIME_GRADS : 0) | (m->side ? RESNET_WGRAD_SIDE : 0), B > 1 ? &r.pads : nullptr);
-	};
-	auto att = [&](int i, const float* g, const float* x, float* out) -> bla_status {
-		Att& a = m->att[i];
-		if (m->attention == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(a.c, a.h * a.w, c.key_dim))
-			return bla_attention_backward_batched_bf16(stream, B, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk,
-			                                           G + a.wv, G + a.wo, out, a.c, a.h * a.w, c.key_dim);
-		return bla_attention_backward_batched_f32(stream, B, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv,
-		                                          G + a.wo, out, a.c, a.h * a.w, c.key_dim, 0);
-	};
-	auto conv = [&](Conv& k, const float* g, const float* x, float* out) -> bla_status {
-		if (bf16) return conv2d_backward_gathered_as_bf16(stream, g, x, P + k.kern, G + k.kern, out, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, 0, k.prep16_bwd);
-		if (m->side) {      // weight gradient on the side lane (g and x stay intact until the join below), data gradient here
-			hipStream_t lane;
-			bla_status s2 = side_lane_fork(s, &lane);
-			if (s2) return s2;
-			s2 = conv2d_backward_batched(lane, g, x, P + k.kern, G + k.kern, nullptr, m->sc.flip, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, nullptr);
-			side_lane_done();
-			if (s2) return s2;
-			return conv2d_backward_batched(stream, g, x, P + k.kern, nullptr, out, m->sc.flip, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, k.prep_bwd);
-		}
-		return conv2d_backward_batched(stream, g, x, P + k.kern, G + k.kern, out, m->sc.flip, B, k.h, k.w, k.k, k.cin, k.cout, k.stride, nullptr, k.prep_bwd);
-	};
 	if (m->n_prep_bwd) { st = conv_prepare_kernels(stream, m->prep_bwd, m->n_prep_bwd, m->prep_max); if (st) return st; }
 	if (m->n_prep16_bwd) { st = bla_conv_bf16_prepare_kernels_table(stream, m->prep16_bwd, m->n_prep16_bwd, m->prep16_max_bwd); if (st) return st; }
-	// up-sampling stage i backwards: gradient of (the optional convolution's output | the resized map) -> gradient of the map before resizing;
-	// g, tmp and out are three different buffers
-	auto upsample = [&](int i, const float* g, float* tmp, float* out) -> bla_status {
-		Conv& u = m->up[i];
-		const float* gn = g;
-		if (u.present) { bla_status s2 = conv(u, g, m->nn[i], tmp); if (s2) return s2; gn = tmp; }
-		return bla_nearest_neighbours_ddx_f32(stream, gn, out, B * u.cin, u.h, u.w, H[3 - i], W[3 - i], 2);
-	};
-	// _split_concat, :1339-1349: the first half of a concatenation's gradient goes on along the main path, the second is the skip connection's
-	auto split = [&](int stage, const float* g_cat, float* g_main, size_t n) -> bla_status {
-		if (n % 4 == 0 && ((uintptr_t)g_cat | (uintptr_t)g_main | (uintptr_t)m->gskip[stage]) % 16 == 0)
-			hipLaunchKernelGGL(unet_split4_kernel, dim3(grid_of(n / 2 * B)), dim3(256), 0, s, (const float4*)g_cat, (float4*)g_main, (float4*)m->gskip[stage], n / 4, n / 2 * B);
-		else hipLaunchKernelGGL(unet_split_kernel, dim3(grid_of(2 * n * B)), dim3(256), 0, s, g_cat, g_main, m->gskip[stage], n, 2 * n * B);
-		BLA_HIP(hipGetLastError());
-		return BLA_OK;
-	};
-	// three rotating gradient buffers: a block never writes the buffer it reads.  With the weight gradients on the side lane every WRITE takes a fresh buffer
-	// from the pool instead (F(x) below), so what the lane still reads -- the gradient a block or convolution came in with -- is never overwritten in this pass
-	float *a = m->t1, *b = m->t2, *cbuf = m->t3;
-	size_t gp = 0;
-	auto F = [&](float*& p) -> float* { if (m->side) p = m->gpool[gp++ % m->gpool.size()]; return p; };
-	const size_t hw0 = (size_t)H[0] * W[0];
-	const size_t n0 = (size_t)D[0] * hw0, n1 = (size_t)D[1] * H[1] * W[1], n2 = (size_t)D[2] * H[2] * W[2], n3 = (size_t)D[3] * H[3] * W[3];
-	const int nout = (int)(c.in_channels * hw0 * B);
-	const float* seed = d_del_y;   // the side lane reads it until the join below; the caller's buffer is never written
+	// Every gradient a step WRITES takes the next buffer: of three in rotation (a step reads the one written last and writes one, so never the one it reads),
+	// or, with the weight gradients on the side lane, of the write-once pool -- what the lane still reads, the gradient a block or convolution came in with, is
+	// never overwritten in this pass (create has counted the writes: backward_writes(m) <= kGradPool)
+	size_t written = 0;
+	auto next = [&]() -> float* { float* p = m->side ? m->gpool[written] : m->ring[written % 3]; written++; return p; };
+	const int nout = (int)((size_t)c.in_channels * H[0] * W[0] * B);
+	float* g = const_cast<float*>(d_del_y);   // the gradient that arrives at the step in hand (the caller's buffer: the last step only reads it, also from the side lane)
 	if (d_noise) {
-		hipLaunchKernelGGL(unet_loss_grad_kernel, dim3(grid_of((size_t)nout)), dim3(256), 0, s, m->outc.out, d_noise, F(a), nout);   // :1353-1364
-		BLA_HIP(hipGetLastError());
-		seed = a;
-	}
-	// output processing, :1367-1369: convolution, ReLU gate, group norm
-	TRY(conv(m->outc, seed, m->out_relu, F(b)));
-	TRY(bla_group_norm_ddx_gated_batched_f32(stream, B, b, F(a), m->res[17].result, m->out_mu, m->out_sd, D[0], c.group_size, (int)hw0, m->out_relu, nullptr));
-	// fourth up-sampling stage, :1372-1374
-	TRY(res(17, a, m->res[16].result, F(b))); TRY(res(16, b, m->cat[3], F(a)));
-	TRY(split(3, a, F(b), n0));
-	// third, :1377-1383 (resize and the optional convolution, then attention 2, ResNet 2, attention 1, ResNet 1)
-	TRY(upsample(2, b, F(a), F(cbuf)));
-	TRY(att(4, cbuf, m->res[15].result, F(a))); TRY(res(15, a, m->att[3].out, F(b))); TRY(att(3, b, m->res[14].result, F(a))); TRY(res(14, a, m->cat[2], F(b)));
-	TRY(split(2, b, F(a), n1));
-	// second, :1386-1390
-	TRY(upsample(1, a, F(b), F(cbuf)));
-	TRY(res(13, cbuf, m->res[12].result, F(a))); TRY(res(12, a, m->cat[1], F(b)));
-	TRY(split(1, b, F(a), n2));
-	// first, :1393-1397
-	TRY(upsample(0, a, F(b), F(cbuf)));
-	TRY(res(11, cbuf, m->res[10].result, F(a))); TRY(res(10, a, m->cat[0], F(b)));
-	TRY(split(0, b, F(a), n3));
-	// middle, :1400-1402
-	TRY(res(9, a, m->att[2].out, F(b))); TRY(att(2, b, m->res[8].result, F(a))); TRY(res(8, a, m->res[7].result, F(b)));
-	// fourth down-sampling stage, :1405-1409: the skip's gradient joins the main path's
-	TRY(bla_add_f32(stream, b, m->gskip[0], n3 * B));
-	TRY(res(7, b, m->res[6].result, F(a))); TRY(res(6, a, m->down[2].out, F(b)));
-	// third, :1412-1417
-	TRY(conv(m->down[2], b, m->res[5].result, F(a)));
-	TRY(bla_add_f32(stream, a, m->gskip[1], n2 * B));
-	TRY(res(5, a, m->res[4].result, F(b))); TRY(res(4, b, m->down[1].out, F(a)));
-	// second, :1420-1427
-	TRY(conv(m->down[1], a, m->att[1].out, F(b)));
-	TRY(att(1, b, m->res[3].result, F(a)));
-	TRY(bla_add_f32(stream, a, m->gskip[2], n1 * B));
-	TRY(res(3, a, m->att[0].out, F(b))); TRY(att(0, b, m->res[2].result, F(a))); TRY(res(2, a, m->down[0].out, F(b)));
-	// first, :1430-1435
-	TRY(conv(m->down[0], b, m->res[1].result, F(a)));
-	TRY(bla_add_f32(stream, a, m->gskip[3], n0 * B));
-	TRY(res(1, a, m->res[0].result, F(b)));
-	TRY(res(0, b, m->last_x, nullptr));   // nothing consumes the gradient of the image: the first block forms its weight gradients only
-	if ((B > 1 || bf16) && m->time_jobs) {   // the 18 blocks' time-weight / time-bias gradients from the channel sums each block left behind (:1191-1199)
-		hipLaunchKernelGGL(time_grads_all_kernel, dim3(18, (unsigned)((c.time_dim + 7) / 8)), dim3(256), 0, s, m->time_jobs, temb, B, c.time_dim);
+		g = next();
+		hipLaunchKernelGGL(unet_loss_grad_kernel, dim3(grid_of((size_t)nout)), dim3(256), 0, s, m->outc.out, d_noise, g, nout);   // :1353-1364
 		BLA_HIP(hipGetLastError());
 	}
-	if (m->side) TRY(side_lane_join(s));      // the weight gradients are in when this stream moves on
+	for (size_t i = m->steps.size(); i-- > 0;) {
+		const Step& t = m->steps[i];
+		const int l = t.level;
+		// a tapped output: the skip connection's gradient (left behind by its CONCAT's split) joins the main path's before the step sees it (:1405-1435)
+		if (t.tap >= 0 && (st = bla_add_f32(stream, g, m->gskip[t.tap], level_floats(m, l) * B))) return st;
+		if (!step_runs(m, t)) continue;
+		const float* x = t.in ? t.in : m->last_x;   // the step's input in the forward pass
+		float* out = i ? next() : nullptr;          // nothing consumes the gradient of the image: the first block forms its weight gradients only
+		switch (t.kind) {
+		case RES: st = m->stack->block_backward(m, stream, m->res[t.index], g, x, out); break;
+		case ATT: st = att_backward(m, stream, m->att[t.index], g, x, out); break;
+		case DOWN: case UP: case OUT_CONV: st = m->stack->conv_backward(m, stream, conv_of(m, t), g, x, out); break;
+		case RESIZE: st = bla_nearest_neighbours_ddx_f32(stream, g, out, B * m->up[t.index].cin, H[l], W[l], H[l + 1], W[l + 1], 2); break;
+		case CONCAT: st = split(m, s, t, g, out); break;
+		case OUT_NORM:   // :1367-1369: the ReLU gate, then group norm
+			st = bla_group_norm_ddx_gated_batched_f32(stream, B, g, out, x, m->out_mu, m->out_sd, c.dims[l], c.group_size, H[l] * W[l], t.out, nullptr);
+			break;
+		}
+		if (st) return st;
+		g = out;
+	}
+	if (m->defer_time_grads) {   // the 18 blocks' time-weight / time-bias gradients from the channel sums each block left behind (:1191-1199)
+		hipLaunchKernelGGL(time_grads_all_kernel, dim3(18, (unsigned)((c.time_dim + 7) / 8)), dim3(256), 0, s, m->time_jobs, m->last_temb, B, c.time_dim);
+		BLA_HIP(hipGetLastError());
+	}
+	if (m->side && (st = side_lane_join(s))) return st;      // the weight gradients are in when this stream moves on
 	m->have_grads = true;
 	return BLA_OK;
 }
-#undef TRY
 
 bla_status bla_unet_backward_f32(bla_unet* m, void* stream, const float* d_noise) {
 	return unet_backward(m, stream, d_noise, nullptr);
