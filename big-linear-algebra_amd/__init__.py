@@ -15,7 +15,8 @@ from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilo
                      conv_bf16_prep_chunks, unet_create_mixed, unet_products, UNET_PRODUCTS_F32, UNET_PRODUCTS_BF16,
                      unet_set_attention, unet_attention, UNET_ATTENTION_F32, UNET_ATTENTION_BF16, attention_bf16_applies, attention_ws,
                      attention_forward_batched_bf16, attention_backward_batched_bf16, to_mxfp8, from_mxfp8, f32_to_mxfp8, mxfp8_to_f32,
-                     gemm_mxfp8, gemm_f32_as_mxfp8)
+                     gemm_mxfp8, gemm_f32_as_mxfp8, UNET_ATTENTION_BF16_ONLINE, attention_online_bf16_applies,
+                     attention_forward_batched_online_bf16, attention_backward_batched_online_bf16)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
@@ -29,4 +30,5 @@ __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Ep
            "conv_bf16_prepare_kernels_table", "conv_bf16_prep_chunks", "unet_create_mixed", "unet_products", "UNET_PRODUCTS_F32", "UNET_PRODUCTS_BF16",
            "unet_set_attention", "unet_attention", "UNET_ATTENTION_F32", "UNET_ATTENTION_BF16", "attention_bf16_applies", "attention_ws",
            "attention_forward_batched_bf16", "attention_backward_batched_bf16", "to_mxfp8", "from_mxfp8", "f32_to_mxfp8", "mxfp8_to_f32", "gemm_mxfp8",
-           "gemm_f32_as_mxfp8"]
+           "gemm_f32_as_mxfp8", "UNET_ATTENTION_BF16_ONLINE", "attention_online_bf16_applies", "attention_forward_batched_online_bf16",
+           "attention_backward_batched_online_bf16"]

@@ -16,62 +16,13 @@
 //
 // Launches: forward 2 (qkv, core); backward 3 (core: one workgroup per image; grads: del_X and the image's four weight-gradient partials, one wave per
 // 32 x 32 output tile; fold: the partials summed in image order).  Every sum has a fixed order: no atomics, the same bits on every run.
-#include "bla_internal.h"
-#include "bla_bf16_tile.h"
+#include "bla_attention_tile.h"
 #include <cmath>
 
 namespace bla {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-struct F4 { float x, y, z, w; };   // four floats at 4-byte alignment (the tensors are float-aligned, nothing more is asked of the caller)
-
-// Edges without branches: a fragment piece outside its operand is read from these zeros instead (the address is chosen, the load is unconditional), so
-// no address outside an operand is ever formed into a load and the kernels stay straight-line code between their barriers.
-__device__ float att_zeros[12];   // (zero-initialised, never written; not const, so that it lives in the same address space as the operands and the loads stay global)
-__device__ __forceinline__ F4 ld4(const float* p, bool ok) { return *(const F4*)(ok ? p : att_zeros); }
-__device__ __forceinline__ bf16x8 frag_pack(const F4& a, const F4& b) {
-	const u32x4 v = {pack2(a.x, a.y), pack2(a.z, a.w), pack2(b.x, b.y), pack2(b.z, b.w)};
-	return __builtin_bit_cast(bf16x8, v);
-}
-// k = j: p[0 .. 7]
-__device__ __forceinline__ bf16x8 frag_row8(const float* p, bool ok) { return frag_pack(ld4(p, ok), ld4(p + 4, ok)); }
-// k = j in permuted order: p[0 .. 3], p[8 .. 11]
-__device__ __forceinline__ bf16x8 frag_perm(const float* p, bool ok_lo, bool ok_hi) { return frag_pack(ld4(p, ok_lo), ld4(p + 8, ok_hi)); }
-// k = j down a column: p[j * stride]
-__device__ __forceinline__ bf16x8 frag_col8(const float* p, size_t stride, bool ok) {
-	float v[8];
-	p = ok ? p : att_zeros;
-	stride = ok ? stride : 0;
-#pragma unroll
-	for (int j = 0; j < 8; ++j) v[j] = p[j * stride];
-	const u32x4 u = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-	return __builtin_bit_cast(bf16x8, u);
-}
-// k = j down a column in permuted order: rows 0 .. 3 and 8 .. 11
-__device__ __forceinline__ bf16x8 frag_colperm(const float* p, size_t stride, bool ok_lo, bool ok_hi) {
-	float v[8];
-	const float *lo = ok_lo ? p : att_zeros, *hi = ok_hi ? p + 8 * stride : att_zeros;
-	const size_t sl = ok_lo ? stride : 0, sh = ok_hi ? stride : 0;
-#pragma unroll
-	for (int j = 0; j < 4; ++j) { v[j] = lo[j * sl]; v[4 + j] = hi[j * sh]; }
-	const u32x4 u = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-	return __builtin_bit_cast(bf16x8, u);
-}
-// registers 8 u .. 8 u + 7 of an accumulator tile: k = j stands for tile row perm(h, j, u)
-__device__ __forceinline__ bf16x8 frag_acc(const f32x16& a, int u) {
-	const u32x4 v = u == 0 ? u32x4{pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(a[4], a[5]), pack2(a[6], a[7])}
-	                       : u32x4{pack2(a[8], a[9]), pack2(a[10], a[11]), pack2(a[12], a[13]), pack2(a[14], a[15])};
-	return __builtin_bit_cast(bf16x8, v);
-}
-__device__ __forceinline__ f32x16 zero16() {
-	f32x16 z;
-#pragma unroll
-	for (int r = 0; r < 16; ++r) z[r] = 0.f;
-	return z;
-}
-__device__ __forceinline__ int acc_row(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }
-#define BLA_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
+// (the fragment readers -- ld4, frag_row8, frag_perm, frag_col8, frag_colperm, frag_acc -- are bla_attention_tile.h's, shared with the online block)
 
 // ---- qkv: Q | K | V = r(Z) . r([Wq | Wk | Wv]), Z = X^T ------------------------------------------------------------------------------------------
 // One wave per 32 rows of Z (four to a workgroup, independent).  A fragment: X[k][s0 + f] down the channels (a half-wave reads 128 contiguous bytes per
@@ -481,6 +432,26 @@ __global__ void __launch_bounds__(256) att_bf16_fold_kernel(const float* __restr
 }
 
 }  // namespace
+
+bla_status att_bf16_launch_qkv(hipStream_t hs, int batch, const float* x, const float* wq, const float* wk, const float* wv, float* q, float* k, float* v, int c, int s,
+                               int d) {
+	hipLaunchKernelGGL(att_bf16_qkv_kernel, dim3((s / 32 + 3) / 4, batch), dim3(256), 0, hs, x, wq, wk, wv, q, k, v, c, s, d);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status att_bf16_launch_grads_fold(hipStream_t hs, int batch, const float* dy, const float* x, const float* wq, const float* wk, const float* wv,
+                                      const float* attention, const float* gq, const float* gk, const float* gv, float* partials, float* del_wq, float* del_wk,
+                                      float* del_wv, float* del_w, float* dx, int c, int s, int d) {
+	const int nct = (c + 31) / 32, nst = s / 32, ndt = (d + 31) / 32;
+	hipLaunchKernelGGL(att_bf16_bwd_grads_kernel, dim3(nct * nst + 4 * nct * ndt, batch), dim3(64), 0, hs, dy, x, wq, wk, wv, attention, gq, gk, gv, partials, dx, c, s, d);
+	BLA_HIP(hipGetLastError());
+	const size_t cd = (size_t)c * d;
+	hipLaunchKernelGGL(att_bf16_fold_kernel, dim3((unsigned)((4 * cd + 255) / 256)), dim3(256), 0, hs, partials, del_wq, del_wk, del_wv, del_w, batch, cd);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
 }  // namespace bla
 
 using namespace bla;
@@ -500,8 +471,7 @@ bla_status bla_attention_forward_batched_bf16(void* stream, int batch, const flo
 	BLA_REQUIRE(d_x && d_wq && d_wk && d_wv && d_w && d_bias && d_out && ws && ws->q && ws->k && ws->v && ws->weights && ws->attention, BLA_ERR_INVALID, "null operand");
 	hipStream_t hs = pick_stream(stream);
 	const int nk = s / 32;
-	hipLaunchKernelGGL(att_bf16_qkv_kernel, dim3((nk + 3) / 4, batch), dim3(256), 0, hs, d_x, d_wq, d_wk, d_wv, ws->q, ws->k, ws->v, c, s, d);
-	BLA_HIP(hipGetLastError());
+	if ((st = att_bf16_launch_qkv(hs, batch, d_x, d_wq, d_wk, d_wv, ws->q, ws->k, ws->v, c, s, d))) return st;
 	const float inv = (float)(1.0 / sqrt((double)d));
 	hipLaunchKernelGGL(att_bf16_fwd_kernel, dim3(nk, batch), dim3(64), 0, hs, ws->q, ws->k, ws->v, d_w, d_bias, ws->weights, ws->attention, d_out, c, s, d, inv);
 	BLA_HIP(hipGetLastError());
@@ -531,14 +501,8 @@ bla_status bla_attention_backward_batched_bf16(void* stream, int batch, const fl
 	switch (s / 32) { BLA_ATT_CORE(1) BLA_ATT_CORE(2) BLA_ATT_CORE(3) BLA_ATT_CORE(4) BLA_ATT_CORE(5) BLA_ATT_CORE(6) BLA_ATT_CORE(7) BLA_ATT_CORE(8) }
 #undef BLA_ATT_CORE
 	BLA_HIP(hipGetLastError());
-	const int nct = (c + 31) / 32, nst = s / 32, ndt = (d + 31) / 32;
-	hipLaunchKernelGGL(att_bf16_bwd_grads_kernel, dim3(nct * nst + 4 * nct * ndt, batch), dim3(64), 0, hs, d_del_y, d_x, d_wq, d_wk, d_wv, fwd->attention, grad->q,
-	                   grad->k, grad->v, d_partials, d_del_x, c, s, d);
-	BLA_HIP(hipGetLastError());
-	const size_t cd = (size_t)c * d;
-	hipLaunchKernelGGL(att_bf16_fold_kernel, dim3((unsigned)((4 * cd + 255) / 256)), dim3(256), 0, hs, d_partials, d_del_wq, d_del_wk, d_del_wv, d_del_w, batch, cd);
-	BLA_HIP(hipGetLastError());
-	return BLA_OK;
+	return att_bf16_launch_grads_fold(hs, batch, d_del_y, d_x, d_wq, d_wk, d_wv, fwd->attention, grad->q, grad->k, grad->v, d_partials, d_del_wq, d_del_wk, d_del_wv,
+	                                  d_del_w, d_del_x, c, s, d);
 }
 
 }  // extern "C"

@@ -104,7 +104,7 @@ constexpr size_t kGradPool = 48;   // side lane: the write-once gradient buffers
 struct bla_unet {
 	bla_unet_config cfg;
 	int batch = 1;
-	int attention = BLA_UNET_ATTENTION_F32;   // BLA_UNET_ATTENTION_BF16: the attention blocks that qualify on bla_attention_{forward,backward}_batched_bf16
+	int attention = BLA_UNET_ATTENTION_F32;   // BLA_UNET_ATTENTION_BF16: the attention blocks that qualify on bla_attention_{forward,backward}_batched_bf16; _BF16_ONLINE: on the online-softmax entries (3.29)
 	int products = BLA_UNET_PRODUCTS_F32;   // BLA_UNET_PRODUCTS_BF16: the blocks and the stand-alone convolutions on the bf16 stack, one stream
 	const Stack* stack = nullptr;           // the calls of `products`
 	int H[4], W[4], max_cout = 1;           // the four resolutions; the widest block output
@@ -447,17 +447,21 @@ bla_status conv_backward_bf16(bla_unet* m, void* stream, const Conv& k, const fl
 }
 // attention: by the model's mode and the block's shape, asked at every call (bla_unet_set_attention may come after create)
 bool att_on_bf16(const bla_unet* m, const Att& a) { return m->attention == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(a.c, a.h * a.w, m->cfg.key_dim); }
+// (the online entries keep the row log-sum-exp in the first B S floats of the block's scores_raw and the row dots in agrad's: both are B S S floats)
+bool att_on_online(const bla_unet* m, const Att& a) {
+	return m->attention == BLA_UNET_ATTENTION_BF16_ONLINE && bla_attention_online_bf16_applies(a.c, a.h * a.w, m->cfg.key_dim);
+}
 bla_status att_forward(bla_unet* m, void* stream, Att& a, const float* in) {
 	const float* P = m->params;
-	return (att_on_bf16(m, a) ? bla_attention_forward_batched_bf16 : bla_attention_forward_batched_f32)(
+	return (att_on_online(m, a) ? bla_attention_forward_batched_online_bf16 : att_on_bf16(m, a) ? bla_attention_forward_batched_bf16 : bla_attention_forward_batched_f32)(
 		stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, m->cfg.key_dim);
 }
 bla_status att_backward(bla_unet* m, void* stream, Att& a, const float* g, const float* x, float* out) {
 	const float* P = m->params; float* G = m->grads;
 	const int d = m->cfg.key_dim;
-	if (att_on_bf16(m, a))
-		return bla_attention_backward_batched_bf16(stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk,
-		                                           G + a.wv, G + a.wo, out, a.c, a.h * a.w, d);
+	if (att_on_online(m, a) || att_on_bf16(m, a))
+		return (att_on_online(m, a) ? bla_attention_backward_batched_online_bf16 : bla_attention_backward_batched_bf16)(
+			stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv, G + a.wo, out, a.c, a.h * a.w, d);
 	return bla_attention_backward_batched_f32(stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv,
 	                                          G + a.wo, out, a.c, a.h * a.w, d, 0);
 }
@@ -576,7 +580,8 @@ int bla_unet_products(const bla_unet* m) { return m ? m->products : BLA_UNET_PRO
 int bla_unet_attention(const bla_unet* m) { return m ? m->attention : BLA_UNET_ATTENTION_F32; }
 
 bla_status bla_unet_set_attention(bla_unet* m, int mode) {
-	BLA_REQUIRE(mode == BLA_UNET_ATTENTION_F32 || mode == BLA_UNET_ATTENTION_BF16, BLA_ERR_INVALID, "bla_unet_set_attention: mode %d (BLA_UNET_ATTENTION_F32 or _BF16)", mode);
+	BLA_REQUIRE(mode == BLA_UNET_ATTENTION_F32 || mode == BLA_UNET_ATTENTION_BF16 || mode == BLA_UNET_ATTENTION_BF16_ONLINE, BLA_ERR_INVALID,
+	            "bla_unet_set_attention: mode %d (BLA_UNET_ATTENTION_F32, _BF16 or _BF16_ONLINE)", mode);
 	BLA_REQUIRE(m, BLA_ERR_INVALID, "null argument");
 	m->attention = mode;
 	return BLA_OK;

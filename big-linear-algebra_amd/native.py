@@ -156,6 +156,9 @@ SIGNATURES = {
     "bla_attention_forward_batched_f32": (_I, [_VP, _I] + [_VP] * 8 + [_I] * 3), "bla_attention_backward_batched_f32": (_I, [_VP, _I] + [_VP] * 14 + [_I] * 4),
     "bla_attention_bf16_applies": (_I, [_I] * 3),
     "bla_attention_forward_batched_bf16": (_I, [_VP, _I] + [_VP] * 8 + [_I] * 3), "bla_attention_backward_batched_bf16": (_I, [_VP, _I] + [_VP] * 14 + [_I] * 3),
+    "bla_attention_online_bf16_applies": (_I, [_I] * 3),
+    "bla_attention_forward_batched_online_bf16": (_I, [_VP, _I] + [_VP] * 8 + [_I] * 3),
+    "bla_attention_backward_batched_online_bf16": (_I, [_VP, _I] + [_VP] * 14 + [_I] * 3),
     "bla_unet_set_attention": (_I, [_VP, _I]), "bla_unet_attention": (_I, [_VP]),
     "bla_resnet_forward_batched_f32": (_I, [_VP, _I] + [_VP] * 6 + [_I] * 7), "bla_resnet_backward_batched_f32": (_I, [_VP, _I] + [_VP] * 9 + [_I] * 7),
     "bla_group_norm_relu_bf16_map": (_I, [_VP, _I, _VP] + [_I] * 4 + [_VP] * 4 + [C.POINTER(ConvBf16Map)]),
@@ -604,7 +607,7 @@ def unet_products(model):
     return lib().bla_unet_products(model)
 
 
-UNET_ATTENTION_F32, UNET_ATTENTION_BF16 = 0, 1
+UNET_ATTENTION_F32, UNET_ATTENTION_BF16, UNET_ATTENTION_BF16_ONLINE = 0, 1, 3   # a bit set: bit 0 bf16 products, bit 1 the online softmax; 2 does not exist
 
 
 def unet_set_attention(model, mode):
@@ -636,6 +639,23 @@ def attention_backward_batched_bf16(batch, del_y, x, wq, wk, wv, w, fwd, grad, p
     """bla_attention_backward_batched_bf16: grad needs q, k, v only; partials is [batch][4 c d] floats of scratch."""
     check(lib().bla_attention_backward_batched_bf16(stream, batch, _ptr(del_y), _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(w), C.byref(fwd), C.byref(grad),
                                                     _ptr(partials), _ptr(del_wq), _ptr(del_wk), _ptr(del_wv), _ptr(del_w), _ptr(del_x), c, s, d))
+
+
+def attention_online_bf16_applies(c, s, d):
+    """bla_attention_online_bf16_applies: host only, no device needed."""
+    return bool(lib().bla_attention_online_bf16_applies(c, s, d))
+
+
+def attention_forward_batched_online_bf16(batch, x, wq, wk, wv, w, bias, ws, out, c, s, d, stream=None):
+    """bla_attention_forward_batched_online_bf16: ws needs q, k, v, attention and scores_raw ([batch][s] floats: the row log-sum-exp)."""
+    check(lib().bla_attention_forward_batched_online_bf16(stream, batch, _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(w), _ptr(bias), C.byref(ws), _ptr(out), c, s, d))
+    return out
+
+
+def attention_backward_batched_online_bf16(batch, del_y, x, wq, wk, wv, w, fwd, grad, partials, del_wq, del_wk, del_wv, del_w, del_x, c, s, d, stream=None):
+    """bla_attention_backward_batched_online_bf16: grad needs q, k, v, attention (del_P) and scores_raw ([batch][s]: the row dots); partials [batch][4 c d]."""
+    check(lib().bla_attention_backward_batched_online_bf16(stream, batch, _ptr(del_y), _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(w), C.byref(fwd), C.byref(grad),
+                                                           _ptr(partials), _ptr(del_wq), _ptr(del_wk), _ptr(del_wv), _ptr(del_w), _ptr(del_x), c, s, d))
 
 
 def conv2d_gathered_bf16(a, rows, p, batch, hp, wp, cp, k, stride, ho, wo, out, ep_bias=None, ep_bias_stride=0, stream=None):

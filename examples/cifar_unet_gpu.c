@@ -414,13 +414,15 @@ static void products_from_env(void) {
 	else if (strcmp(v, "bf16") == 0) g_products = BLA_UNET_PRODUCTS_BF16;
 	else { fprintf(stderr, "BLA_UNET_PRODUCTS=%s: expected f32 or bf16\n", v); exit(1); }
 }
-/* BLA_UNET_ATTENTION=f32|bf16 (default f32): where the model's attention blocks multiply (bla_unet_set_attention); orthogonal to the above. */
+/* BLA_UNET_ATTENTION=f32|bf16|online (default f32): where the model's attention blocks multiply (bla_unet_set_attention; online = bf16
+ * products with the online softmax, any block up to S = 4096); orthogonal to the above. */
 static int g_attention = BLA_UNET_ATTENTION_F32;
 static void attention_from_env(void) {
 	const char* v = env_or("BLA_UNET_ATTENTION", "f32");
 	if (strcmp(v, "f32") == 0) g_attention = BLA_UNET_ATTENTION_F32;
 	else if (strcmp(v, "bf16") == 0) g_attention = BLA_UNET_ATTENTION_BF16;
-	else { fprintf(stderr, "BLA_UNET_ATTENTION=%s: expected f32 or bf16\n", v); exit(1); }
+	else if (strcmp(v, "online") == 0) g_attention = BLA_UNET_ATTENTION_BF16_ONLINE;
+	else { fprintf(stderr, "BLA_UNET_ATTENTION=%s: expected f32, bf16 or online\n", v); exit(1); }
 }
 static Device device_open(int batch, size_t drop_per_image) {
 	Device dv; memset(&dv, 0, sizeof dv); dv.batch = batch;

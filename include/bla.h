@@ -669,7 +669,8 @@ BLA_API bla_status bla_attention_backward_batched_f32(void* stream, int batch, c
  * Sums over the batch and across waves have a fixed order: no atomics, the same bits on every run, and image b of a batch equals a batch-1 run of it.
  * bla_attention_bf16_applies (host only, no device needed) is 1 exactly when s % 32 == 0, 32 <= s <= 256, d % 8 == 0, 8 <= d <= 64 and c % 8 == 0 (a d
  * that is no multiple of 16 contracts over zero padding); outside that set both entries return BLA_ERR_INVALID before any launch, outputs untouched.  A
- * wave holds a query's whole row of scores in registers, which is what bounds s: longer sequences need an online softmax and are out of scope.
+ * wave holds a query's whole row of scores in registers, which is what bounds s: longer sequences run on the online-softmax entries below
+ * (bla_attention_{forward,backward}_batched_online_bf16, s up to 4096).
  * Any batch in 1 .. 65535; no workspace growth, so the entries can be captured without a warm-up rule. */
 BLA_API int bla_attention_bf16_applies(int c, int s, int d);
 BLA_API bla_status bla_attention_forward_batched_bf16(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv,
@@ -678,6 +679,37 @@ BLA_API bla_status bla_attention_backward_batched_bf16(void* stream, int batch, 
                                                        const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
                                                        float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w, float* d_del_x,
                                                        int c, int s, int d);
+/* The bf16 attention block for long sequences: the softmax runs ONLINE over blocks of BLA_ATTENTION_ONLINE_KEYS keys taken in ascending
+ * order, and NO S x S TENSOR EXISTS IN MEMORY in either direction.  The forward pass saves one float per query, the row's log-sum-exp; the backward pass
+ * recomputes the probabilities from Q, K and that float.  The rule is unchanged: BOTH OPERANDS OF EVERY MATRIX PRODUCT ARE ROUNDED WITH bla_f32_to_bf16's
+ * ROUNDING (r) IMMEDIATELY BEFORE THE PRODUCT; everything else is fp32.  Per image, Z = X^T, inv = (float)(1 / sqrt((double)d)), key blocks j ascending:
+ *   forward:  Q, K, V as in the bf16 entry (the same kernel: the same bits).
+ *             m = -inf, l = 0, Acc = 0;  per key block j:
+ *               T_j = inv (r(Q) r(K_j)^T);  m' = max(m, rowmax T_j);  a = exp(m - m');  p = exp(T_j - m')
+ *               l = l a + rowsum(p)  (p unrounded);  Acc = Acc a + r(p) r(V_j);  m = m'
+ *             A = Acc / l;  lse = m + log(l);  out = (r(A) r(W) + bias)^T
+ *             Written: ws->q, k, v, attention (= A) as [B][S][d] fp32 and d_out, like the bf16 entry; ws->scores_raw as [B][S] FLOATS, THE ROW
+ *             LOG-SUM-EXP lse.  ws->weights is neither read nor written and may be NULL.
+ *   backward: del_W = sum_b r(A)^T r(del_Y');  del_P = r(del_Y') r(W)^T;  dot_i = sum_dd del_P[i][dd] A[i][dd]   (fp32)
+ *             per key block j:  T_j as above (the same instructions);  P_j = exp(T_j - lse);  del_S_j = r(del_P) r(V_j)^T
+ *               del_I_j = inv P_j o (del_S_j - dot);  del_V_j = r(P_j)^T r(del_P);  del_K_j = r(del_I_j)^T r(Q);  del_Q += r(del_I_j) r(K_j)
+ *             del_Wq/k/v, del_X: as in the bf16 entry.
+ *             Read: fwd->q, k, v, attention, scores_raw (= lse).  grad->q, k, v receive del_Q, del_K, del_V; grad->attention receives del_P as
+ *             [B][S][d]; grad->scores_raw receives the row dots as [B][S]; grad->weights is unused and may be NULL.  d_partials: [batch][4 c d].
+ *             dot_i = <del_P_i, A_i> equals <P_i, del_S_i> of the materialised block in exact arithmetic: that is what lets the pass run without P.
+ * Every sum over key blocks, query blocks, waves and the batch has a fixed order: no atomics, the same bits on every run, and image b of a batch equals a
+ * batch-1 run of it.  The entries are NOT bit-equal to bla_attention_*_batched_bf16 on shapes both accept (the unnormalised p is what is rounded here).
+ * bla_attention_online_bf16_applies (host only) is 1 exactly when s % 32 == 0, 32 <= s <= 4096, d % 8 == 0, 8 <= d <= 64, c % 8 == 0 and c > 0; outside
+ * that set both entries return BLA_ERR_INVALID before any launch, outputs untouched.  Any batch in 1 .. 65535; no workspace growth, so the entries can
+ * be captured without a warm-up rule. */
+#define BLA_ATTENTION_ONLINE_KEYS 32   /* keys per step of the online softmax */
+BLA_API int bla_attention_online_bf16_applies(int c, int s, int d);
+BLA_API bla_status bla_attention_forward_batched_online_bf16(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv,
+                                                             const float* d_w, const float* d_bias, const bla_attention_ws* ws, float* d_out, int c, int s, int d);
+BLA_API bla_status bla_attention_backward_batched_online_bf16(void* stream, int batch, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk,
+                                                              const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
+                                                              float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w,
+                                                              float* d_del_x, int c, int s, int d);
 BLA_API bla_status bla_resnet_forward_batched_f32(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p,
                                                   const unsigned char* d_drop, const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k,
                                                   int tdim, int group_size);
@@ -771,9 +803,13 @@ BLA_API int bla_unet_products(const bla_unet* m);               /* the mode the 
  * bla_attention_{forward,backward}_batched_f32, as always -- a model never switched is bit-equal to before in both `products` modes.
  * BLA_UNET_ATTENTION_BF16: an attention block whose shape bla_attention_bf16_applies accepts runs bla_attention_{forward,backward}_batched_bf16, bit for
  * bit those entries; a block it refuses (at the reference's constants the 4 x 4 mid block, S = 16) keeps the fp32 entries.  Both paths share the block's
- * bla_attention_ws, so the setter is legal between passes (not between a forward pass and its backward pass).  Any other mode: BLA_ERR_INVALID, the
- * model unchanged. */
-enum { BLA_UNET_ATTENTION_F32 = 0, BLA_UNET_ATTENTION_BF16 = 1 };
+ * bla_attention_ws, so the setter is legal between passes (not between a forward pass and its backward pass).
+ * BLA_UNET_ATTENTION_BF16_ONLINE: a block that bla_attention_online_bf16_applies accepts (S up to 4096) runs
+ * bla_attention_{forward,backward}_batched_online_bf16, bit for bit those entries; every other block keeps the fp32 entries.  The row log-sum-exp lives in
+ * the first B S floats of the block's scores_raw, the row dots in the gradient workspace's; nothing more is allocated.
+ * The mode is a bit set: bit 0 = bf16 products, bit 1 = the online softmax.  2 (an online softmax on fp32 products) does not exist; it and any other
+ * value: BLA_ERR_INVALID, the model unchanged. */
+enum { BLA_UNET_ATTENTION_F32 = 0, BLA_UNET_ATTENTION_BF16 = 1, BLA_UNET_ATTENTION_BF16_ONLINE = 3 };
 BLA_API bla_status bla_unet_set_attention(bla_unet* m, int mode);
 BLA_API int bla_unet_attention(const bla_unet* m);
 BLA_API int bla_unet_batch(const bla_unet* m);
