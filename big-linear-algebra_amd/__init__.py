@@ -16,7 +16,8 @@ from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilo
                      unet_set_attention, unet_attention, UNET_ATTENTION_F32, UNET_ATTENTION_BF16, attention_bf16_applies, attention_ws,
                      attention_forward_batched_bf16, attention_backward_batched_bf16, to_mxfp8, from_mxfp8, f32_to_mxfp8, mxfp8_to_f32,
                      gemm_mxfp8, gemm_f32_as_mxfp8, UNET_ATTENTION_BF16_ONLINE, attention_online_bf16_applies,
-                     attention_forward_batched_online_bf16, attention_backward_batched_online_bf16)
+                     attention_forward_batched_online_bf16, attention_backward_batched_online_bf16, attention_online_bf16_heads_applies,
+                     attention_forward_batched_online_bf16_heads, attention_backward_batched_online_bf16_heads)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
@@ -31,4 +32,5 @@ __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Ep
            "unet_set_attention", "unet_attention", "UNET_ATTENTION_F32", "UNET_ATTENTION_BF16", "attention_bf16_applies", "attention_ws",
            "attention_forward_batched_bf16", "attention_backward_batched_bf16", "to_mxfp8", "from_mxfp8", "f32_to_mxfp8", "mxfp8_to_f32", "gemm_mxfp8",
            "gemm_f32_as_mxfp8", "UNET_ATTENTION_BF16_ONLINE", "attention_online_bf16_applies", "attention_forward_batched_online_bf16",
-           "attention_backward_batched_online_bf16"]
+           "attention_backward_batched_online_bf16", "attention_online_bf16_heads_applies", "attention_forward_batched_online_bf16_heads",
+           "attention_backward_batched_online_bf16_heads"]

@@ -26,7 +26,9 @@ namespace {
 
 // ---- qkv: Q | K | V = r(Z) . r([Wq | Wk | Wv]), Z = X^T ------------------------------------------------------------------------------------------
 // One wave per 32 rows of Z (four to a workgroup, independent).  A fragment: X[k][s0 + f] down the channels (a half-wave reads 128 contiguous bytes per
-// k); B fragment: column n of the C x 3d concatenation, i.e. column n % d of matrix n / d.  3 d <= 192: six accumulator tiles at most.
+// k); B fragment: column n of the C x 3d concatenation, i.e. column n % d of matrix n / d.  A wave holds six accumulator tiles, 192 columns: all of them
+// at d <= 64; the multi-head block's d (its heads side by side, up to 256) takes groups of six tiles on gridDim.z.  An element's contraction over C is the
+// same ascending 16-deep steps whatever group its column falls in.
 __global__ void __launch_bounds__(256) att_bf16_qkv_kernel(const float* __restrict__ x, const float* __restrict__ wq, const float* __restrict__ wk,
                                                            const float* __restrict__ wv, float* __restrict__ q, float* __restrict__ k, float* __restrict__ v,
                                                            int c, int s, int d) {
@@ -34,15 +36,15 @@ __global__ void __launch_bounds__(256) att_bf16_qkv_kernel(const float* __restri
 	const int rb = blockIdx.x * 4 + wave, b = blockIdx.y;
 	if (rb * 32 >= s) return;
 	const float* xb = x + (size_t)b * c * s + rb * 32 + fr;
-	const int nt = (3 * d + 31) / 32;
+	const int nt = (3 * d + 31) / 32, j0 = blockIdx.z * 6;
 	f32x16 acc[6];
 	const float* wp[6];
 	bool wok[6];
 #pragma unroll
 	for (int j = 0; j < 6; ++j) {
 		acc[j] = zero16();
-		const int n = 32 * j + fr, mi = n / d;
-		wok[j] = j < nt && n < 3 * d;
+		const int n = 32 * (j0 + j) + fr, mi = n / d;
+		wok[j] = j0 + j < nt && n < 3 * d;
 		wp[j] = wok[j] ? (mi == 0 ? wq : mi == 1 ? wk : wv) + n % d : wq;
 	}
 	for (int k0 = 0; k0 < c; k0 += 16) {
@@ -51,15 +53,39 @@ __global__ void __launch_bounds__(256) att_bf16_qkv_kernel(const float* __restri
 		const bf16x8 a = frag_col8(xb + (size_t)kk * s, (size_t)s, okk);
 #pragma unroll
 		for (int j = 0; j < 6; ++j)
-			if (j < nt) acc[j] = BLA_MFMA(a, frag_col8(wp[j] + (size_t)kk * d, (size_t)d, okk && wok[j]), acc[j]);
+			if (j0 + j < nt) acc[j] = BLA_MFMA(a, frag_col8(wp[j] + (size_t)kk * d, (size_t)d, okk && wok[j]), acc[j]);
 	}
 #pragma unroll
 	for (int j = 0; j < 6; ++j) {
 		if (!wok[j]) continue;
-		const int n = 32 * j + fr, mi = n / d;
+		const int n = 32 * (j0 + j) + fr, mi = n / d;
 		float* dst = (mi == 0 ? q : mi == 1 ? k : v) + (size_t)b * s * d + n % d;
 #pragma unroll
 		for (int r = 0; r < 16; ++r) dst[(size_t)(rb * 32 + acc_row(r, fh)) * d] = acc[j][r];
+	}
+}
+
+// ---- project: out^T = r(W)^T r(A)^T + bias, the multi-head block's output product ----------------------------------------------------
+// One wave per 32 channels x 32 queries (four query blocks to a workgroup, independent), the contraction over all d = heads x head width columns of A in
+// ascending 16-deep steps.  A fragment: W[dd + j][cc] down a column of W; B fragment: A[query f][dd + j], a row of A.  `out` is stored in runs of 32
+// consecutive pixels of a channel, like the forward cores' fused product.  Channel tiles run fastest over the grid, so the tiles that read the same rows
+// of A are neighbours.
+__global__ void __launch_bounds__(256) att_bf16_project_kernel(const float* __restrict__ attention, const float* __restrict__ w, const float* __restrict__ bias,
+                                                               float* __restrict__ out, int c, int s, int d) {
+	const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), fr = lane & 31, fh = lane >> 5;
+	const int ct = blockIdx.x, rb = blockIdx.y * 4 + wave, b = blockIdx.z;
+	if (rb * 32 >= s) return;
+	const int cc = ct * 32 + fr, query = rb * 32 + fr;
+	const float* arow = attention + ((size_t)b * s + query) * d;
+	f32x16 o = zero16();
+	for (int d0 = 0; d0 < d; d0 += 16) {
+		const int dd = d0 + 8 * fh;
+		o = BLA_MFMA(frag_col8(w + (size_t)dd * c + cc, (size_t)c, cc < c && dd < d), frag_row8(arow + dd, dd < d), o);
+	}
+#pragma unroll
+	for (int r = 0; r < 16; ++r) {
+		const int ch = ct * 32 + acc_row(r, fh);
+		if (ch < c) out[((size_t)b * c + ch) * s + query] = o[r] + bias[ch];
 	}
 }
 
@@ -435,7 +461,14 @@ __global__ void __launch_bounds__(256) att_bf16_fold_kernel(const float* __restr
 
 bla_status att_bf16_launch_qkv(hipStream_t hs, int batch, const float* x, const float* wq, const float* wk, const float* wv, float* q, float* k, float* v, int c, int s,
                                int d) {
-	hipLaunchKernelGGL(att_bf16_qkv_kernel, dim3((s / 32 + 3) / 4, batch), dim3(256), 0, hs, x, wq, wk, wv, q, k, v, c, s, d);
+	const int nt = (3 * d + 31) / 32;
+	hipLaunchKernelGGL(att_bf16_qkv_kernel, dim3((s / 32 + 3) / 4, batch, (nt + 5) / 6), dim3(256), 0, hs, x, wq, wk, wv, q, k, v, c, s, d);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
+
+bla_status att_bf16_launch_project(hipStream_t hs, int batch, const float* attention, const float* w, const float* bias, float* out, int c, int s, int d) {
+	hipLaunchKernelGGL(att_bf16_project_kernel, dim3((c + 31) / 32, (s / 32 + 3) / 4, batch), dim3(256), 0, hs, attention, w, bias, out, c, s, d);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
 }

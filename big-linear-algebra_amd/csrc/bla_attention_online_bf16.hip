@@ -15,6 +15,13 @@
 // dkv at d <= 16 loads the fp32 words of the NEXT block's fragments before it works on the current block (the last step loads its own block again: no
 // address past the tensors is formed): measured 7 % off that kernel; the same in the forward core and dq measured nothing and is not done.
 // qkv, grads and fold are bla_attention_bf16.hip's (bla_attention_tile.h).
+//
+// Several heads (bla_attention_*_batched_online_bf16_heads): the heads lie side by side in rows of ld = heads x d floats, head h in columns
+// h d .. h d + d - 1, and gridDim.z is the head.  The four kernels take the row stride ld beside the head width d: every edge test and every tile store
+// is bounded by d, every row step is ld, lse and the row dots sit at (b heads + h) S.  One body serves both pairs of entries (the single-head entries
+// pass ld = d and one grid plane), so a head's arithmetic is the single-head block's instruction for instruction.  With several heads the forward core
+// stops after A (template flag): out contracts over all heads and is a launch of its own (att_bf16_launch_project), as are qkv, grads and fold at
+// width ld.
 #include "bla_attention_tile.h"
 #include <cmath>
 
@@ -48,13 +55,13 @@ struct BlockWords {
 	static constexpr int DT = (ND + 1) / 2;
 	Row8 row[ND];
 	Col8 col[2][DT];
-	__device__ __forceinline__ void load(const float* rows, const float* cols, int t, int d, int fr, int fh) {
+	__device__ __forceinline__ void load(const float* rows, const float* cols, int t, int d, int ld, int fr, int fh) {
 #pragma unroll
-		for (int i = 0; i < ND; ++i) row[i] = ld_row8(rows + (size_t)(t * 32 + fr) * d + 16 * i + 8 * fh, 16 * i + 8 * fh < d);
+		for (int i = 0; i < ND; ++i) row[i] = ld_row8(rows + (size_t)(t * 32 + fr) * ld + 16 * i + 8 * fh, 16 * i + 8 * fh < d);
 #pragma unroll
 		for (int u = 0; u < 2; ++u)
 #pragma unroll
-			for (int dt = 0; dt < DT; ++dt) col[u][dt] = ld_colperm(cols + (size_t)(t * 32 + 16 * u + 4 * fh) * d + dt * 32 + fr, (size_t)d, dt * 32 + fr < d);
+			for (int dt = 0; dt < DT; ++dt) col[u][dt] = ld_colperm(cols + (size_t)(t * 32 + 16 * u + 4 * fh) * ld + dt * 32 + fr, (size_t)ld, dt * 32 + fr < d);
 	}
 };
 
@@ -79,28 +86,28 @@ __device__ __forceinline__ void store_tile_t(float* row, const f32x16& a, int dt
 }
 
 // ---- forward core ----------------------------------------------------------------------------------------------------------------------------------
-template <int ND>
+template <int ND, bool PROJ>
 __global__ void __launch_bounds__(64 * kWaves) att_online_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                                       const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ lse,
-                                                                      float* __restrict__ attention, float* __restrict__ out, int c, int s, int d, float inv) {
+                                                                      float* __restrict__ attention, float* __restrict__ out, int c, int s, int d, int ld, float inv) {
 	constexpr int DT = (ND + 1) / 2;
 	const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), fr = lane & 31, fh = lane >> 5;
 	const int rb = blockIdx.x * kWaves + wave, b = blockIdx.y, nk = s >> 5;
 	if (rb >= nk) return;
-	const size_t img = (size_t)b * s * d;
+	const size_t img = (size_t)b * s * ld + (size_t)blockIdx.z * d, vec = ((size_t)b * gridDim.z + blockIdx.z) * s;
 	const float *qb = q + img, *kb = k + img, *vb = v + img;
 	const int query = rb * 32 + fr;
 
 	bf16x8 qf[ND];
 #pragma unroll
-	for (int i = 0; i < ND; ++i) qf[i] = frag_row8(qb + (size_t)query * d + 16 * i + 8 * fh, 16 * i + 8 * fh < d);
+	for (int i = 0; i < ND; ++i) qf[i] = frag_row8(qb + (size_t)query * ld + 16 * i + 8 * fh, 16 * i + 8 * fh < d);
 	float m = -INFINITY, l = 0.f;
 	f32x16 at[DT];   // Acc^T[dd][query]
 #pragma unroll
 	for (int dt = 0; dt < DT; ++dt) at[dt] = zero16();
 	BlockWords<ND> cur;   // rows of K, columns of V
 	for (int t = 0; t < nk; ++t) {
-		cur.load(kb, vb, t, d, fr, fh);
+		cur.load(kb, vb, t, d, ld, fr, fh);
 		f32x16 sc = score_tile_t<ND>(cur.row, qf, inv);
 		float mx = m;
 #pragma unroll
@@ -125,16 +132,17 @@ __global__ void __launch_bounds__(64 * kWaves) att_online_fwd_kernel(const float
 			for (int dt = 0; dt < DT; ++dt) at[dt] = BLA_MFMA(pack(cur.col[u][dt]), pf, at[dt]);
 		}
 	}
-	if (fh == 0) lse[(size_t)b * s + query] = m + logf(l);
+	if (fh == 0) lse[vec + query] = m + logf(l);
 	bf16x8 af[DT][2];
 #pragma unroll
 	for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
 		for (int r = 0; r < 16; ++r) at[dt][r] /= l;
-		store_tile_t(attention + ((size_t)b * s + query) * d, at[dt], dt, d, fh);
+		store_tile_t(attention + img + (size_t)query * ld, at[dt], dt, d, fh);
 		af[dt][0] = frag_acc(at[dt], 0);
 		af[dt][1] = frag_acc(at[dt], 1);
 	}
+	if (!PROJ) return;   // several heads: the contraction of out runs over all of them (att_bf16_launch_project)
 	// out^T[cc][query] = sum over dd of W[dd][cc] A[query][dd] + bias[cc]
 	for (int c0 = 0; c0 < c; c0 += 32) {
 		f32x16 o = zero16();
@@ -158,12 +166,13 @@ __global__ void __launch_bounds__(64 * kWaves) att_online_fwd_kernel(const float
 // ---- backward preamble: del_P = r(del_Y') r(W)^T and dot = <del_P, A> per query -----------------------------------------------------------------------
 // del_P^T's tiles (rows dd, column = the lane's query), so the dot is a pass over the lane's registers and one exchange with lane + 32.
 __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_pre_kernel(const float* __restrict__ dy, const float* __restrict__ w, const float* __restrict__ attention,
-                                                                          float* __restrict__ dp, float* __restrict__ dots, int c, int s, int d) {
+                                                                          float* __restrict__ dp, float* __restrict__ dots, int c, int s, int d, int ld) {
 	const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), fr = lane & 31, fh = lane >> 5;
 	const int rb = blockIdx.x * kWaves + wave, b = blockIdx.y, ndt = (d + 31) >> 5;
 	if (rb * 32 >= s) return;
 	const int query = rb * 32 + fr;
 	const float* dyb = dy + (size_t)b * c * s;
+	w += (size_t)blockIdx.z * d * c;   // the head's rows of W
 	f32x16 dPT[2];
 	dPT[0] = zero16(); dPT[1] = zero16();
 	for (int c0 = 0; c0 < c; c0 += 16) {
@@ -177,7 +186,7 @@ __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_pre_kernel(const f
 			dPT[dt] = BLA_MFMA(frag_row8(w + (size_t)dd * c + cc, okc && dd < d), yf, dPT[dt]);   // rows dd, column query
 		}
 	}
-	const size_t row = ((size_t)b * s + query) * d;
+	const size_t row = ((size_t)b * s + query) * ld + (size_t)blockIdx.z * d;
 	float dot = 0.f;
 #pragma unroll
 	for (int dt = 0; dt < 2; ++dt) {
@@ -191,7 +200,7 @@ __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_pre_kernel(const f
 		}
 	}
 	dot += __shfl_xor(dot, 32, 64);
-	if (fh == 0) dots[(size_t)b * s + query] = dot;
+	if (fh == 0) dots[((size_t)b * gridDim.z + blockIdx.z) * s + query] = dot;
 }
 
 // ---- backward dq: del_Q of 32 queries over all key blocks ------------------------------------------------------------------------------------------------
@@ -200,31 +209,31 @@ __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_pre_kernel(const f
 template <int ND>
 __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_dq_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                                          const float* __restrict__ dp, const float* __restrict__ lse, const float* __restrict__ dots,
-                                                                         float* __restrict__ gq, int s, int d, float inv) {
+                                                                         float* __restrict__ gq, int s, int d, int ld, float inv) {
 	constexpr int DT = (ND + 1) / 2;
 	const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), fr = lane & 31, fh = lane >> 5;
 	const int rb = blockIdx.x * kWaves + wave, b = blockIdx.y, nk = s >> 5;
 	if (rb >= nk) return;
-	const size_t img = (size_t)b * s * d;
+	const size_t img = (size_t)b * s * ld + (size_t)blockIdx.z * d, vec = ((size_t)b * gridDim.z + blockIdx.z) * s;
 	const float *qb = q + img, *kb = k + img, *vb = v + img, *dpb = dp + img;
 	const int query = rb * 32 + fr;
 	bf16x8 qf[ND], pf[ND];
 #pragma unroll
 	for (int i = 0; i < ND; ++i) {
 		const bool ok = 16 * i + 8 * fh < d;
-		qf[i] = frag_row8(qb + (size_t)query * d + 16 * i + 8 * fh, ok);
-		pf[i] = frag_row8(dpb + (size_t)query * d + 16 * i + 8 * fh, ok);
+		qf[i] = frag_row8(qb + (size_t)query * ld + 16 * i + 8 * fh, ok);
+		pf[i] = frag_row8(dpb + (size_t)query * ld + 16 * i + 8 * fh, ok);
 	}
-	const float L = lse[(size_t)b * s + query], dot = dots[(size_t)b * s + query];
+	const float L = lse[vec + query], dot = dots[vec + query];
 	f32x16 dQ[DT];
 #pragma unroll
 	for (int dt = 0; dt < DT; ++dt) dQ[dt] = zero16();
 	BlockWords<ND> cur;   // rows and columns of K
 	Row8 vrow[ND];        // rows of V
 	for (int t = 0; t < nk; ++t) {
-		cur.load(kb, kb, t, d, fr, fh);
+		cur.load(kb, kb, t, d, ld, fr, fh);
 #pragma unroll
-		for (int i = 0; i < ND; ++i) vrow[i] = ld_row8(vb + (size_t)(t * 32 + fr) * d + 16 * i + 8 * fh, 16 * i + 8 * fh < d);
+		for (int i = 0; i < ND; ++i) vrow[i] = ld_row8(vb + (size_t)(t * 32 + fr) * ld + 16 * i + 8 * fh, 16 * i + 8 * fh < d);
 		const f32x16 sc = score_tile_t<ND>(cur.row, qf, inv);
 		f32x16 dI = zero16();   // del_S^T[key][query] first
 #pragma unroll
@@ -239,7 +248,7 @@ __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_dq_kernel(const fl
 		}
 	}
 #pragma unroll
-	for (int dt = 0; dt < DT; ++dt) store_tile_t(gq + img + (size_t)query * d, dQ[dt], dt, d, fh);
+	for (int dt = 0; dt < DT; ++dt) store_tile_t(gq + img + (size_t)query * ld, dQ[dt], dt, d, fh);
 }
 
 // ---- backward dkv: del_K and del_V of 32 keys over all query blocks ---------------------------------------------------------------------------------------
@@ -249,33 +258,33 @@ __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_dq_kernel(const fl
 template <int ND>
 __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                                           const float* __restrict__ dp, const float* __restrict__ lse, const float* __restrict__ dots,
-                                                                          float* __restrict__ gk, float* __restrict__ gv, int s, int d, float inv) {
+                                                                          float* __restrict__ gk, float* __restrict__ gv, int s, int d, int ld, float inv) {
 	constexpr int DT = (ND + 1) / 2;
 	constexpr bool PF = ND == 1;   // a block ahead where it was measured to pay
 	const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), fr = lane & 31, fh = lane >> 5;
 	const int kt = blockIdx.x * kWaves + wave, b = blockIdx.y, nk = s >> 5;
 	if (kt >= nk) return;
-	const size_t img = (size_t)b * s * d;
-	const float *qb = q + img, *kb = k + img, *vb = v + img, *dpb = dp + img, *lb = lse + (size_t)b * s, *db = dots + (size_t)b * s;
+	const size_t img = (size_t)b * s * ld + (size_t)blockIdx.z * d, vec = ((size_t)b * gridDim.z + blockIdx.z) * s;
+	const float *qb = q + img, *kb = k + img, *vb = v + img, *dpb = dp + img, *lb = lse + vec, *db = dots + vec;
 	const int key = kt * 32 + fr;
 	bf16x8 kf[ND], vf[ND];
 #pragma unroll
 	for (int i = 0; i < ND; ++i) {
 		const bool ok = 16 * i + 8 * fh < d;
-		kf[i] = frag_row8(kb + (size_t)key * d + 16 * i + 8 * fh, ok);
-		vf[i] = frag_row8(vb + (size_t)key * d + 16 * i + 8 * fh, ok);
+		kf[i] = frag_row8(kb + (size_t)key * ld + 16 * i + 8 * fh, ok);
+		vf[i] = frag_row8(vb + (size_t)key * ld + 16 * i + 8 * fh, ok);
 	}
 	f32x16 dK[DT], dV[DT];
 #pragma unroll
 	for (int dt = 0; dt < DT; ++dt) { dK[dt] = zero16(); dV[dt] = zero16(); }
 	BlockWords<ND> qc, qn, pc, pn;   // rows and columns of Q and of del_P for a block of queries
-	if (PF) { qn.load(qb, qb, 0, d, fr, fh); pn.load(dpb, dpb, 0, d, fr, fh); }
+	if (PF) { qn.load(qb, qb, 0, d, ld, fr, fh); pn.load(dpb, dpb, 0, d, ld, fr, fh); }
 	for (int t = 0; t < nk; ++t) {
 		if (PF) {
 			qc = qn; pc = pn;
 			const int tn = t + 1 < nk ? t + 1 : t;
-			qn.load(qb, qb, tn, d, fr, fh); pn.load(dpb, dpb, tn, d, fr, fh);
-		} else { qc.load(qb, qb, t, d, fr, fh); pc.load(dpb, dpb, t, d, fr, fh); }
+			qn.load(qb, qb, tn, d, ld, fr, fh); pn.load(dpb, dpb, tn, d, ld, fr, fh);
+		} else { qc.load(qb, qb, t, d, ld, fr, fh); pc.load(dpb, dpb, t, d, ld, fr, fh); }
 		f32x16 P = zero16(), dI = zero16();
 #pragma unroll
 		for (int i = 0; i < ND; ++i) {
@@ -305,8 +314,8 @@ __global__ void __launch_bounds__(64 * kWaves) att_online_bwd_dkv_kernel(const f
 	}
 #pragma unroll
 	for (int dt = 0; dt < DT; ++dt) {
-		store_tile_t(gk + img + (size_t)key * d, dK[dt], dt, d, fh);
-		store_tile_t(gv + img + (size_t)key * d, dV[dt], dt, d, fh);
+		store_tile_t(gk + img + (size_t)key * ld, dK[dt], dt, d, fh);
+		store_tile_t(gv + img + (size_t)key * ld, dV[dt], dt, d, fh);
 	}
 }
 
@@ -320,32 +329,86 @@ extern "C" {
 int bla_attention_online_bf16_applies(int c, int s, int d) {
 	return s % 32 == 0 && s >= 32 && s <= 4096 && d % 8 == 0 && d >= 8 && d <= 64 && c % 8 == 0 && c > 0;
 }
+int bla_attention_online_bf16_heads_applies(int c, int s, int heads, int d) {
+	return bla_attention_online_bf16_applies(c, s, d) && heads >= 1 && heads <= 256 / d;   // heads d <= 256
+}
+
+}  // extern "C"
 
 #define BLA_ATT_ONLINE_SHAPE(batch, c, s, d)                                                                                     \
 	BLA_REQUIRE(batch > 0 && batch <= 65535 && bla_attention_online_bf16_applies(c, s, d), BLA_ERR_INVALID,                       \
 	            "online bf16 attention: B=%d C=%d S=%d d=%d (S %% 32 == 0 in 32..4096, d %% 8 == 0 in 8..64, C %% 8 == 0)", batch, c, s, d)
+#define BLA_ATT_HEADS_SHAPE(batch, c, s, heads, d)                                                                                               \
+	BLA_REQUIRE(batch > 0 && batch <= 65535 && bla_attention_online_bf16_heads_applies(c, s, heads, d), BLA_ERR_INVALID,                          \
+	            "online bf16 attention: B=%d C=%d S=%d heads=%d d=%d (S %% 32 == 0 in 32..4096, d %% 8 == 0 in 8..64, heads d <= 256, C %% 8 == 0)", \
+	            batch, c, s, heads, d)
+#define BLA_ATT_FWD_NULLS(ws) \
+	BLA_REQUIRE(d_x && d_wq && d_wk && d_wv && d_w && d_bias && d_out && ws && ws->q && ws->k && ws->v && ws->scores_raw && ws->attention, BLA_ERR_INVALID, "null operand")
+#define BLA_ATT_BWD_NULLS(fwd, grad)                                                                                                                            \
+	BLA_REQUIRE(d_del_y && d_x && d_wq && d_wk && d_wv && d_w && fwd && grad && d_partials && d_del_wq && d_del_wk && d_del_wv && d_del_w && d_del_x,           \
+	            BLA_ERR_INVALID, "null operand");                                                                                                               \
+	BLA_REQUIRE(fwd->q && fwd->k && fwd->v && fwd->scores_raw && fwd->attention && grad->q && grad->k && grad->v && grad->attention && grad->scores_raw,        \
+	            BLA_ERR_INVALID, "null workspace")
 // ND = ceil(d / 16)
 #define BLA_ATT_ONLINE_BY_ND(KERNEL, ...)                                                         \
 	switch ((d + 15) / 16) {                                                                      \
-	case 1: hipLaunchKernelGGL(KERNEL<1>, grid, block, 0, hs, __VA_ARGS__); break;                \
-	case 2: hipLaunchKernelGGL(KERNEL<2>, grid, block, 0, hs, __VA_ARGS__); break;                \
-	case 3: hipLaunchKernelGGL(KERNEL<3>, grid, block, 0, hs, __VA_ARGS__); break;                \
-	default: hipLaunchKernelGGL(KERNEL<4>, grid, block, 0, hs, __VA_ARGS__); break;               \
+	case 1: hipLaunchKernelGGL(KERNEL(1), grid, block, 0, hs, __VA_ARGS__); break;                \
+	case 2: hipLaunchKernelGGL(KERNEL(2), grid, block, 0, hs, __VA_ARGS__); break;                \
+	case 3: hipLaunchKernelGGL(KERNEL(3), grid, block, 0, hs, __VA_ARGS__); break;                \
+	default: hipLaunchKernelGGL(KERNEL(4), grid, block, 0, hs, __VA_ARGS__); break;               \
 	}
+#define BLA_ATT_FWD_FUSED(ND) (att_online_fwd_kernel<ND, true>)
+#define BLA_ATT_FWD_HEADS(ND) (att_online_fwd_kernel<ND, false>)
+#define BLA_ATT_DKV(ND) (att_online_bwd_dkv_kernel<ND>)
+#define BLA_ATT_DQ(ND) (att_online_bwd_dq_kernel<ND>)
+
+namespace {
+// both pairs of entries: `heads` heads of width d side by side in rows of heads * d floats, a head per grid plane; one head is the single-head block, whose
+// forward core also multiplies by W (with several the contraction of `out` runs over all of them: a launch of its own)
+bla_status online_forward(hipStream_t hs, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv, const float* d_w, const float* d_bias,
+                          const bla_attention_ws* ws, float* d_out, int c, int s, int heads, int d) {
+	const int ld = heads * d;
+	bla_status st = att_bf16_launch_qkv(hs, batch, d_x, d_wq, d_wk, d_wv, ws->q, ws->k, ws->v, c, s, ld);
+	if (st) return st;
+	const float inv = (float)(1.0 / sqrt((double)d));
+	const dim3 grid((s / 32 + kWaves - 1) / kWaves, batch, heads), block(64 * kWaves);
+	if (heads == 1) {
+		BLA_ATT_ONLINE_BY_ND(BLA_ATT_FWD_FUSED, ws->q, ws->k, ws->v, d_w, d_bias, ws->scores_raw, ws->attention, d_out, c, s, d, ld, inv)
+		BLA_HIP(hipGetLastError());
+		return BLA_OK;
+	}
+	BLA_ATT_ONLINE_BY_ND(BLA_ATT_FWD_HEADS, ws->q, ws->k, ws->v, d_w, d_bias, ws->scores_raw, ws->attention, d_out, c, s, d, ld, inv)
+	BLA_HIP(hipGetLastError());
+	return att_bf16_launch_project(hs, batch, ws->attention, d_w, d_bias, d_out, c, s, ld);
+}
+
+bla_status online_backward(hipStream_t hs, int batch, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv, const float* d_w,
+                           const bla_attention_ws* fwd, const bla_attention_ws* grad, float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv,
+                           float* d_del_w, float* d_del_x, int c, int s, int heads, int d) {
+	const int ld = heads * d;
+	const float inv = (float)(1.0 / sqrt((double)d));
+	const dim3 grid((s / 32 + kWaves - 1) / kWaves, batch, heads), block(64 * kWaves);
+	hipLaunchKernelGGL(att_online_bwd_pre_kernel, grid, block, 0, hs, d_del_y, d_w, fwd->attention, grad->attention, grad->scores_raw, c, s, d, ld);
+	BLA_HIP(hipGetLastError());
+	BLA_ATT_ONLINE_BY_ND(BLA_ATT_DKV, fwd->q, fwd->k, fwd->v, grad->attention, fwd->scores_raw, grad->scores_raw, grad->k, grad->v, s, d, ld, inv)
+	BLA_HIP(hipGetLastError());
+	BLA_ATT_ONLINE_BY_ND(BLA_ATT_DQ, fwd->q, fwd->k, fwd->v, grad->attention, fwd->scores_raw, grad->scores_raw, grad->q, s, d, ld, inv)
+	BLA_HIP(hipGetLastError());
+	// (nothing in grads or fold bounds the width: at heads * d they are the multi-head weight gradients and del_X)
+	return att_bf16_launch_grads_fold(hs, batch, d_del_y, d_x, d_wq, d_wk, d_wv, fwd->attention, grad->q, grad->k, grad->v, d_partials, d_del_wq, d_del_wk, d_del_wv,
+	                                  d_del_w, d_del_x, c, s, ld);
+}
+}  // namespace
+
+extern "C" {
 
 bla_status bla_attention_forward_batched_online_bf16(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv,
                                                      const float* d_w, const float* d_bias, const bla_attention_ws* ws, float* d_out, int c, int s, int d) {
 	bla_status st = require_ready();
 	if (st) return st;
 	BLA_ATT_ONLINE_SHAPE(batch, c, s, d);
-	BLA_REQUIRE(d_x && d_wq && d_wk && d_wv && d_w && d_bias && d_out && ws && ws->q && ws->k && ws->v && ws->scores_raw && ws->attention, BLA_ERR_INVALID, "null operand");
-	hipStream_t hs = pick_stream(stream);
-	if ((st = att_bf16_launch_qkv(hs, batch, d_x, d_wq, d_wk, d_wv, ws->q, ws->k, ws->v, c, s, d))) return st;
-	const float inv = (float)(1.0 / sqrt((double)d));
-	const dim3 grid((s / 32 + kWaves - 1) / kWaves, batch), block(64 * kWaves);
-	BLA_ATT_ONLINE_BY_ND(att_online_fwd_kernel, ws->q, ws->k, ws->v, d_w, d_bias, ws->scores_raw, ws->attention, d_out, c, s, d, inv)
-	BLA_HIP(hipGetLastError());
-	return BLA_OK;
+	BLA_ATT_FWD_NULLS(ws);
+	return online_forward(pick_stream(stream), batch, d_x, d_wq, d_wk, d_wv, d_w, d_bias, ws, d_out, c, s, 1, d);
 }
 
 bla_status bla_attention_backward_batched_online_bf16(void* stream, int batch, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk,
@@ -355,22 +418,31 @@ bla_status bla_attention_backward_batched_online_bf16(void* stream, int batch, c
 	bla_status st = require_ready();
 	if (st) return st;
 	BLA_ATT_ONLINE_SHAPE(batch, c, s, d);
-	BLA_REQUIRE(d_del_y && d_x && d_wq && d_wk && d_wv && d_w && fwd && grad && d_partials && d_del_wq && d_del_wk && d_del_wv && d_del_w && d_del_x, BLA_ERR_INVALID,
-	            "null operand");
-	BLA_REQUIRE(fwd->q && fwd->k && fwd->v && fwd->scores_raw && fwd->attention && grad->q && grad->k && grad->v && grad->attention && grad->scores_raw,
-	            BLA_ERR_INVALID, "null workspace");
-	hipStream_t hs = pick_stream(stream);
-	const float inv = (float)(1.0 / sqrt((double)d));
-	const dim3 grid((s / 32 + kWaves - 1) / kWaves, batch), block(64 * kWaves);
-	hipLaunchKernelGGL(att_online_bwd_pre_kernel, grid, block, 0, hs, d_del_y, d_w, fwd->attention, grad->attention, grad->scores_raw, c, s, d);
-	BLA_HIP(hipGetLastError());
-	BLA_ATT_ONLINE_BY_ND(att_online_bwd_dkv_kernel, fwd->q, fwd->k, fwd->v, grad->attention, fwd->scores_raw, grad->scores_raw, grad->k, grad->v,
-	                     s, d, inv)
-	BLA_HIP(hipGetLastError());
-	BLA_ATT_ONLINE_BY_ND(att_online_bwd_dq_kernel, fwd->q, fwd->k, fwd->v, grad->attention, fwd->scores_raw, grad->scores_raw, grad->q, s, d, inv)
-	BLA_HIP(hipGetLastError());
-	return att_bf16_launch_grads_fold(hs, batch, d_del_y, d_x, d_wq, d_wk, d_wv, fwd->attention, grad->q, grad->k, grad->v, d_partials, d_del_wq, d_del_wk, d_del_wv,
-	                                  d_del_w, d_del_x, c, s, d);
+	BLA_ATT_BWD_NULLS(fwd, grad);
+	return online_backward(pick_stream(stream), batch, d_del_y, d_x, d_wq, d_wk, d_wv, d_w, fwd, grad, d_partials, d_del_wq, d_del_wk, d_del_wv, d_del_w, d_del_x, c, s, 1,
+	                       d);
+}
+
+bla_status bla_attention_forward_batched_online_bf16_heads(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv,
+                                                           const float* d_w, const float* d_bias, const bla_attention_ws* ws, float* d_out, int c, int s, int heads,
+                                                           int d) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_ATT_HEADS_SHAPE(batch, c, s, heads, d);
+	BLA_ATT_FWD_NULLS(ws);
+	return online_forward(pick_stream(stream), batch, d_x, d_wq, d_wk, d_wv, d_w, d_bias, ws, d_out, c, s, heads, d);
+}
+
+bla_status bla_attention_backward_batched_online_bf16_heads(void* stream, int batch, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk,
+                                                            const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
+                                                            float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w, float* d_del_x,
+                                                            int c, int s, int heads, int d) {
+	bla_status st = require_ready();
+	if (st) return st;
+	BLA_ATT_HEADS_SHAPE(batch, c, s, heads, d);
+	BLA_ATT_BWD_NULLS(fwd, grad);
+	return online_backward(pick_stream(stream), batch, d_del_y, d_x, d_wq, d_wk, d_wv, d_w, fwd, grad, d_partials, d_del_wq, d_del_wk, d_del_wv, d_del_w, d_del_x, c, s,
+	                       heads, d);
 }
 
 }  // extern "C"

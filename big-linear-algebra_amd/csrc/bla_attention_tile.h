@@ -65,9 +65,11 @@ __device__ __forceinline__ int acc_row(int r, int fh) { return (r & 3) + 8 * (r 
 
 // ---- the launches both attention blocks share (kernels in bla_attention_bf16.hip; none of them is bounded by S: their grids are S / 32 row blocks or
 // 32 x 32 output tiles by the batch) ------------------------------------------------------------------------------------------------------------------
-// Q | K | V = r(Z) r([Wq | Wk | Wv]) -> q, k, v [batch][S][d]
+// Q | K | V = r(Z) r([Wq | Wk | Wv]) -> q, k, v [batch][S][d]; any d % 8 == 0 (the multi-head block passes heads x head width)
 bla_status att_bf16_launch_qkv(hipStream_t hs, int batch, const float* x, const float* wq, const float* wk, const float* wv, float* q, float* k, float* v, int c, int s,
                                int d);
+// out [batch][C][S] = (r(A) r(W) + bias)^T over all d columns of A [batch][S][d]: the multi-head block's output product
+bla_status att_bf16_launch_project(hipStream_t hs, int batch, const float* attention, const float* w, const float* bias, float* out, int c, int s, int d);
 // del_X, the per-image weight-gradient partials, and their fold in image order
 bla_status att_bf16_launch_grads_fold(hipStream_t hs, int batch, const float* dy, const float* x, const float* wq, const float* wk, const float* wv,
                                       const float* attention, const float* gq, const float* gk, const float* gv, float* partials, float* del_wq, float* del_wk,

@@ -710,6 +710,32 @@ BLA_API bla_status bla_attention_backward_batched_online_bf16(void* stream, int 
                                                               const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
                                                               float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w,
                                                               float* d_del_x, int c, int s, int d);
+/* Multi-head attention on the online block: `heads` heads of width d, D = heads d the width of the block.  Nothing in the library routes to
+ * these entries yet.  Layouts: Wq, Wk, Wv [C][D], head h in columns h d .. h d + d - 1;  W [D][C], head h in rows h d .. h d + d - 1;  bias [C];
+ * ws->q, k, v, attention and grad->q, k, v, attention [B][S][D], a head's columns as in Wq;  ws->scores_raw [B][heads][S], the row log-sum-exp of each
+ * head;  grad->scores_raw [B][heads][S], the row dots of each head;  `weights` unused, may be NULL;  d_partials [batch][4 c D].  Float alignment only.
+ * Arithmetic: the rule and the notation of the online entries above.  Q = r(Z) r(Wq), K, V likewise, at width D (the contraction over C in ascending
+ * 16-deep steps: a column's bits do not depend on D).  Per head h, with Q_h, K_h, V_h, A_h, del_P_h the head's d columns and
+ * inv = (float)(1 / sqrt((double)d)) -- THE HEAD'S WIDTH, NOT D -- the forward recurrence above with the head's own m, l, Acc and lse_h, and the
+ * backward pass above with dot_h,i = sum over the head's d columns of del_P[i][dd] A[i][dd], P_j = exp(T_h,j - lse_h), del_Q_h, del_K_h, del_V_h.
+ * Across heads:  out = (r(A) r(W) + bias)^T, the contraction over all D columns in ascending 16-deep steps;  del_P = r(del_Y') r(W)^T (head h from W's
+ * rows of head h);  del_W, del_Wq/k/v and del_X as in the bf16 entry at width D (del_X sums the three products over all D columns).
+ * A head's q, k, v, attention, lse, del_P, dots, del_Q/K/V and its slices of the four weight gradients are bit for bit what the single-head online
+ * entries give on that head's slices of the weights; out and del_X are sums over the heads and equal them only at heads == 1, where both entries ARE
+ * the single-head entries (every layout above is then theirs).  Every sum has a fixed order: no atomics, the same bits on every run, and image b of a
+ * batch equals a batch-1 run of it.  No S x S tensor exists in memory.
+ * bla_attention_online_bf16_heads_applies (host only) is 1 exactly when s % 32 == 0, 32 <= s <= 4096, d % 8 == 0, 8 <= d <= 64, heads >= 1,
+ * heads d <= 256, c % 8 == 0 and c > 0; outside that set, or with batch outside 1 .. 65535 or a NULL operand or workspace field that is read or written,
+ * both entries return BLA_ERR_INVALID before any launch, outputs untouched.  Forward: 3 launches (qkv, core, output product); backward: 5.  No workspace
+ * growth, so the entries can be captured without a warm-up rule. */
+BLA_API int bla_attention_online_bf16_heads_applies(int c, int s, int heads, int d);
+BLA_API bla_status bla_attention_forward_batched_online_bf16_heads(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk,
+                                                                   const float* d_wv, const float* d_w, const float* d_bias, const bla_attention_ws* ws,
+                                                                   float* d_out, int c, int s, int heads, int d);
+BLA_API bla_status bla_attention_backward_batched_online_bf16_heads(void* stream, int batch, const float* d_del_y, const float* d_x, const float* d_wq,
+                                                                    const float* d_wk, const float* d_wv, const float* d_w, const bla_attention_ws* fwd,
+                                                                    const bla_attention_ws* grad, float* d_partials, float* d_del_wq, float* d_del_wk,
+                                                                    float* d_del_wv, float* d_del_w, float* d_del_x, int c, int s, int heads, int d);
 BLA_API bla_status bla_resnet_forward_batched_f32(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p,
                                                   const unsigned char* d_drop, const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k,
                                                   int tdim, int group_size);
