@@ -17,7 +17,8 @@ from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilo
                      attention_forward_batched_bf16, attention_backward_batched_bf16, to_mxfp8, from_mxfp8, f32_to_mxfp8, mxfp8_to_f32,
                      gemm_mxfp8, gemm_f32_as_mxfp8, UNET_ATTENTION_BF16_ONLINE, attention_online_bf16_applies,
                      attention_forward_batched_online_bf16, attention_backward_batched_online_bf16, attention_online_bf16_heads_applies,
-                     attention_forward_batched_online_bf16_heads, attention_backward_batched_online_bf16_heads)
+                     attention_forward_batched_online_bf16_heads, attention_backward_batched_online_bf16_heads, attention_f32_heads_applies,
+                     attention_forward_batched_f32_heads, attention_backward_batched_f32_heads, unet_create_heads, unet_heads)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
@@ -33,4 +34,5 @@ __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Ep
            "attention_forward_batched_bf16", "attention_backward_batched_bf16", "to_mxfp8", "from_mxfp8", "f32_to_mxfp8", "mxfp8_to_f32", "gemm_mxfp8",
            "gemm_f32_as_mxfp8", "UNET_ATTENTION_BF16_ONLINE", "attention_online_bf16_applies", "attention_forward_batched_online_bf16",
            "attention_backward_batched_online_bf16", "attention_online_bf16_heads_applies", "attention_forward_batched_online_bf16_heads",
-           "attention_backward_batched_online_bf16_heads"]
+           "attention_backward_batched_online_bf16_heads", "attention_f32_heads_applies", "attention_forward_batched_f32_heads",
+           "attention_backward_batched_f32_heads", "unet_create_heads", "unet_heads"]

@@ -22,7 +22,7 @@
 // bla_unet_create_mixed(.., BLA_UNET_PRODUCTS_BF16) is the same composition with the ResNet blocks and the stand-alone convolutions on the bf16 stack:
 // same buckets, same entries, one stream; pinned against a float64 restatement with the compositions' roundings (tests/test_unet_bf16_{host,gpu}.py).
 //
-// The wiring stands in ONE place, the step list kNetwork, and three walkers read it: bla_unet_create_mixed forwards (parameter bucket, tensor names, dropout
+// The wiring stands in ONE place, the step list kNetwork, and three walkers read it: bla_unet_create_heads forwards (parameter bucket, tensor names, dropout
 // offsets; then every step's buffers and its input / output / skip pointers), bla_unet_forward_f32 forwards, unet_backward in reverse.  A change of topology is
 // an edit of kNetwork (and of res[18] / att[5] / kEmbSplit if the number of blocks changes).  What the two product stacks do differently is one table of calls
 // (Stack), chosen at create; attention is chosen per call (bla_unet_set_attention).
@@ -105,6 +105,7 @@ struct bla_unet {
 	bla_unet_config cfg;
 	int batch = 1;
 	int attention = BLA_UNET_ATTENTION_F32;   // BLA_UNET_ATTENTION_BF16: the attention blocks that qualify on bla_attention_{forward,backward}_batched_bf16; _BF16_ONLINE: on the online-softmax entries (3.29)
+	int heads = 1;                          // bla_unet_create_heads: heads of width cfg.key_dim in every attention block
 	int products = BLA_UNET_PRODUCTS_F32;   // BLA_UNET_PRODUCTS_BF16: the blocks and the stand-alone convolutions on the bf16 stack, one stream
 	const Stack* stack = nullptr;           // the calls of `products`
 	int H[4], W[4], max_cout = 1;           // the four resolutions; the widest block output
@@ -184,7 +185,7 @@ void plan_res(bla_unet* m, Res& r, const std::string& name, int cin, int cout, i
 	m->drop_count += (size_t)cout * h * w;
 }
 void plan_att(bla_unet* m, Att& a, const std::string& name, int c, int h, int w) {
-	const int d = m->cfg.key_dim;
+	const int d = m->cfg.key_dim * m->heads;   // the block's width: the heads side by side
 	a.c = c; a.h = h; a.w = w;
 	a.wq = add_tensor(m, name + ".Q_proj", (size_t)c * d);
 	a.wk = add_tensor(m, name + ".K_proj", (size_t)c * d);
@@ -258,6 +259,17 @@ bla_status alloc_res(bla_unet* m, Res& r) {
 		r.pads.dy_pad = m->dy_pad[res_i];
 	}
 	return BLA_OK;
+}
+// several heads: q, k, v, attention at the block's width; one float per (image, head, row) -- the row log-sum-exp of the online entries, in the
+// gradient workspace their row dots -- in scores_raw; P [B][heads][S][S] only where the fp32 heads entries will run (with_p), never in the gradient workspace
+bla_status alloc_att_ws_heads(bla_unet* m, bla_attention_ws& ws, size_t s, bool with_p) {
+	bla_status st;
+	const size_t B = m->batch, heads = m->heads, width = heads * m->cfg.key_dim;
+	ws = bla_attention_ws{};
+	if ((st = dalloc(m, &ws.q, B * s * width)) || (st = dalloc(m, &ws.k, B * s * width)) || (st = dalloc(m, &ws.v, B * s * width)) ||
+	    (st = dalloc(m, &ws.attention, B * s * width)) || (st = dalloc(m, &ws.scores_raw, B * heads * s)))
+		return st;
+	return with_p ? dalloc(m, &ws.weights, B * heads * s * s) : BLA_OK;
 }
 bla_status alloc_att_ws(bla_unet* m, bla_attention_ws& ws, size_t s1, size_t d) {
 	bla_status st;
@@ -451,14 +463,28 @@ bool att_on_bf16(const bla_unet* m, const Att& a) { return m->attention == BLA_U
 bool att_on_online(const bla_unet* m, const Att& a) {
 	return m->attention == BLA_UNET_ATTENTION_BF16_ONLINE && bla_attention_online_bf16_applies(a.c, a.h * a.w, m->cfg.key_dim);
 }
+// several heads: the fp32 heads entries where they apply (S <= 64), else the online ones -- under BLA_UNET_ATTENTION_BF16_ONLINE the other way round.  Create
+// has made sure that one of the two accepts every block, so a long block is bf16-online in BOTH modes.
+bool heads_fit_f32(const bla_unet* m, const Att& a) { return bla_attention_f32_heads_applies(a.c, a.h * a.w, m->heads, m->cfg.key_dim); }
+bool heads_fit_online(const bla_unet* m, const Att& a) { return bla_attention_online_bf16_heads_applies(a.c, a.h * a.w, m->heads, m->cfg.key_dim); }
+bool heads_on_online(const bla_unet* m, const Att& a) {
+	return m->attention == BLA_UNET_ATTENTION_BF16_ONLINE ? heads_fit_online(m, a) : !heads_fit_f32(m, a);
+}
 bla_status att_forward(bla_unet* m, void* stream, Att& a, const float* in) {
 	const float* P = m->params;
+	if (m->heads > 1)
+		return (heads_on_online(m, a) ? bla_attention_forward_batched_online_bf16_heads : bla_attention_forward_batched_f32_heads)(
+			stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, m->heads, m->cfg.key_dim);
 	return (att_on_online(m, a) ? bla_attention_forward_batched_online_bf16 : att_on_bf16(m, a) ? bla_attention_forward_batched_bf16 : bla_attention_forward_batched_f32)(
 		stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, m->cfg.key_dim);
 }
 bla_status att_backward(bla_unet* m, void* stream, Att& a, const float* g, const float* x, float* out) {
 	const float* P = m->params; float* G = m->grads;
 	const int d = m->cfg.key_dim;
+	if (m->heads > 1)
+		return (heads_on_online(m, a) ? bla_attention_backward_batched_online_bf16_heads : bla_attention_backward_batched_f32_heads)(
+			stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv, G + a.wo, out, a.c, a.h * a.w,
+			m->heads, d);
 	if (att_on_online(m, a) || att_on_bf16(m, a))
 		return (att_on_online(m, a) ? bla_attention_backward_batched_online_bf16 : bla_attention_backward_batched_bf16)(
 			stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv, G + a.wo, out, a.c, a.h * a.w, d);
@@ -579,15 +605,21 @@ int bla_unet_products(const bla_unet* m) { return m ? m->products : BLA_UNET_PRO
 
 int bla_unet_attention(const bla_unet* m) { return m ? m->attention : BLA_UNET_ATTENTION_F32; }
 
+int bla_unet_heads(const bla_unet* m) { return m ? m->heads : 1; }
+
 bla_status bla_unet_set_attention(bla_unet* m, int mode) {
 	BLA_REQUIRE(mode == BLA_UNET_ATTENTION_F32 || mode == BLA_UNET_ATTENTION_BF16 || mode == BLA_UNET_ATTENTION_BF16_ONLINE, BLA_ERR_INVALID,
 	            "bla_unet_set_attention: mode %d (BLA_UNET_ATTENTION_F32, _BF16 or _BF16_ONLINE)", mode);
 	BLA_REQUIRE(m, BLA_ERR_INVALID, "null argument");
+	BLA_REQUIRE(m->heads == 1 || mode != BLA_UNET_ATTENTION_BF16, BLA_ERR_INVALID,
+	            "bla_unet_set_attention: BLA_UNET_ATTENTION_BF16 on a model with %d heads (the materialising bf16 block has none)", m->heads);
 	m->attention = mode;
 	return BLA_OK;
 }
 
-bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int batch, int products) {
+bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int batch, int products) { return bla_unet_create_heads(out, cfg, batch, products, 1); }
+
+bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int batch, int products, int heads) {
 	BLA_REQUIRE(products == BLA_UNET_PRODUCTS_F32 || products == BLA_UNET_PRODUCTS_BF16, BLA_ERR_INVALID, "bla_unet_create_mixed: products %d (BLA_UNET_PRODUCTS_F32 or _BF16)", products);
 	const bool bf16 = products == BLA_UNET_PRODUCTS_BF16;
 	bla_status st = require_ready();
@@ -597,9 +629,12 @@ bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int
 	BLA_REQUIRE(cfg->image_h > 0 && cfg->image_w > 0 && cfg->in_channels > 0 && cfg->time_dim > 0 && cfg->kernel > 0 && cfg->group_size > 0 && cfg->key_dim > 0 &&
 	            cfg->dims[0] > 0 && cfg->dims[1] > 0 && cfg->dims[2] > 0 && cfg->dims[3] > 0, BLA_ERR_INVALID, "bad U-Net configuration");
 	BLA_REQUIRE(cfg->image_h % 8 == 0 && cfg->image_w % 8 == 0, BLA_ERR_INVALID, "image size must be a multiple of 8 (three halvings, each undone by a x2 up-sampling)");
+	BLA_REQUIRE(heads >= 1 && (heads == 1 || heads <= 256 / cfg->key_dim), BLA_ERR_INVALID, "bla_unet_create_heads: %d heads of width %d (heads >= 1, heads key_dim <= 256)",
+	            heads, cfg->key_dim);
 	bla_unet* m = new bla_unet();
 	m->cfg = *cfg;
 	m->batch = batch;
+	m->heads = heads;
 	m->products = products;
 	m->stack = bf16 ? &kStackBf16 : &kStackF32;
 	const size_t B = (size_t)batch;
@@ -624,6 +659,13 @@ bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int
 	}
 
 	auto fail = [&](bla_status s) { (void)bla_unet_destroy(m); return s; };
+	if (heads > 1)   // every block needs one of the two multi-head paths (before anything is allocated)
+		for (const Att& a : m->att)
+			if (!heads_fit_f32(m, a) && !heads_fit_online(m, a)) {
+				set_error("bla_unet_create_heads: no multi-head attention path for C=%d S=%d heads=%d d=%d (fp32: S <= 64; online bf16: S %% 32 == 0, d %% 8 == 0, C %% 8 == 0)",
+				          a.c, a.h * a.w, heads, cfg->key_dim);
+				return fail(BLA_ERR_INVALID);
+			}
 	if ((st = dalloc_zeroed(m, &m->params, m->count)) || (st = dalloc_zeroed(m, &m->grads, m->count))) return fail(st);
 	size_t max_act = 0, max_s = 0, max_flip = 0, max_cout_hw = 0, max_cin_hw = 0, max_cd = 1;
 	for (Res& r : m->res) {
@@ -647,8 +689,9 @@ bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int
 		case ATT: {
 			Att& a = m->att[s.index];
 			const size_t sp = (size_t)a.h * a.w;
-			if ((st = alloc_att_ws(m, a.fwd, sp, cfg->key_dim)) || (st = dalloc(m, &a.out, B * a.c * sp))) return fail(st);
-			max_s = std::max(max_s, sp); max_cd = std::max(max_cd, (size_t)a.c * cfg->key_dim);
+			if ((st = heads > 1 ? alloc_att_ws_heads(m, a.fwd, sp, heads_fit_f32(m, a)) : alloc_att_ws(m, a.fwd, sp, cfg->key_dim)) || (st = dalloc(m, &a.out, B * a.c * sp)))
+				return fail(st);
+			max_s = std::max(max_s, sp); max_cd = std::max(max_cd, (size_t)a.c * cfg->key_dim * heads);
 			s.out = a.out;
 			break;
 		}
@@ -688,7 +731,7 @@ bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int
 	}
 	if ((st = dalloc(m, &m->ring[0], max_act)) || (st = dalloc(m, &m->ring[1], max_act)) || (st = dalloc(m, &m->ring[2], max_act)) || (st = dalloc(m, &m->sc.g_out_a, max_cout_hw)) ||
 	    (st = dalloc(m, &m->sc.g_out_b, max_cout_hw)) || (st = dalloc(m, &m->sc.g_in, max_cin_hw)) || (st = dalloc(m, &m->sc.flip, max_flip)) ||
-	    (st = alloc_att_ws(m, m->agrad, max_s, cfg->key_dim)) || (st = dalloc(m, &m->dtb, B * m->max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
+	    (st = heads > 1 ? alloc_att_ws_heads(m, m->agrad, max_s, false) : alloc_att_ws(m, m->agrad, max_s, cfg->key_dim)) || (st = dalloc(m, &m->dtb, B * m->max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
 		return fail(st);
 	if ((st = dalloc_zeroed(m, &m->zero_drop, B * m->drop_count))) return fail(st);
 	{   // the 18 time-embedding projections (and, for a batch, their gradients) as one launch each way (eight embedding rows in LDS), and the embedding gradient's

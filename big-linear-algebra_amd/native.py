@@ -162,6 +162,10 @@ SIGNATURES = {
     "bla_attention_online_bf16_heads_applies": (_I, [_I] * 4),
     "bla_attention_forward_batched_online_bf16_heads": (_I, [_VP, _I] + [_VP] * 8 + [_I] * 4),
     "bla_attention_backward_batched_online_bf16_heads": (_I, [_VP, _I] + [_VP] * 14 + [_I] * 4),
+    "bla_attention_f32_heads_applies": (_I, [_I] * 4),
+    "bla_attention_forward_batched_f32_heads": (_I, [_VP, _I] + [_VP] * 8 + [_I] * 4),
+    "bla_attention_backward_batched_f32_heads": (_I, [_VP, _I] + [_VP] * 14 + [_I] * 4),
+    "bla_unet_create_heads": (_I, [C.POINTER(_VP), _VP, _I, _I, _I]), "bla_unet_heads": (_I, [_VP]),
     "bla_unet_set_attention": (_I, [_VP, _I]), "bla_unet_attention": (_I, [_VP]),
     "bla_resnet_forward_batched_f32": (_I, [_VP, _I] + [_VP] * 6 + [_I] * 7), "bla_resnet_backward_batched_f32": (_I, [_VP, _I] + [_VP] * 9 + [_I] * 7),
     "bla_group_norm_relu_bf16_map": (_I, [_VP, _I, _VP] + [_I] * 4 + [_VP] * 4 + [C.POINTER(ConvBf16Map)]),
@@ -678,6 +682,34 @@ def attention_backward_batched_online_bf16_heads(batch, del_y, x, wq, wk, wv, w,
     check(lib().bla_attention_backward_batched_online_bf16_heads(stream, batch, _ptr(del_y), _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(w), C.byref(fwd),
                                                                  C.byref(grad), _ptr(partials), _ptr(del_wq), _ptr(del_wk), _ptr(del_wv), _ptr(del_w), _ptr(del_x),
                                                                  c, s, heads, d))
+
+
+def attention_f32_heads_applies(c, s, heads, d):
+    """bla_attention_f32_heads_applies: host only, no device needed; d is the width of one head."""
+    return bool(lib().bla_attention_f32_heads_applies(c, s, heads, d))
+
+
+def attention_forward_batched_f32_heads(batch, x, wq, wk, wv, w, bias, ws, out, c, s, heads, d, stream=None):
+    """bla_attention_forward_batched_f32_heads: ws needs q, k, v, attention ([batch][s][heads d]) and weights ([batch][heads][s][s])."""
+    check(lib().bla_attention_forward_batched_f32_heads(stream, batch, _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(w), _ptr(bias), C.byref(ws), _ptr(out), c, s, heads, d))
+    return out
+
+
+def attention_backward_batched_f32_heads(batch, del_y, x, wq, wk, wv, w, fwd, grad, partials, del_wq, del_wk, del_wv, del_w, del_x, c, s, heads, d, stream=None):
+    """bla_attention_backward_batched_f32_heads: grad needs q, k, v and attention (del_P); partials [batch][c heads d]."""
+    check(lib().bla_attention_backward_batched_f32_heads(stream, batch, _ptr(del_y), _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(w), C.byref(fwd), C.byref(grad),
+                                                         _ptr(partials), _ptr(del_wq), _ptr(del_wk), _ptr(del_wv), _ptr(del_w), _ptr(del_x), c, s, heads, d))
+
+
+def unet_create_heads(cfg, batch=1, products=UNET_PRODUCTS_F32, heads=1):
+    """bla_unet_create_heads: the U-Net with `heads` attention heads of width cfg.key_dim; returns the model handle like unet_create_mixed."""
+    h = C.c_void_p()
+    check(lib().bla_unet_create_heads(C.byref(h), C.byref(cfg), batch, products, heads))
+    return h
+
+
+def unet_heads(model):
+    return lib().bla_unet_heads(model)
 
 
 def conv2d_gathered_bf16(a, rows, p, batch, hp, wp, cp, k, stride, ho, wo, out, ep_bias=None, ep_bias_stride=0, stream=None):

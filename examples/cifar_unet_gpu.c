@@ -175,6 +175,28 @@ static const char* env_or(const char* name, const char* fallback) { const char* 
 static int env_flag(const char* name) { const char* v = getenv(name); return v && *v && strcmp(v, "0") != 0; }
 static int side_of(int resolution) { int s = IMAGE_SIDE; for (int r = 1; r < resolution; r++) s = (s + RESIZE_STRIDE - 1) / RESIZE_STRIDE; return s; }   /* :39-46 */
 
+/* BLA_UNET_HEADS=<n> (default 1): attention heads of width KEY_DIM in every self-attention block (bla_unet_create_heads); the attention
+ * parameter files are then KEY_DIM x n wide.  Read before any sub-command opens the device: a value that is no positive integer, or one the model refuses
+ * (no multi-head path for one of its blocks, or BLA_UNET_ATTENTION=bf16, which has no heads), stops every one of them. */
+static int g_heads = 1;
+static void heads_from_env(int attention) {
+	const char* v = env_or("BLA_UNET_HEADS", "1");
+	char* end;
+	const long n = strtol(v, &end, 10);
+	if (end == v || *end || n < 1 || n > 65536) { fprintf(stderr, "BLA_UNET_HEADS=%s: expected a positive integer\n", v); exit(1); }
+	g_heads = (int)n;
+	if (g_heads == 1) return;
+	if (attention == BLA_UNET_ATTENTION_BF16) { fprintf(stderr, "BLA_UNET_HEADS=%s: BLA_UNET_ATTENTION=bf16 has no heads (f32 or online)\n", v); exit(1); }
+	const int level[2] = {2, 4};   /* the resolutions with attention blocks */
+	for (int i = 0; i < 2; i++) {
+		const int c = kDims[level[i] - 1], s = side_of(level[i]) * side_of(level[i]);
+		if (!bla_attention_f32_heads_applies(c, s, g_heads, KEY_DIM) && !bla_attention_online_bf16_heads_applies(c, s, g_heads, KEY_DIM)) {
+			fprintf(stderr, "BLA_UNET_HEADS=%s: the model refuses %d heads of width %d (C = %d, S = %d; heads x %d <= 256)\n", v, g_heads, KEY_DIM, c, s, KEY_DIM);
+			exit(1);
+		}
+	}
+}
+
 /* ---- the parameter tensors, in init_parameters' order (:1804-1844) ------------------------------------------------------------------ */
 typedef enum { DRAW_HE, DRAW_XAVIER, DRAW_ZERO } Draw;
 typedef struct Tensor {
@@ -228,14 +250,14 @@ static void plan_resnet(const char* member, const char* dir, int resolution, int
 /* _init_self_attention_block :1473-1482 / _save_self_attention_block :1528-1543; `dir` is made, the files go below `files_in` */
 static void plan_attention(const char* member, const char* dir, const char* files_in, int resolution, int embed) {
 	static const char* part[5] = {"Q_proj", "K_proj", "V_proj", "weights", "biases"}, *leaf[5] = {"query", "key", "value", "weight", "bias"};
-	const int area = side_of(resolution) * side_of(resolution);
+	const int area = side_of(resolution) * side_of(resolution), width = KEY_DIM * g_heads;   /* the heads side by side */
 	plan_dir(dir);
 	for (int i = 0; i < 5; i++) {
 		char name[64], file[96];
 		snprintf(name, sizeof name, "%s.%s", member, part[i]); snprintf(file, sizeof file, "%s/%s.csv", files_in, leaf[i]);
-		if (i < 2) plan(name, file, embed, KEY_DIM, 0, 0, DRAW_XAVIER, area, KEY_DIM);
-		else if (i == 2) plan(name, file, embed, KEY_DIM, 0, 0, DRAW_HE, area, 0);
-		else if (i == 3) plan(name, file, KEY_DIM, embed, 0, 0, DRAW_HE, KEY_DIM, 0);
+		if (i < 2) plan(name, file, embed, width, 0, 0, DRAW_XAVIER, area, width);
+		else if (i == 2) plan(name, file, embed, width, 0, 0, DRAW_HE, area, 0);
+		else if (i == 3) plan(name, file, width, embed, 0, 0, DRAW_HE, width, 0);
 		else plan(name, file, 1, embed, 0, 0, DRAW_ZERO, 0, 0);
 	}
 }
@@ -428,7 +450,7 @@ static Device device_open(int batch, size_t drop_per_image) {
 	Device dv; memset(&dv, 0, sizeof dv); dv.batch = batch;
 	CHECK(bla_init(atoi(env_or("BLA_DEVICE", "0"))));
 	bla_unet_config cfg = {IMAGE_SIDE, IMAGE_SIDE, IMAGE_CHANNELS, {kDims[0], kDims[1], kDims[2], kDims[3]}, TIME_EMBED_DIM, KERNEL_SIZE, GROUP_SIZE, KEY_DIM};
-	CHECK(bla_unet_create_mixed(&dv.net, &cfg, batch, g_products));
+	CHECK(bla_unet_create_heads(&dv.net, &cfg, batch, g_products, g_heads));
 	CHECK(bla_unet_set_attention(dv.net, g_attention));
 	if (bla_unet_dropout_count(dv.net) != drop_per_image * batch) { fprintf(stderr, "dropout layout: device %zu, host %zu\n", bla_unet_dropout_count(dv.net), drop_per_image * batch); exit(1); }
 	CHECK(bla_malloc((void**)&dv.x, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
@@ -1306,6 +1328,7 @@ int main(int argc, char** argv) {
 	}
 	products_from_env();   /* before any sub-command opens the device: a bad value stops every one of them */
 	attention_from_env();
+	heads_from_env(g_attention);
 	plan_model();
 	if (strncmp(argv[1], "run", 3) == 0) {
 		run(argc < 3 ? 1 : atoi(argv[2]));

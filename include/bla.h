@@ -710,8 +710,8 @@ BLA_API bla_status bla_attention_backward_batched_online_bf16(void* stream, int 
                                                               const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
                                                               float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w,
                                                               float* d_del_x, int c, int s, int d);
-/* Multi-head attention on the online block: `heads` heads of width d, D = heads d the width of the block.  Nothing in the library routes to
- * these entries yet.  Layouts: Wq, Wk, Wv [C][D], head h in columns h d .. h d + d - 1;  W [D][C], head h in rows h d .. h d + d - 1;  bias [C];
+/* Multi-head attention on the online block: `heads` heads of width d, D = heads d the width of the block.  bla_unet_create_heads routes
+ * to these entries.  Layouts: Wq, Wk, Wv [C][D], head h in columns h d .. h d + d - 1;  W [D][C], head h in rows h d .. h d + d - 1;  bias [C];
  * ws->q, k, v, attention and grad->q, k, v, attention [B][S][D], a head's columns as in Wq;  ws->scores_raw [B][heads][S], the row log-sum-exp of each
  * head;  grad->scores_raw [B][heads][S], the row dots of each head;  `weights` unused, may be NULL;  d_partials [batch][4 c D].  Float alignment only.
  * Arithmetic: the rule and the notation of the online entries above.  Q = r(Z) r(Wq), K, V likewise, at width D (the contraction over C in ascending
@@ -736,6 +736,35 @@ BLA_API bla_status bla_attention_backward_batched_online_bf16_heads(void* stream
                                                                     const float* d_wk, const float* d_wv, const float* d_w, const bla_attention_ws* fwd,
                                                                     const bla_attention_ws* grad, float* d_partials, float* d_del_wq, float* d_del_wk,
                                                                     float* d_del_wv, float* d_del_w, float* d_del_x, int c, int s, int heads, int d);
+/* Multi-head attention in fp32 for short sequences: the fp32 batched block's arithmetic per head, with the materialised softmax -- what a
+ * multi-head block runs where the online entries above do not apply (S < 32 or no multiple of 32: the 4 x 4 mid block).  bla_unet_create_heads routes to it.
+ * Layouts, as in the online heads entries: Wq, Wk, Wv [C][D], D = heads d, head h in columns h d .. h d + d - 1;  W [D][C], head h in rows h d .. h d + d - 1;
+ * bias [C];  ws->q, k, v, attention and grad->q, k, v, attention (= del_P) [B][S][D], a head's columns as in Wq;  ws->weights = P as [B][heads][S][S];
+ * scores_raw is neither read nor written and may be NULL in both workspaces;  grad->weights is unused and may be NULL;  d_partials [batch][C D].  Float
+ * alignment only; S and d need not be multiples of anything.
+ * Per image, Z = X^T, inv = (float)(1 / sqrt((double)d)) -- THE HEAD'S WIDTH, NOT D:
+ *   forward:  Q = Z Wq, K = Z Wk, V = Z Wv at width D;  per head h:  T_h = inv (Q_h K_h^T);  P_h = softmax of T_h's rows, the row maximum subtracted;
+ *             A_h = P_h V_h;  out [C][S] = (A W + bias)^T, the contraction over all D columns.
+ *   backward (the intended composition only, no jacobian_from_raw):  del_W = sum_b A^T del_Y';  del_P = del_Y' W^T (head h from W's rows of head h);  per head:
+ *             del_S_h = del_P_h V_h^T;  dot_i = <P_h,i, del_S_h,i> (double, rounded once);  del_I_h = inv P_h o (del_S_h - dot);  del_V_h = P_h^T del_P_h;
+ *             del_Q_h = del_I_h K_h;  del_K_h = del_I_h^T Q_h;  then del_Wq/k/v = sum_b Z^T del_Q/K/V and del_X = Wq del_Q^T + Wk del_K^T + Wv del_V^T at width D.
+ * The products at width D are the fp32 batched block's own calls (bla_gemm_batched_f32, the sums over the batch in image order) with d := D.  The per-head
+ * part is two fused kernels, one workgroup per (image, head): T, del_S and del_I never leave the chip, P is stored once.  Every sum in them is one thread's
+ * loop in ascending index order: no atomics, the same bits on every run, and in them image b of a batch equals a batch-1 run of it (the width-D products
+ * keep bla_gemm_batched_f32's plan, which is the same for every batch while 32 x 32 tiles x batch stays below 129).  Forward: 5 launches; backward: 11 or 13.
+ * heads == 1: the entries ARE bla_attention_{forward,backward}_batched_f32 (jacobian_from_raw = 0) -- the same launches, the same bits, every layout above
+ * is then theirs -- and scores_raw (both workspaces) and grad->weights are REQUIRED, as they are there.
+ * bla_attention_f32_heads_applies (host only) is 1 exactly when 1 <= s <= 64, 1 <= d <= 64, heads >= 1, heads d <= 256 and c > 0; outside that set, or with
+ * batch outside 1 .. 65535 or a NULL operand or workspace field that is read or written, both entries return BLA_ERR_INVALID before any launch, outputs
+ * untouched.  No workspace growth beyond what bla_gemm_batched_f32 may ask for. */
+BLA_API int bla_attention_f32_heads_applies(int c, int s, int heads, int d);
+BLA_API bla_status bla_attention_forward_batched_f32_heads(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv,
+                                                           const float* d_w, const float* d_bias, const bla_attention_ws* ws, float* d_out, int c, int s, int heads,
+                                                           int d);
+BLA_API bla_status bla_attention_backward_batched_f32_heads(void* stream, int batch, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk,
+                                                            const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
+                                                            float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w, float* d_del_x,
+                                                            int c, int s, int heads, int d);
 BLA_API bla_status bla_resnet_forward_batched_f32(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p,
                                                   const unsigned char* d_drop, const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k,
                                                   int tdim, int group_size);
@@ -838,6 +867,21 @@ BLA_API int bla_unet_products(const bla_unet* m);               /* the mode the 
 enum { BLA_UNET_ATTENTION_F32 = 0, BLA_UNET_ATTENTION_BF16 = 1, BLA_UNET_ATTENTION_BF16_ONLINE = 3 };
 BLA_API bla_status bla_unet_set_attention(bla_unet* m, int mode);
 BLA_API int bla_unet_attention(const bla_unet* m);
+/* The same network with multi-head self-attention: every attention block has `heads` heads of width cfg->key_dim -- bla_unet_config is unchanged,
+ * key_dim stays the width of ONE head -- so its Q_proj, K_proj, V_proj tensors are [C][D] and its `weights` tensor [D][C], D = heads key_dim, laid out as the
+ * heads entries above state; bla_unet_tensor_info and bla_unet_param_count report those sizes.  heads == 1 is bla_unet_create_mixed in every respect.
+ * heads > 1, routing per block, asked at every call:
+ *   BLA_UNET_ATTENTION_F32 (the default): bla_attention_{forward,backward}_batched_f32_heads where bla_attention_f32_heads_applies accepts the block (S <= 64),
+ *     otherwise bla_attention_{forward,backward}_batched_online_bf16_heads;
+ *   BLA_UNET_ATTENTION_BF16_ONLINE: the online heads entries where bla_attention_online_bf16_heads_applies accepts the block, otherwise the fp32 heads entries;
+ *   BLA_UNET_ATTENTION_BF16: bla_unet_set_attention returns BLA_ERR_INVALID, the model unchanged (the materialising bf16 block has no heads).
+ * SO A heads > 1 MODEL'S LONG BLOCKS (S > 64) MULTIPLY IN bf16 ON THE ONLINE SOFTMAX IN BOTH MODES, BLA_UNET_ATTENTION_F32 INCLUDED: there is no fp32 multi-head
+ * path for S > 64.  At the reference's constants that is the four 16 x 16 blocks (S = 256); the 4 x 4 mid block (S = 16) is fp32 in mode 0.
+ * A block that neither predicate accepts (e.g. 36 x 36 images: S = 324 at level 1), heads < 1 or heads key_dim > 256: BLA_ERR_INVALID, nothing allocated
+ * is left behind, *out untouched.  A heads > 1 model allocates P ([B][heads][S][S]) only for the blocks the fp32 heads predicate accepts; its other per-block
+ * buffers beside q, k, v, attention are B heads S floats (the row log-sum-exp / the row dots): no S x S buffer exists for the long blocks. */
+BLA_API bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int batch, int products, int heads);
+BLA_API int bla_unet_heads(const bla_unet* m);                  /* the number of heads the model was created with (1 for every other create entry) */
 BLA_API int bla_unet_batch(const bla_unet* m);
 BLA_API bla_status bla_unet_destroy(bla_unet* m);
 BLA_API size_t bla_unet_param_count(const bla_unet* m);         /* floats in each bucket (every tensor starts 16-byte aligned) */
