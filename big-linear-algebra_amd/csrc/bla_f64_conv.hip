@@ -114,10 +114,6 @@ __global__ void __launch_bounds__(kT) softmax_rows_f64_kernel(double* __restrict
 }
 }  // namespace
 
-#define BLA_ENTER()                  \
-	bla_status st = require_ready(); \
-	if (st) return st;
-
 extern "C" {
 
 bla_status bla_im2col_f64(void* stream, const double* d_x, double* d_out, int h, int w, int k, int c_in, int stride) {

@@ -186,6 +186,8 @@ bla_status resnet_backward_bf16(void* stream, int batch, const float* d_del_out,
 
 // bla_unet.hip: dst[i] = sum over the images of src[b][i], added in image order (the bf16 block of bla_conv_bf16.hip forms its time_b gradient with it too)
 bla_status batch_sum(void* stream, const float* src, float* dst, int batch, size_t n);
+// bla_unet.hip: out[r] = (s[r] o (g[r] - <s[r], g[r]>)) * scale per row: the launch behind bla_softmax_ddx_f32 (scale 1) and the batched fp32 attention block
+bla_status softmax_ddx_launch(void* stream, const float* s, const float* g, float* out, int rows, int dim, float scale);
 
 // bla_unet_model.hip: the configuration a U-Net was created with (bla_diffusion.hip's sampler sizes its embeddings from it)
 const bla_unet_config* unet_config(const bla_unet* m);
@@ -242,6 +244,11 @@ struct RandStreamGuard {
 		hipError_t _e = (call);                                     \
 		if (_e != hipSuccess) return ::bla::hip_fail(_e, #call);    \
 	} while (0)
+
+// the first statement of an entry: the status `st`, and out unless the library is initialised
+#define BLA_ENTER()                                                 \
+	bla_status st = ::bla::require_ready();                         \
+	if (st) return st;
 
 #define BLA_REQUIRE(cond, status, ...)                              \
 	do {                                                            \

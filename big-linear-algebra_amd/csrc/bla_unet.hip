@@ -1,9 +1,9 @@
 // bla_unet.hip -- the elementwise / resize glue ops that sit on either side of every conv() in the reference's U-Net
 // (model/cifar_unet.c:235-253,1024-1097,1168-1178,1229-1259), SURVEY 8(f) rank 1.  All HBM-bound, one pass each;
 // channel arrays are contiguous [C][H*W] buffers.  The adds of _nearest_neighbours_ddx are done in the reference's
-// order (row-major over the source block), so the fp32 result is bit-identical to the fp32 oracle.
+// order (row-major over the source block), so the fp32 result is bit-identical to the fp32 oracle.  Behind them the ResNet block, single-image and
+// batched, and the batched group norms.  The softmax Jacobian kernel serves bla_softmax_ddx_f32 and, through softmax_ddx_launch, other translation units.
 #include "bla_internal.h"
-#include <cmath>
 
 namespace bla {
 constexpr int kT = 256;
@@ -92,6 +92,11 @@ __global__ void __launch_bounds__(kT) softmax_ddx_kernel(const float* __restrict
 	if (scale == 1.f) { for (int j = lane; j < dim; j += 64) out[(size_t)r * dim + j] = sr[j] * (gr[j] - d); }
 	else { for (int j = lane; j < dim; j += 64) out[(size_t)r * dim + j] = (sr[j] * (gr[j] - d)) * scale; }   // the matrix_scale behind it (:1308), same rounding
 }
+bla_status softmax_ddx_launch(void* stream, const float* s, const float* g, float* out, int rows, int dim, float scale) {   // bla_internal.h
+	hipLaunchKernelGGL(softmax_ddx_kernel, dim3((rows + 3) / 4), dim3(kT), 0, pick_stream(stream), s, g, out, rows, dim, scale);
+	BLA_HIP(hipGetLastError());
+	return BLA_OK;
+}
 // dst[i] = sum over the images of src[b][i] (in image order): weight gradients of a batch from per-image products
 __global__ void __launch_bounds__(kT) batch_sum_kernel(const float* __restrict__ src, float* __restrict__ dst, int batch, size_t n) {
 	for (size_t i = (size_t)blockIdx.x * kT + threadIdx.x; i < n; i += (size_t)gridDim.x * kT) {
@@ -123,10 +128,6 @@ static bool fold_groups(int batch, int c, int group_size, int* channels, int* gr
 }  // namespace bla
 
 using namespace bla;
-
-#define BLA_ENTER()                       \
-	bla_status st = require_ready();      \
-	if (st) return st;
 
 extern "C" {
 
@@ -192,148 +193,7 @@ bla_status bla_softmax_ddx_f32(void* stream, const float* d_softmax_output, cons
 	BLA_REQUIRE(rows >= 0 && dim >= 0, BLA_ERR_INVALID, "bad shape %dx%d", rows, dim);
 	if (rows == 0 || dim == 0) return BLA_OK;
 	BLA_REQUIRE(d_softmax_output && d_gradient && d_out, BLA_ERR_INVALID, "null operand");
-	hipLaunchKernelGGL(softmax_ddx_kernel, dim3((rows + 3) / 4), dim3(kT), 0, pick_stream(stream), d_softmax_output, d_gradient, d_out, rows, dim, 1.f);
-	BLA_HIP(hipGetLastError());
-	return BLA_OK;
-}
-
-/* ---- self-attention block, model/cifar_unet.c:999-1022 / :1261-1337, device-resident, intended composition --------
- * x, out, del_y, del_x: [C][S] (S = H*W); wq/wk/wv: [C][d]; w: [d][C]; bias: [C].  Every matrix_transpose the reference
- * materialises (9 of them) and both channel reshapes disappear into the GEMM's transa/transb: the [S][C] "input" matrix
- * is X^T, so Z.Wq is a TN product on X itself, and output = dense^T comes straight out of a TT product. */
-static bla_status ep_gemm(void* s, int ta, int tb, int m, int n, int k, const float* A, int lda, const float* B, int ldb, float* C, int ldc, float alpha,
-                          float beta, const float* bias_row) {
-	bla_gemm_epilogue ep = {};
-	ep.alpha = alpha; ep.beta = beta; ep.bias_row = bias_row;
-	return bla_gemm_f32(s, ta, tb, m, n, k, A, lda, B, ldb, C, ldc, &ep);
-}
-
-// two independent products in one launch where both are latency-bound shapes (bla_gemm_pair_f32); plain alpha/beta epilogues
-static bla_status pair_gemm(void* s, int ta1, int tb1, int m1, int n1, int k1, const float* A1, int lda1, const float* B1, int ldb1, float* C1, int ldc1,
-                            int ta2, int tb2, int m2, int n2, int k2, const float* A2, int lda2, const float* B2, int ldb2, float* C2, int ldc2, float alpha2 = 1.f) {
-	bla_gemm_epilogue e1 = {}, e2 = {};
-	e1.alpha = 1.f; e2.alpha = alpha2;
-	bla_gemm_desc p = {ta1, tb1, m1, n1, k1, A1, lda1, B1, ldb1, C1, ldc1, &e1};
-	bla_gemm_desc q = {ta2, tb2, m2, n2, k2, A2, lda2, B2, ldb2, C2, ldc2, &e2};
-	return bla_gemm_pair_f32(s, &p, &q);
-}
-
-bla_status bla_attention_forward_f32(void* stream, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv, const float* d_w,
-                                     const float* d_bias, const bla_attention_ws* ws, float* d_out, int c, int s, int d) {
-	BLA_ENTER();
-	BLA_REQUIRE(c > 0 && s > 0 && d > 0, BLA_ERR_INVALID, "bad attention shape C=%d S=%d d=%d", c, s, d);
-	BLA_REQUIRE(d_x && d_wq && d_wk && d_wv && d_w && d_bias && d_out && ws && ws->q && ws->k && ws->v && ws->scores_raw && ws->weights && ws->attention,
-	            BLA_ERR_INVALID, "null operand");
-	const float inv = (float)(1.0 / sqrt((double)d));                                                  // :1010
-	st = pair_gemm(stream, 1, 0, s, d, c, d_x, s, d_wq, d, ws->q, d,                                       // Q = Z Wq, Z = X^T   :1003-1004
-	               1, 0, s, d, c, d_x, s, d_wk, d, ws->k, d); if (st) return st;                          // beside K = Z Wk (one launch)
-	st = ep_gemm(stream, 1, 0, s, d, c, d_x, s, d_wv, d, ws->v, d, 1.f, 0.f, nullptr); if (st) return st;
-	{   // (Q K^T) / sqrt(d) :1007-1014, stored twice by the product itself: scores_raw (kept) and weights (softmaxed in place, :1015)
-		bla_gemm_epilogue ep = {};
-		ep.alpha = inv; ep.pre_act = ws->scores_raw; ep.ld_pre = s;
-		st = bla_gemm_f32(stream, 0, 1, s, s, d, ws->q, d, ws->k, d, ws->weights, s, &ep); if (st) return st;
-	}
-	st = bla_softmax_rows_f32(stream, ws->weights, s, s); if (st) return st;                               // :1015
-	st = ep_gemm(stream, 0, 0, s, d, s, ws->weights, s, ws->v, d, ws->attention, d, 1.f, 0.f, nullptr); if (st) return st;   // :1018
-	return ep_gemm(stream, 1, 1, c, s, d, d_w, c, ws->attention, d, d_out, s, 1.f, 0.f, d_bias);              // (P W + b)^T   :1019-1021
-}
-
-bla_status bla_attention_backward_f32(void* stream, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv,
-                                      const float* d_w, const bla_attention_ws* fw, const bla_attention_ws* g, float* d_del_wq, float* d_del_wk,
-                                      float* d_del_wv, float* d_del_w, float* d_del_x, int c, int s, int d, int jacobian_from_raw) {
-	BLA_ENTER();
-	BLA_REQUIRE(c > 0 && s > 0 && d > 0, BLA_ERR_INVALID, "bad attention shape C=%d S=%d d=%d", c, s, d);
-	BLA_REQUIRE(d_del_y && d_x && d_wq && d_wk && d_wv && d_w && fw && g && d_del_wq && d_del_wk && d_del_wv && d_del_w && d_del_x, BLA_ERR_INVALID, "null operand");
-	BLA_REQUIRE(g->q && g->k && g->v && g->scores_raw && g->weights && g->attention, BLA_ERR_INVALID, "null gradient workspace");
-	const float inv = (float)(1.0 / sqrt((double)d));
-	float *del_q = g->q, *del_k = g->k, *del_v = g->v, *del_i = g->scores_raw, *del_s = g->weights, *del_p = g->attention;
-	// independent products share a launch (the reference runs all fourteen one after the other)
-	st = pair_gemm(stream, 1, 1, d, c, s, fw->attention, d, d_del_y, s, d_del_w, c,                                          // del_W = P^T del_Y'     :1291-1293
-	               1, 1, s, d, c, d_del_y, s, d_w, c, del_p, d); if (st) return st;                                         // del_P = del_Y' W^T     :1295-1297
-	st = pair_gemm(stream, 0, 1, s, s, d, del_p, d, fw->v, d, del_s, s,                                                     // del_S = del_P V^T      :1303-1305
-	               1, 0, s, d, s, fw->weights, s, del_p, d, del_v, d); if (st) return st;                                   // del_V = S^T del_P      :1299-1301
-	st = bla_softmax_ddx_f32(stream, jacobian_from_raw ? fw->scores_raw : fw->weights, del_s, del_i, s, s); if (st) return st;   // :1307
-	st = bla_scale_f32(stream, del_i, (size_t)s * s, inv); if (st) return st;                                                // :1308
-	st = pair_gemm(stream, 0, 0, s, d, s, del_i, s, fw->k, d, del_q, d,                                                     // :1310
-	               1, 0, s, d, s, del_i, s, fw->q, d, del_k, d); if (st) return st;                                         // :1312-1314
-	st = pair_gemm(stream, 0, 0, c, d, s, d_x, s, del_k, d, d_del_wk, d,                                                    // Z^T = X              :1316-1319
-	               0, 0, c, d, s, d_x, s, del_q, d, d_del_wq, d); if (st) return st;
-	st = pair_gemm(stream, 0, 0, c, d, s, d_x, s, del_v, d, d_del_wv, d,
-	               0, 1, c, s, d, d_wq, d, del_q, d, d_del_x, s); if (st) return st;                                        // del_Z^T, same add order :1322-1334
-	st = ep_gemm(stream, 0, 1, c, s, d, d_wk, d, del_k, d, d_del_x, s, 1.f, 1.f, nullptr); if (st) return st;
-	return ep_gemm(stream, 0, 1, c, s, d, d_wv, d, del_v, d, d_del_x, s, 1.f, 1.f, nullptr);
-}
-
-/* The same block for a batch of images, x / out [B][C][S], every workspace buffer B times the single-image size.  Each per-image product becomes
- * one launch over the batch (bla_gemm_batched_f32); the four weight gradients are summed over the images from per-image products (d_partials:
- * [B][C*d] scratch). */
-static bla_status bgemm(void* s, int ta, int tb, int m, int n, int k, const float* A, int lda, long sa, const float* B, int ldb, long sb, float* C, int ldc, long sc,
-                        int batch, float alpha = 1.f, float beta = 0.f, const float* bias_row = nullptr, float* pre = nullptr, int ld_pre = 0, long spre = 0) {
-	bla_gemm_epilogue ep = {};
-	ep.alpha = alpha; ep.beta = beta; ep.bias_row = bias_row; ep.pre_act = pre; ep.ld_pre = ld_pre;
-	return bla_gemm_batched_f32(s, ta, tb, m, n, k, A, lda, sa, B, ldb, sb, C, ldc, sc, batch, &ep, spre);
-}
-
-bla_status bla_attention_forward_batched_f32(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv, const float* d_w,
-                                             const float* d_bias, const bla_attention_ws* ws, float* d_out, int c, int s, int d) {
-	if (batch == 1) return bla_attention_forward_f32(stream, d_x, d_wq, d_wk, d_wv, d_w, d_bias, ws, d_out, c, s, d);
-	BLA_ENTER();
-	BLA_REQUIRE(batch > 0 && c > 0 && s > 0 && d > 0, BLA_ERR_INVALID, "bad attention shape B=%d C=%d S=%d d=%d", batch, c, s, d);
-	BLA_REQUIRE(d_x && d_wq && d_wk && d_wv && d_w && d_bias && d_out && ws && ws->q && ws->k && ws->v && ws->scores_raw && ws->weights && ws->attention,
-	            BLA_ERR_INVALID, "null operand");
-	const float inv = (float)(1.0 / sqrt((double)d));
-	const long xs = (long)c * s, qs = (long)s * d, ss = (long)s * s;
-	st = bgemm(stream, 1, 0, s, d, c, d_x, s, xs, d_wq, d, 0, ws->q, d, qs, batch); if (st) return st;                       // Q = Z Wq   :1003-1004
-	st = bgemm(stream, 1, 0, s, d, c, d_x, s, xs, d_wk, d, 0, ws->k, d, qs, batch); if (st) return st;
-	st = bgemm(stream, 1, 0, s, d, c, d_x, s, xs, d_wv, d, 0, ws->v, d, qs, batch); if (st) return st;
-	st = bgemm(stream, 0, 1, s, s, d, ws->q, d, qs, ws->k, d, qs, ws->weights, s, ss, batch, inv, 0.f, nullptr, ws->scores_raw, s, ss); if (st) return st;   // :1007-1014
-	st = bla_softmax_rows_f32(stream, ws->weights, batch * s, s); if (st) return st;                                       // :1015
-	st = bgemm(stream, 0, 0, s, d, s, ws->weights, s, ss, ws->v, d, qs, ws->attention, d, qs, batch); if (st) return st;     // :1018
-	return bgemm(stream, 1, 1, c, s, d, d_w, c, 0, ws->attention, d, qs, d_out, s, xs, batch, 1.f, 0.f, d_bias);             // :1019-1021
-}
-
-bla_status bla_attention_backward_batched_f32(void* stream, int batch, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk,
-                                              const float* d_wv, const float* d_w, const bla_attention_ws* fw, const bla_attention_ws* g, float* d_partials,
-                                              float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w, float* d_del_x, int c, int s, int d,
-                                              int jacobian_from_raw) {
-	if (batch == 1)
-		return bla_attention_backward_f32(stream, d_del_y, d_x, d_wq, d_wk, d_wv, d_w, fw, g, d_del_wq, d_del_wk, d_del_wv, d_del_w, d_del_x, c, s, d, jacobian_from_raw);
-	BLA_ENTER();
-	BLA_REQUIRE(batch > 0 && c > 0 && s > 0 && d > 0, BLA_ERR_INVALID, "bad attention shape B=%d C=%d S=%d d=%d", batch, c, s, d);
-	BLA_REQUIRE(d_del_y && d_x && d_wq && d_wk && d_wv && d_w && fw && g && d_partials && d_del_wq && d_del_wk && d_del_wv && d_del_w && d_del_x, BLA_ERR_INVALID, "null operand");
-	BLA_REQUIRE(g->q && g->k && g->v && g->scores_raw && g->weights && g->attention, BLA_ERR_INVALID, "null gradient workspace");
-	const float inv = (float)(1.0 / sqrt((double)d));
-	const long xs = (long)c * s, qs = (long)s * d, ss = (long)s * s, ws_ = (long)c * d;
-	float *del_q = g->q, *del_k = g->k, *del_v = g->v, *del_i = g->scores_raw, *del_s = g->weights, *del_p = g->attention;
-	st = bgemm(stream, 1, 1, d, c, s, fw->attention, d, qs, d_del_y, s, xs, d_partials, c, ws_, batch); if (st) return st;      // del_W = sum P^T del_Y'   :1291-1293
-	st = batch_sum(stream, d_partials, d_del_w, batch, (size_t)ws_); if (st) return st;
-	st = bgemm(stream, 1, 1, s, d, c, d_del_y, s, xs, d_w, c, 0, del_p, d, qs, batch); if (st) return st;                       // del_P = del_Y' W^T       :1295-1297
-	st = bgemm(stream, 0, 1, s, s, d, del_p, d, qs, fw->v, d, qs, del_s, s, ss, batch); if (st) return st;                      // del_S = del_P V^T        :1303-1305
-	st = bgemm(stream, 1, 0, s, d, s, fw->weights, s, ss, del_p, d, qs, del_v, d, qs, batch); if (st) return st;                // del_V = S^T del_P        :1299-1301
-	hipLaunchKernelGGL(softmax_ddx_kernel, dim3((batch * s + 3) / 4), dim3(kT), 0, pick_stream(stream), jacobian_from_raw ? fw->scores_raw : fw->weights, del_s, del_i,
-	                   batch * s, s, inv);                                                                                    // :1307-1308 in one pass
-	BLA_HIP(hipGetLastError());
-	st = bgemm(stream, 0, 0, s, d, s, del_i, s, ss, fw->k, d, qs, del_q, d, qs, batch); if (st) return st;                      // :1310
-	st = bgemm(stream, 1, 0, s, d, s, del_i, s, ss, fw->q, d, qs, del_k, d, qs, batch); if (st) return st;                      // :1312-1314
-	st = bgemm(stream, 0, 0, c, d, s, d_x, s, xs, del_k, d, qs, d_partials, d, ws_, batch); if (st) return st;                  // Z^T = X                :1316-1319
-	st = batch_sum(stream, d_partials, d_del_wk, batch, (size_t)ws_); if (st) return st;
-	st = bgemm(stream, 0, 0, c, d, s, d_x, s, xs, del_q, d, qs, d_partials, d, ws_, batch); if (st) return st;
-	st = batch_sum(stream, d_partials, d_del_wq, batch, (size_t)ws_); if (st) return st;
-	st = bgemm(stream, 0, 0, c, d, s, d_x, s, xs, del_v, d, qs, d_partials, d, ws_, batch); if (st) return st;
-	st = batch_sum(stream, d_partials, d_del_wv, batch, (size_t)ws_); if (st) return st;
-	if (gemm_thin_applies(c, s, d, batch)) {   // the three d-deep terms of del_Z^T accumulate in registers (q, then k, then v) and are stored once  :1322-1334
-		const ThinPart parts[3] = {{d_wq, del_q, 0, qs, d, d}, {d_wk, del_k, 0, qs, d, d}, {d_wv, del_v, 0, qs, d, d}};
-		st = gemm_thin_parts(stream, 0, 1, c, s, d, parts, 3, d_del_x, s, xs, batch, 1.f, 0.f, nullptr, nullptr, 0, 0);
-		if (st == BLA_OK) {   // (gemm_thin_parts is below bla_gemm_batched_f32, which names its own launches: without this bla_gemm_last_kernel() still showed del_Wv's product)
-			char name[64];
-			snprintf(name, sizeof(name), "gemm_f32_thin_nt_x%d_parts3", batch);
-			gemm_note_last_kernel(name);
-		}
-		return st;
-	}
-	st = bgemm(stream, 0, 1, c, s, d, d_wq, d, 0, del_q, d, qs, d_del_x, s, xs, batch); if (st) return st;                      // del_Z^T, same add order :1322-1334
-	st = bgemm(stream, 0, 1, c, s, d, d_wk, d, 0, del_k, d, qs, d_del_x, s, xs, batch, 1.f, 1.f); if (st) return st;
-	return bgemm(stream, 0, 1, c, s, d, d_wv, d, 0, del_v, d, qs, d_del_x, s, xs, batch, 1.f, 1.f);
+	return softmax_ddx_launch(stream, d_softmax_output, d_gradient, d_out, rows, dim, 1.f);
 }
 
 bla_status bla_sum_f32(void* stream, float* d_out, const float* d_a, const float* d_b, size_t n) {

@@ -1,4 +1,4 @@
-// bla_unet_model.hip -- the reference's U-Net (model/cifar_unet.c) assembled from the device-resident blocks of bla_unet.hip:
+// bla_unet_model.hip -- the reference's U-Net (model/cifar_unet.c) assembled from the device-resident blocks of bla_unet.hip and bla_attention_*.hip:
 // forward() (:1099-1166) and backward() (:1351-1436) for one image -- or for a batch of images at once (bla_unet_create_batched: every
 // activation carries a leading image index, every image its own time embedding, the gradients are summed over the images: what a mini-batch
 // of the reference's one-image-at-a-time loop accumulates) -- parameters and gradients in two flat buckets.
@@ -25,7 +25,7 @@
 // The wiring stands in ONE place, the step list kNetwork, and three walkers read it: bla_unet_create_heads forwards (parameter bucket, tensor names, dropout
 // offsets; then every step's buffers and its input / output / skip pointers), bla_unet_forward_f32 forwards, unet_backward in reverse.  A change of topology is
 // an edit of kNetwork (and of res[18] / att[5] / kEmbSplit if the number of blocks changes).  What the two product stacks do differently is one table of calls
-// (Stack), chosen at create; attention is chosen per call (bla_unet_set_attention).
+// (Stack), chosen at create; which entries an attention block runs on is its stored route, decided in att_route (at create and by bla_unet_set_attention).
 #include "bla_internal.h"
 #include <algorithm>
 #include <cstring>
@@ -51,8 +51,10 @@ struct Res {
 };
 // one ResNet block's time-embedding projection (model/cifar_unet.c:1051-1052) and its gradients (:1191-1199); all 18 run as one launch each way
 struct TimeJob { const float* w; const float* bias; float* tdense; const float* dtb; float* g_tw; float* g_tb; int cout; };
+enum AttRoute { ROUTE_NONE, ROUTE_F32, ROUTE_BF16, ROUTE_ONLINE, ROUTE_F32_HEADS, ROUTE_ONLINE_HEADS };   // the entries an attention block runs on (att_route)
 struct Att {
 	int c, h, w;
+	AttRoute route;   // decided by att_route at create and at every bla_unet_set_attention
 	size_t wq, wk, wv, wo, bias;
 	bla_attention_ws fwd;
 	float* out;
@@ -260,25 +262,17 @@ bla_status alloc_res(bla_unet* m, Res& r) {
 	}
 	return BLA_OK;
 }
-// several heads: q, k, v, attention at the block's width; one float per (image, head, row) -- the row log-sum-exp of the online entries, in the
-// gradient workspace their row dots -- in scores_raw; P [B][heads][S][S] only where the fp32 heads entries will run (with_p), never in the gradient workspace
-bla_status alloc_att_ws_heads(bla_unet* m, bla_attention_ws& ws, size_t s, bool with_p) {
+// an attention workspace for sequences of s: q, k, v, attention [B][s][heads key_dim], then the two buffers whose floats the caller states (weights: 0 for none).
+// One head: both B s s (scores and P; the bf16 entries keep row statistics at the head of scores_raw) under EVERY mode: a later switch must work (DESIGN 3.29
+// "Open").  Several heads (3.31): scores_raw one float per (image, head, row), the online entries' statistics; P only in a block the fp32 heads entries apply to.
+bla_status alloc_att_ws(bla_unet* m, bla_attention_ws& ws, size_t s, size_t scores_raw, size_t weights) {
 	bla_status st;
-	const size_t B = m->batch, heads = m->heads, width = heads * m->cfg.key_dim;
+	const size_t n = (size_t)m->batch * s * m->heads * m->cfg.key_dim;
 	ws = bla_attention_ws{};
-	if ((st = dalloc(m, &ws.q, B * s * width)) || (st = dalloc(m, &ws.k, B * s * width)) || (st = dalloc(m, &ws.v, B * s * width)) ||
-	    (st = dalloc(m, &ws.attention, B * s * width)) || (st = dalloc(m, &ws.scores_raw, B * heads * s)))
+	if ((st = dalloc(m, &ws.q, n)) || (st = dalloc(m, &ws.k, n)) || (st = dalloc(m, &ws.v, n)) || (st = dalloc(m, &ws.attention, n)) ||
+	    (st = dalloc(m, &ws.scores_raw, scores_raw)))
 		return st;
-	return with_p ? dalloc(m, &ws.weights, B * heads * s * s) : BLA_OK;
-}
-bla_status alloc_att_ws(bla_unet* m, bla_attention_ws& ws, size_t s1, size_t d) {
-	bla_status st;
-	const size_t s = s1, ss = s1 * s1 * m->batch;
-	d *= m->batch;
-	if ((st = dalloc(m, &ws.q, s * d)) || (st = dalloc(m, &ws.k, s * d)) || (st = dalloc(m, &ws.v, s * d)) || (st = dalloc(m, &ws.attention, s * d)) ||
-	    (st = dalloc(m, &ws.scores_raw, ss)) || (st = dalloc(m, &ws.weights, ss)))
-		return st;
-	return BLA_OK;
+	return weights ? dalloc(m, &ws.weights, weights) : BLA_OK;
 }
 
 // tdense[b][c] = sum_t temb[b][t] W[t][c] + bias[c] for every block at once: grid (block, 8 images, 64 channels); a workgroup = 64 channels x 4 quarters of
@@ -457,39 +451,50 @@ bla_status conv_backward_f32(bla_unet* m, void* stream, const Conv& k, const flo
 bla_status conv_backward_bf16(bla_unet* m, void* stream, const Conv& k, const float* g, const float* x, float* out) {
 	return conv2d_backward_gathered_as_bf16(stream, g, x, m->params + k.kern, m->grads + k.kern, out, m->batch, k.h, k.w, k.k, k.cin, k.cout, k.stride, 0, k.prep16_bwd);
 }
-// attention: by the model's mode and the block's shape, asked at every call (bla_unet_set_attention may come after create)
-bool att_on_bf16(const bla_unet* m, const Att& a) { return m->attention == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(a.c, a.h * a.w, m->cfg.key_dim); }
-// (the online entries keep the row log-sum-exp in the first B S floats of the block's scores_raw and the row dots in agrad's: both are B S S floats)
-bool att_on_online(const bla_unet* m, const Att& a) {
-	return m->attention == BLA_UNET_ATTENTION_BF16_ONLINE && bla_attention_online_bf16_applies(a.c, a.h * a.w, m->cfg.key_dim);
-}
-// several heads: the fp32 heads entries where they apply (S <= 64), else the online ones -- under BLA_UNET_ATTENTION_BF16_ONLINE the other way round.  Create
-// has made sure that one of the two accepts every block, so a long block is bf16-online in BOTH modes.
-bool heads_fit_f32(const bla_unet* m, const Att& a) { return bla_attention_f32_heads_applies(a.c, a.h * a.w, m->heads, m->cfg.key_dim); }
-bool heads_fit_online(const bla_unet* m, const Att& a) { return bla_attention_online_bf16_heads_applies(a.c, a.h * a.w, m->heads, m->cfg.key_dim); }
-bool heads_on_online(const bla_unet* m, const Att& a) {
-	return m->attention == BLA_UNET_ATTENTION_BF16_ONLINE ? heads_fit_online(m, a) : !heads_fit_f32(m, a);
+// THE ROUTING RULE, stated once: the entries a block of c channels and s positions runs on under `mode`, with `heads` heads of width d.
+//   one head:      the mode's bf16 entries where they apply to the shape, else fp32, which takes any shape (never ROUTE_NONE);
+//   several heads: where both the fp32 heads entries (S <= 64) and the online ones apply, the mode chooses; else the one that applies, under EVERY mode -- a long
+//                  block is bf16-online under both modes.  ROUTE_NONE: neither applies, so no mode can run the block (BLA_UNET_ATTENTION_BF16 has no heads).
+AttRoute att_route(int mode, int heads, int c, int s, int d) {
+	const bool online_mode = mode == BLA_UNET_ATTENTION_BF16_ONLINE;
+	if (heads == 1)
+		return online_mode && bla_attention_online_bf16_applies(c, s, d) ? ROUTE_ONLINE : mode == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(c, s, d) ? ROUTE_BF16 : ROUTE_F32;
+	const bool f32 = bla_attention_f32_heads_applies(c, s, heads, d), online = bla_attention_online_bf16_heads_applies(c, s, heads, d);
+	if (f32 && online) return online_mode ? ROUTE_ONLINE_HEADS : ROUTE_F32_HEADS;
+	return f32 ? ROUTE_F32_HEADS : online ? ROUTE_ONLINE_HEADS : ROUTE_NONE;
 }
 bla_status att_forward(bla_unet* m, void* stream, Att& a, const float* in) {
 	const float* P = m->params;
-	if (m->heads > 1)
-		return (heads_on_online(m, a) ? bla_attention_forward_batched_online_bf16_heads : bla_attention_forward_batched_f32_heads)(
-			stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, m->heads, m->cfg.key_dim);
-	return (att_on_online(m, a) ? bla_attention_forward_batched_online_bf16 : att_on_bf16(m, a) ? bla_attention_forward_batched_bf16 : bla_attention_forward_batched_f32)(
-		stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, a.h * a.w, m->cfg.key_dim);
+	const int s = a.h * a.w, d = m->cfg.key_dim;
+	switch (a.route) {
+	case ROUTE_F32: case ROUTE_BF16: case ROUTE_ONLINE:
+		return (a.route == ROUTE_F32 ? bla_attention_forward_batched_f32 : a.route == ROUTE_BF16 ? bla_attention_forward_batched_bf16 : bla_attention_forward_batched_online_bf16)(
+			stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, s, d);
+	case ROUTE_F32_HEADS: case ROUTE_ONLINE_HEADS:
+		return (a.route == ROUTE_F32_HEADS ? bla_attention_forward_batched_f32_heads : bla_attention_forward_batched_online_bf16_heads)(
+			stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, s, m->heads, d);
+	case ROUTE_NONE: break;   // (create refuses such a model)
+	}
+	set_error("attention block without a route");
+	return BLA_ERR_INVALID;
 }
 bla_status att_backward(bla_unet* m, void* stream, Att& a, const float* g, const float* x, float* out) {
 	const float* P = m->params; float* G = m->grads;
-	const int d = m->cfg.key_dim;
-	if (m->heads > 1)
-		return (heads_on_online(m, a) ? bla_attention_backward_batched_online_bf16_heads : bla_attention_backward_batched_f32_heads)(
-			stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv, G + a.wo, out, a.c, a.h * a.w,
-			m->heads, d);
-	if (att_on_online(m, a) || att_on_bf16(m, a))
-		return (att_on_online(m, a) ? bla_attention_backward_batched_online_bf16 : bla_attention_backward_batched_bf16)(
-			stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv, G + a.wo, out, a.c, a.h * a.w, d);
-	return bla_attention_backward_batched_f32(stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv,
-	                                          G + a.wo, out, a.c, a.h * a.w, d, 0);
+	const int s = a.h * a.w, d = m->cfg.key_dim;
+	switch (a.route) {
+	case ROUTE_F32:
+		return bla_attention_backward_batched_f32(stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk,
+		                                          G + a.wv, G + a.wo, out, a.c, s, d, 0);
+	case ROUTE_BF16: case ROUTE_ONLINE:
+		return (a.route == ROUTE_BF16 ? bla_attention_backward_batched_bf16 : bla_attention_backward_batched_online_bf16)(
+			stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv, G + a.wo, out, a.c, s, d);
+	case ROUTE_F32_HEADS: case ROUTE_ONLINE_HEADS:
+		return (a.route == ROUTE_F32_HEADS ? bla_attention_backward_batched_f32_heads : bla_attention_backward_batched_online_bf16_heads)(
+			stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv, G + a.wo, out, a.c, s, m->heads, d);
+	case ROUTE_NONE: break;
+	}
+	set_error("attention block without a route");
+	return BLA_ERR_INVALID;
 }
 // floats per image of a map at the width and size of resolution `level`: a tapped output, one half of a concatenation
 size_t level_floats(const bla_unet* m, int level) { return (size_t)m->cfg.dims[level] * m->H[level] * m->W[level]; }
@@ -613,7 +618,8 @@ bla_status bla_unet_set_attention(bla_unet* m, int mode) {
 	BLA_REQUIRE(m, BLA_ERR_INVALID, "null argument");
 	BLA_REQUIRE(m->heads == 1 || mode != BLA_UNET_ATTENTION_BF16, BLA_ERR_INVALID,
 	            "bla_unet_set_attention: BLA_UNET_ATTENTION_BF16 on a model with %d heads (the materialising bf16 block has none)", m->heads);
-	m->attention = mode;
+	m->attention = mode;   // (no route is ROUTE_NONE: create has made sure that some path takes every block under every mode accepted here)
+	for (Att& a : m->att) a.route = att_route(mode, m->heads, a.c, a.h * a.w, m->cfg.key_dim);
 	return BLA_OK;
 }
 
@@ -659,13 +665,12 @@ bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int
 	}
 
 	auto fail = [&](bla_status s) { (void)bla_unet_destroy(m); return s; };
-	if (heads > 1)   // every block needs one of the two multi-head paths (before anything is allocated)
-		for (const Att& a : m->att)
-			if (!heads_fit_f32(m, a) && !heads_fit_online(m, a)) {
-				set_error("bla_unet_create_heads: no multi-head attention path for C=%d S=%d heads=%d d=%d (fp32: S <= 64; online bf16: S %% 32 == 0, d %% 8 == 0, C %% 8 == 0)",
-				          a.c, a.h * a.w, heads, cfg->key_dim);
-				return fail(BLA_ERR_INVALID);
-			}
+	for (Att& a : m->att)   // every block's route under the default mode; ROUTE_NONE: under no mode (several heads, neither multi-head path) -- before anything is allocated
+		if ((a.route = att_route(m->attention, heads, a.c, a.h * a.w, cfg->key_dim)) == ROUTE_NONE) {
+			set_error("bla_unet_create_heads: no multi-head attention path for C=%d S=%d heads=%d d=%d (fp32: S <= 64; online bf16: S %% 32 == 0, d %% 8 == 0, C %% 8 == 0)",
+			          a.c, a.h * a.w, heads, cfg->key_dim);
+			return fail(BLA_ERR_INVALID);
+		}
 	if ((st = dalloc_zeroed(m, &m->params, m->count)) || (st = dalloc_zeroed(m, &m->grads, m->count))) return fail(st);
 	size_t max_act = 0, max_s = 0, max_flip = 0, max_cout_hw = 0, max_cin_hw = 0, max_cd = 1;
 	for (Res& r : m->res) {
@@ -680,6 +685,7 @@ bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int
 	}
 	// the other steps' buffers, and every step's input, output and skip: a step reads what the step before it wrote
 	float* prev = nullptr;   // the model's input
+	const bool one_head = heads == 1;   // the attention workspaces (alloc_att_ws): one head keeps S x S scores and P, several one float a row and P where fp32 runs
 	for (Step& s : m->steps) {
 		const int l = s.level;
 		const size_t n = B * level_floats(m, l);   // a map of the level's own width
@@ -689,7 +695,9 @@ bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int
 		case ATT: {
 			Att& a = m->att[s.index];
 			const size_t sp = (size_t)a.h * a.w;
-			if ((st = heads > 1 ? alloc_att_ws_heads(m, a.fwd, sp, heads_fit_f32(m, a)) : alloc_att_ws(m, a.fwd, sp, cfg->key_dim)) || (st = dalloc(m, &a.out, B * a.c * sp)))
+			// (under the default mode ROUTE_F32_HEADS is exactly "the fp32 heads entries apply": those blocks own P, whatever the mode turns to)
+			if ((st = alloc_att_ws(m, a.fwd, sp, B * heads * sp * (one_head ? sp : 1), one_head || a.route == ROUTE_F32_HEADS ? B * heads * sp * sp : 0)) ||
+			    (st = dalloc(m, &a.out, B * a.c * sp)))
 				return fail(st);
 			max_s = std::max(max_s, sp); max_cd = std::max(max_cd, (size_t)a.c * cfg->key_dim * heads);
 			s.out = a.out;
@@ -731,7 +739,7 @@ bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int
 	}
 	if ((st = dalloc(m, &m->ring[0], max_act)) || (st = dalloc(m, &m->ring[1], max_act)) || (st = dalloc(m, &m->ring[2], max_act)) || (st = dalloc(m, &m->sc.g_out_a, max_cout_hw)) ||
 	    (st = dalloc(m, &m->sc.g_out_b, max_cout_hw)) || (st = dalloc(m, &m->sc.g_in, max_cin_hw)) || (st = dalloc(m, &m->sc.flip, max_flip)) ||
-	    (st = heads > 1 ? alloc_att_ws_heads(m, m->agrad, max_s, false) : alloc_att_ws(m, m->agrad, max_s, cfg->key_dim)) || (st = dalloc(m, &m->dtb, B * m->max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
+	    (st = alloc_att_ws(m, m->agrad, max_s, B * heads * max_s * (one_head ? max_s : 1), one_head ? B * max_s * max_s : 0)) || (st = dalloc(m, &m->dtb, B * m->max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
 		return fail(st);
 	if ((st = dalloc_zeroed(m, &m->zero_drop, B * m->drop_count))) return fail(st);
 	{   // the 18 time-embedding projections (and, for a batch, their gradients) as one launch each way (eight embedding rows in LDS), and the embedding gradient's

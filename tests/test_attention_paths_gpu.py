@@ -1,4 +1,4 @@
-"""The fp32 self-attention block (bla_attention_{forward,backward}[_batched]_f32, csrc/bla_unet.hip) at shapes off the three golden ones, against float64.
+"""The fp32 self-attention block (bla_attention_{forward,backward}[_batched]_f32, csrc/bla_attention_f32.hip) at shapes off the three golden ones, against float64.
 
 The reference is always oracle.attention_forward / attention_backward in float64, image by image; a batch's weight gradients are the float64 sums over its
 images.  The single-image device block is never the reference.  Checked: every saved forward tensor (q, k, v, scores_raw, weights, attention, out), the five

@@ -6,6 +6,8 @@ CFG, batch 2, 2 heads of width 8), parameters, inputs, the float64 networks and 
   multi-head block: predictions 1e-4 normwise, gradient tensors 1e-2 (tests/test_unet_model.py's bounds).  Mode 3 moves the level-1 blocks onto the online
   bf16 heads entries: other bits, every gradient tensor within 0.25 normwise of mode 0's (DESIGN 3.29's model bound), bit-reproducible, and mode 0 afterwards
   gives the first bits again.
+* The blocks' stored routes follow every switch: mode 0, mode 3, mode 0 gives the first bits again; mode 3's are those of a fresh model put under mode 3
+  before its first pass; a refused switch to BLA_UNET_ATTENTION_BF16 changes nothing of the next pass.
 * 32 x 32 images, fp32 products: level-1 S = 256 runs the online heads entries in BOTH modes, mid S = 16 the fp32 heads entries in both (the online predicate
   refuses it) -- so the two modes are bit-equal.  Per tensor the device lies within twice the host-recorded ||rounded - exact|| / ||exact|| (DESIGN 3.25 - 3.30's
   margin); the one tensor whose recorded value depends on the draw of the roundings (host.DRAW_DEPENDENT) within 0.25 normwise instead.
@@ -128,6 +130,26 @@ def test_16x16_against_the_float64_network_and_the_online_mode(dev):
     back = m.one_pass(data, dev.UNET_ATTENTION_F32)
     assert np.array_equal(back[0], out) and np.array_equal(back[1], grads)
     m.destroy()
+
+
+def test_stored_routes_follow_every_switch(dev):
+    """Every attention block keeps the route bla_unet_set_attention last decided for it: a route left behind by an earlier mode would show as other bits.
+    16 x 16, batch 2, 2 heads, fp32 products: the level-1 blocks (S = 64) move between the fp32 heads and the online heads entries, the mid block (S = 4) stays."""
+    cfg = host.cfg_at(16)
+    P, data, L = host.make_params(cfg), device_inputs(dev, cfg), dev.lib()
+    m, fresh = Model(dev, cfg, F32, HEADS, P), Model(dev, cfg, F32, HEADS, P)
+
+    def same(p, q):
+        return np.array_equal(p[0], q[0]) and np.array_equal(p[1], q[1])
+    first = m.one_pass(data)
+    second = m.one_pass(data, dev.UNET_ATTENTION_BF16_ONLINE)
+    third = m.one_pass(data, dev.UNET_ATTENTION_F32)
+    assert np.isfinite(first[1]).all() and np.abs(first[1]).max() > 0 and not same(second, first)
+    assert same(third, first)
+    assert same(second, fresh.one_pass(data, dev.UNET_ATTENTION_BF16_ONLINE))      # a model that was never under another mode
+    assert L.bla_unet_set_attention(m.h, dev.UNET_ATTENTION_BF16) == 1 and b"heads" in L.bla_last_error() and L.bla_unet_attention(m.h) == dev.UNET_ATTENTION_F32
+    assert same(m.one_pass(data), third)                                           # the refused switch left mode and routes alone
+    m.destroy(); fresh.destroy()
 
 
 def test_32x32_within_twice_the_recorded_rounding(dev):
