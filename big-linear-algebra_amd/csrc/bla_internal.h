@@ -106,6 +106,8 @@ bla_status conv_prepare_kernels(void* stream, const KernelPrepJob* d_jobs, int n
 struct PadLayout { int w, wh, plane, pt, pl; };      // plane = 0: none
 PadLayout conv_padded_layout(int h, int w, int k, int stride);
 struct PadOut { float* dst; PadLayout L; };          // a producer's second output: dst[plane_index * L.plane + (y + L.pt) * L.wh + x + L.pl], halo zeroed once by the owner
+// the padding pass itself: dst [planes][s][s][hh][wh] = src [planes][h][w] with its (pt, pl) padding, cut into s x s parity planes (s = 1: plain padding)
+void launch_pad_split(hipStream_t st, const float* src, float* dst, unsigned planes, int h, int w, int pt, int pl, int s, unsigned hh, unsigned wh);
 
 // bla_conv_last_plan(): what the last conv2d_forward / conv2d_backward call launched, one token per product (bla.h has the grammar).  Host side only: the
 // entry resets the record, says whose product comes next (role: fwd, wgrad, dgrad, dgrad.dil) and every launch site of the family writes its part
@@ -139,12 +141,17 @@ bool gemm_thin_applies(int m, int n, int k, int batch);
 bla_status gemm_thin_parts(void* stream, int transa, int transb, int m, int n, int k, const ThinPart* parts, int nparts, float* C, int ldc, long stride_c, int batch,
                            float alpha, float beta, const float* bias_row, float* pre, int ld_pre, long stride_pre);
 
-// group norm + ReLU + dropout in one pass (relu = max(norm, 0), dropped = drop ? 0 : relu), model/cifar_unet.c:1056-1058
+// bla_group_norm.hip: group norm + ReLU + dropout in one pass (relu = max(norm, 0), dropped = drop ? 0 : relu), model/cifar_unet.c:1056-1058
 bla_status group_norm_relu_dropout(void* stream, const float* d_in, float* d_relu, const unsigned char* d_drop, float* d_dropped, float* d_stdevs, float* d_means,
                                    int channels, int group_size, int hw, const PadOut* pad = nullptr);   // d_drop may be NULL with pad (then the padded copy holds the ReLU output)
 // group_norm_ddx with the ReLU gate on its input and the residual gradient added to its output (either may be NULL), model/cifar_unet.c:1204-1205,1219
 bla_status group_norm_ddx_gated(void* stream, const float* d_source, float* d_dest, const float* d_data, const float* d_means, const float* d_stdevs,
                                 int channels, int group_size, int hw, const float* d_relu_gate, const float* d_addend, const PadOut* pad = nullptr);
+// the two over a batch [B][C][HW]; pad is written, and *pad_done says so, only when the batch folds into the channel count (every shape of the U-Net does)
+bla_status group_norm_relu_dropout_batched(void* stream, int batch, const float* in, float* out, float* sd, float* mu, int c, int gs, int hw, const unsigned char* drop,
+                                           float* dropped, const PadOut* pad = nullptr, bool* pad_done = nullptr);
+bla_status group_norm_ddx_gated_batched(void* stream, int batch, const float* src, float* dst, const float* data, const float* mu, const float* sd, int c, int gs, int hw,
+                                        const float* gate, const float* addend, const PadOut* pad = nullptr, bool* pad_done = nullptr);
 
 // bla_unet.hip: the batched ResNet block with the time-embedding projection hoisted out (bla_unet_model.hip forms all blocks' projections / time gradients in
 // one launch each): RESNET_TDENSE_READY = ws->tdense is already filled; RESNET_DEFER_TIME_GRADS = only the per-image channel sums go to d_dtb

@@ -1,7 +1,7 @@
 // bla_norm_bf16.hip -- group norm and its gradient with a channel-last bf16 output (include/bla.h, "group norm into a bf16 map").
 //
 // The bf16 convolutions gather from a padded channel-last map [B][Hp][Wp][Cp]; inside a ResNet block that map is the output of a group norm, which the fp32
-// family writes planar.  The two entries here run the fp32 family's arithmetic (csrc/bla_conv.hip, quirk Q3 kept: `stdevs` holds the variance and the
+// family writes planar.  The two entries here run the fp32 family's arithmetic (csrc/bla_group_norm.hip, quirk Q3 kept: `stdevs` holds the variance and the
 // output is divided by it) and store the result where the next product reads it -- the store contract of bla_conv2d_gathered_bf16_chained.
 //   * stats launch: one 1024-thread workgroup per (image, group).  fp64 sums in a fixed order (a thread's elements ascending, the wave by shuffles, the
 //     sixteen waves ascending): the same call gives the same bits.  Forward: sum x and sum x^2 (x^2 is exact in fp64), m = (float)(sum x / n),

@@ -2,7 +2,7 @@
 // (model/cifar_unet.c:235-253,1024-1097,1168-1178,1229-1259), SURVEY 8(f) rank 1.  All HBM-bound, one pass each;
 // channel arrays are contiguous [C][H*W] buffers.  The adds of _nearest_neighbours_ddx are done in the reference's
 // order (row-major over the source block), so the fp32 result is bit-identical to the fp32 oracle.  Behind them the ResNet block, single-image and
-// batched, and the batched group norms.  The softmax Jacobian kernel serves bla_softmax_ddx_f32 and, through softmax_ddx_launch, other translation units.
+// batched (their group norms: bla_group_norm.hip).  The softmax Jacobian kernel serves bla_softmax_ddx_f32 and, through softmax_ddx_launch, other translation units.
 #include "bla_internal.h"
 
 namespace bla {
@@ -117,13 +117,6 @@ bla_status batch_sum(void* stream, const float* src, float* dst, int batch, size
 	hipLaunchKernelGGL(batch_sum_kernel, dim3(blocks_for(n)), dim3(kT), 0, pick_stream(stream), src, dst, batch, n);
 	BLA_HIP(hipGetLastError());
 	return BLA_OK;
-}
-// Group norm over a batch [B][C][HW]: the groups of one image never reach into the next, so the batch folds into the channel count when the
-// groups divide the channels (B*C channels, same groups) or when an image is one short group (groups of C).  false: ragged, image by image.
-static bool fold_groups(int batch, int c, int group_size, int* channels, int* group) {
-	if (c % group_size == 0) { *channels = batch * c; *group = group_size; return true; }
-	if (c < group_size) { *channels = batch * c; *group = c; return true; }
-	return batch == 1 ? (*channels = c, *group = group_size, true) : false;
 }
 }  // namespace bla
 
@@ -271,51 +264,6 @@ bla_status bla_resnet_backward_f32(void* stream, const float* d_del_out, const f
 /* The ResNet block for a batch: x / del_x [B][Cin][HW], result / del_out [B][Cout][HW], temb [B][T] (every image its own time step), d_drop
  * [B][Cout*HW]; the workspace buffers are B times the single-image sizes (tdense [B][Cout], mu / sd [B][groups]).  The convolutions run as
  * batched implicit GEMMs, the norms over B*C channels; the gradients are summed over the images.  d_dtb: [B][Cout] scratch. */
-// pad (optional): the padded copy of what this norm feeds the next convolution with, written in the same pass; *pad_done says whether it was (only when the
-// batch folds into the channel count -- every shape of the U-Net does)
-static bla_status gn_relu_b(void* stream, int batch, const float* in, float* out, float* sd, float* mu, int c, int gs, int hw, const unsigned char* drop, float* dropped,
-                            const PadOut* pad = nullptr, bool* pad_done = nullptr) {
-	int ch, grp;
-	if (pad_done) *pad_done = false;
-	if (fold_groups(batch, c, gs, &ch, &grp)) {
-		if ((pad && pad->dst) || !out) { if (pad_done) *pad_done = pad && pad->dst; return group_norm_relu_dropout(stream, in, out, drop, dropped, sd, mu, ch, grp, hw, pad); }
-		return drop ? group_norm_relu_dropout(stream, in, out, drop, dropped, sd, mu, ch, grp, hw) : bla_group_norm_relu_f32(stream, in, out, sd, mu, ch, grp, hw);
-	}
-	const int groups = (c + gs - 1) / gs;
-	for (int b = 0; b < batch; b++) {
-		const size_t o = (size_t)b * c * hw;
-		bla_status st = drop ? group_norm_relu_dropout(stream, in + o, out + o, drop + o, dropped + o, sd + (size_t)b * groups, mu + (size_t)b * groups, c, gs, hw)
-		                     : bla_group_norm_relu_f32(stream, in + o, out + o, sd + (size_t)b * groups, mu + (size_t)b * groups, c, gs, hw);
-		if (st) return st;
-	}
-	return BLA_OK;
-}
-static bla_status gn_ddx_b(void* stream, int batch, const float* src, float* dst, const float* data, const float* mu, const float* sd, int c, int gs, int hw,
-                           const float* gate, const float* addend, const PadOut* pad = nullptr, bool* pad_done = nullptr) {
-	int ch, grp;
-	if (pad_done) *pad_done = false;
-	if (fold_groups(batch, c, gs, &ch, &grp)) {
-		if (pad && pad->dst && pad_done) *pad_done = true;
-		return group_norm_ddx_gated(stream, src, dst, data, mu, sd, ch, grp, hw, gate, addend, pad);
-	}
-	const int groups = (c + gs - 1) / gs;
-	for (int b = 0; b < batch; b++) {
-		const size_t o = (size_t)b * c * hw;
-		bla_status st = group_norm_ddx_gated(stream, src + o, dst + o, data + o, mu + (size_t)b * groups, sd + (size_t)b * groups, c, gs, hw, gate ? gate + o : nullptr,
-		                                     addend ? addend + o : nullptr);
-		if (st) return st;
-	}
-	return BLA_OK;
-}
-
-bla_status bla_group_norm_relu_batched_f32(void* stream, int batch, const float* d_in, float* d_out, float* d_stdevs, float* d_means, int channels, int group_size, int hw) {
-	return gn_relu_b(stream, batch, d_in, d_out, d_stdevs, d_means, channels, group_size, hw, nullptr, nullptr);
-}
-bla_status bla_group_norm_ddx_gated_batched_f32(void* stream, int batch, const float* d_source, float* d_dest, const float* d_data, const float* d_means,
-                                                const float* d_stdevs, int channels, int group_size, int hw, const float* d_relu_gate, const float* d_addend) {
-	return gn_ddx_b(stream, batch, d_source, d_dest, d_data, d_means, d_stdevs, channels, group_size, hw, d_relu_gate, d_addend);
-}
-
 bla_status bla_resnet_forward_batched_f32(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p, const unsigned char* d_drop,
                                           const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k, int tdim, int group_size) {
 	return resnet_forward_batched(stream, batch, d_x, d_temb, p, d_drop, ws, d_result, h, w, cin, cout, k, tdim, group_size, 0, nullptr);
@@ -343,7 +291,7 @@ bla_status bla::resnet_forward_batched(void* stream, int batch, const float* d_x
 	const PadLayout L = pads ? conv_padded_layout(h, w, k, 1) : PadLayout{};
 	const PadOut po1 = {pads && L.plane ? pads->pad1 : nullptr, L}, po2 = {pads && L.plane ? pads->pad2 : nullptr, L};
 	bool have1 = false, have2 = false;
-	st = gn_relu_b(stream, batch, d_x, ws->relu1, ws->sd1, ws->mu1, cin, group_size, hw, nullptr, nullptr, &po1, &have1); if (st) return st;            // :1046-1047
+	st = group_norm_relu_dropout_batched(stream, batch, d_x, ws->relu1, ws->sd1, ws->mu1, cin, group_size, hw, nullptr, nullptr, &po1, &have1); if (st) return st;            // :1046-1047
 	if (pads) { pads->have1 = have1; }
 	if (!(flags & RESNET_TDENSE_READY)) {
 		bla_gemm_epilogue ep = {};
@@ -353,7 +301,7 @@ bla_status bla::resnet_forward_batched(void* stream, int batch, const float* d_x
 	st = conv2d_forward_epilogue(stream, ws->relu1, p->conv1, ws->c1, h, w, k, cin, cout, 1, ws->tdense, nullptr, nullptr, batch, cout, have1 ? pads->pad1 : nullptr,
 	                             pads ? pads->k1_fwd : nullptr);
 	if (st) return st;                                                                                                                      // :1048,1053
-	st = gn_relu_b(stream, batch, ws->c1, ws->relu2, ws->sd2, ws->mu2, cout, group_size, hw, d_drop, ws->dp, &po2, &have2); if (st) return st;          // :1056-1058
+	st = group_norm_relu_dropout_batched(stream, batch, ws->c1, ws->relu2, ws->sd2, ws->mu2, cout, group_size, hw, d_drop, ws->dp, &po2, &have2); if (st) return st;          // :1056-1058
 	if (pads) { pads->have2 = have2; }
 	const float* r = d_x;
 	if (cin != cout) {
@@ -397,7 +345,7 @@ bla_status bla::resnet_backward_batched(void* stream, int batch, const float* d_
 	const PadLayout L = pads && pads->dy_pad && d_del_x && k % 2 == 1 && conv_kernel_prep_mode(batch, h, w, k, cin, cout, 1, true) == 3 ? conv_padded_layout(h, w, k, 1) : PadLayout{};
 	const PadOut pod = {L.plane ? pads->dy_pad : nullptr, L};
 	bool have_dy = false;
-	st = gn_ddx_b(stream, batch, sc->g_out_a, g_out_b, ws->c1, ws->mu2, ws->sd2, cout, group_size, hw, ws->dp, nullptr, &pod, &have_dy); if (st) return st;
+	st = group_norm_ddx_gated_batched(stream, batch, sc->g_out_a, g_out_b, ws->c1, ws->mu2, ws->sd2, cout, group_size, hw, ws->dp, nullptr, &pod, &have_dy); if (st) return st;
 	// time-embedding projection, :1191-1199: per image the per-channel sums, then bias gradient = their sum over the images, weight gradient = temb^T . dtb
 	st = bla_col_sum_f32(stream, g_out_b, batch * cout, hw, d_dtb, BLA_COLSUM_INTENDED); if (st) return st;
 	if (!(flags & RESNET_DEFER_TIME_GRADS)) {
@@ -421,7 +369,7 @@ bla_status bla::resnet_backward_batched(void* stream, int batch, const float* d_
 		st = bla_conv2d_backward_batched_f32(stream, d_del_out, d_x, p->res, side ? nullptr : g->res, pads->g_res, sc->flip, batch, h, w, 1, cin, cout, 1); if (st) return st;
 	}
 	if (d_del_x) {
-		st = gn_ddx_b(stream, batch, sc->g_in, d_del_x, d_x, ws->mu1, ws->sd1, cin, group_size, hw, ws->relu1, cin == cout ? d_del_out : (res_first ? pads->g_res : nullptr));
+		st = group_norm_ddx_gated_batched(stream, batch, sc->g_in, d_del_x, d_x, ws->mu1, ws->sd1, cin, group_size, hw, ws->relu1, cin == cout ? d_del_out : (res_first ? pads->g_res : nullptr));
 		if (st) return st;
 	}
 	if (cin != cout && !res_first && !(side && !d_del_x)) {

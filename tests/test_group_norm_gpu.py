@@ -1,8 +1,8 @@
-"""Every group-norm kernel path of csrc/bla_conv.hip, held element by element to a derived rounding bound against a float64 reference.
+"""Every group-norm kernel path of csrc/bla_group_norm.hip, held element by element to a derived rounding bound against a float64 reference.
 
 The family is eight kernels behind launch_group_norm<RELU> and launch_group_norm_ddx: one workgroup per group or slices of 2,048 elements, 16-byte or
 scalar loads -- chosen by the size of a full group and by alignment (`path_of` below restates the rule, and a host test asserts that the case table
-reaches all four paths).  The batched entries add fold_groups (csrc/bla_unet.hip).  Every output is a view inside a larger allocation pre-filled with
+reaches all four paths).  The batched entries add fold_groups (same file).  Every output is a view inside a larger allocation pre-filled with
 0xFF bytes whose guard floats must come back untouched; an element a kernel does not write stays NaN and fails every bound.
 
 Bounds, u = 2^-24 (m, v: the mean and variance the device returned; v is what `stdevs` holds and what the output is divided by -- the reference's quirk):
@@ -32,7 +32,7 @@ SLICE = 2048          # kGnSlice
 
 
 def path_of(channels, group_size, hw, aligned=True):
-    """The dispatch rule of launch_group_norm<RELU> and launch_group_norm_ddx (csrc/bla_conv.hip), which choose alike: one workgroup per group up to
+    """The dispatch rule both launchers take from gn_route (csrc/bla_group_norm.hip), each with its own alignment predicate: one workgroup per group up to
     16,384 elements in a full group, slices beyond; 16-byte kernels when hw is a multiple of 4 and every tensor pointer is 16-byte aligned."""
     n_max = min(channels, group_size) * hw
     vec = hw % 4 == 0 and aligned
@@ -432,7 +432,7 @@ def per_image(I, b, c, hw, ng):
 @pytest.mark.gpu
 @pytest.mark.parametrize("i", range(len(BATCHED)), ids=lambda i: case_id(BATCHED[i]))
 def test_batched_entries(dev, i):
-    """bla_group_norm_relu_batched_f32 and bla_group_norm_ddx_gated_batched_f32 against the per-image reference: fold_groups (csrc/bla_unet.hip) folds
+    """bla_group_norm_relu_batched_f32 and bla_group_norm_ddx_gated_batched_f32 against the per-image reference: fold_groups (csrc/bla_group_norm.hip) folds
     the batch into the channel count, shortens the group to the image, or goes image by image -- the groups of one image never reach into the next."""
     batch, c, gs, hw = BATCHED[i]; I = batched_inputs(i)
     ng = (c + gs - 1) // gs; n = c * hw
