@@ -18,7 +18,9 @@ from .native import (BlaError, DeviceArray, lib, init, is_available, gemm, Epilo
                      gemm_mxfp8, gemm_f32_as_mxfp8, UNET_ATTENTION_BF16_ONLINE, attention_online_bf16_applies,
                      attention_forward_batched_online_bf16, attention_backward_batched_online_bf16, attention_online_bf16_heads_applies,
                      attention_forward_batched_online_bf16_heads, attention_backward_batched_online_bf16_heads, attention_f32_heads_applies,
-                     attention_forward_batched_f32_heads, attention_backward_batched_f32_heads, unet_create_heads, unet_heads)
+                     attention_forward_batched_f32_heads, attention_backward_batched_f32_heads, unet_create_heads, unet_heads, UNET_ATTENTION_F32_ONLINE,
+                     attention_online_f32_applies, attention_forward_batched_online_f32, attention_backward_batched_online_f32, unet_create_attention,
+                     unet_device_bytes)
 
 from . import native, mnist_nn  # noqa: F401,E402
 
@@ -35,4 +37,5 @@ __all__ = ["BlaError", "DeviceArray", "lib", "init", "is_available", "gemm", "Ep
            "gemm_f32_as_mxfp8", "UNET_ATTENTION_BF16_ONLINE", "attention_online_bf16_applies", "attention_forward_batched_online_bf16",
            "attention_backward_batched_online_bf16", "attention_online_bf16_heads_applies", "attention_forward_batched_online_bf16_heads",
            "attention_backward_batched_online_bf16_heads", "attention_f32_heads_applies", "attention_forward_batched_f32_heads",
-           "attention_backward_batched_f32_heads", "unet_create_heads", "unet_heads"]
+           "attention_backward_batched_f32_heads", "unet_create_heads", "unet_heads", "UNET_ATTENTION_F32_ONLINE", "attention_online_f32_applies",
+           "attention_forward_batched_online_f32", "attention_backward_batched_online_f32", "unet_create_attention", "unet_device_bytes"]

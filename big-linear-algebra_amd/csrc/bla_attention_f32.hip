@@ -169,7 +169,9 @@ bla_status bgemm(void* s, int ta, int tb, int m, int n, int k, const float* A, i
 	return bla_gemm_batched_f32(s, ta, tb, m, n, k, A, lda, sa, B, ldb, sb, C, ldc, sc, batch, &ep, spre);
 }
 
-// ---- the stages both batched forms share, at a row width D (one head: d; several: heads d, the heads side by side) -----------------------------------------
+}  // namespace
+
+// ---- the stages the batched forms share (declared in bla_internal.h: bla_attention_online_f32.hip runs them too), at a row width D (one head: d; several: heads d, the heads side by side) -----------------------------------------
 // x / out / del_y / del_x [B][C][S]; q, k, v, attention, their gradients [B][S][D]; wq / wk / wv [C][D]; w [D][C]; partials: [B][C*D] scratch, summed in image order
 bla_status project_qkv(void* stream, int batch, const float* x, const float* wq, const float* wk, const float* wv, const bla_attention_ws* ws, int c, int s, int D) {
 	const long xs = (long)c * s, qs = (long)s * D;
@@ -211,7 +213,6 @@ bla_status grad_qkv_weights_and_del_x(void* stream, int batch, const float* x, c
 	return bgemm(stream, 0, 1, c, s, D, wv, D, 0, del_v, D, qs, del_x, s, xs, batch, 1.f, 1.f);
 }
 
-}  // namespace
 }  // namespace bla
 
 using namespace bla;

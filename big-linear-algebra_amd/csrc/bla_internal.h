@@ -196,6 +196,15 @@ bla_status batch_sum(void* stream, const float* src, float* dst, int batch, size
 // bla_unet.hip: out[r] = (s[r] o (g[r] - <s[r], g[r]>)) * scale per row: the launch behind bla_softmax_ddx_f32 (scale 1) and the batched fp32 attention block
 bla_status softmax_ddx_launch(void* stream, const float* s, const float* g, float* out, int rows, int dim, float scale);
 
+// bla_attention_f32.hip: the stages of the batched fp32 attention block that do not depend on the softmax, at a row width D = heads d.
+// x / out / del_y / del_x [B][C][S]; q, k, v, attention, their gradients [B][S][D]; wq / wk / wv [C][D]; w [D][C]; partials [B][C*D], summed in image order
+bla_status project_qkv(void* stream, int batch, const float* x, const float* wq, const float* wk, const float* wv, const bla_attention_ws* ws, int c, int s, int D);
+bla_status project_out(void* stream, int batch, const float* w, const float* bias, const float* attention, float* out, int c, int s, int D);
+bla_status grad_out_weight_and_del_p(void* stream, int batch, const float* del_y, const float* w, const float* attention, float* partials, float* del_w, float* del_p,
+                                     int c, int s, int D);
+bla_status grad_qkv_weights_and_del_x(void* stream, int batch, const float* x, const float* wq, const float* wk, const float* wv, const float* del_q, const float* del_k,
+                                      const float* del_v, float* partials, float* del_wq, float* del_wk, float* del_wv, float* del_x, int c, int s, int D);
+
 // bla_unet_model.hip: the configuration a U-Net was created with (bla_diffusion.hip's sampler sizes its embeddings from it)
 const bla_unet_config* unet_config(const bla_unet* m);
 // bla_guidance.hip: true when the runtime does not know p as device memory (class labels handed in from the host are checked there); the Bernoulli

@@ -51,12 +51,13 @@ struct Res {
 };
 // one ResNet block's time-embedding projection (model/cifar_unet.c:1051-1052) and its gradients (:1191-1199); all 18 run as one launch each way
 struct TimeJob { const float* w; const float* bias; float* tdense; const float* dtb; float* g_tw; float* g_tb; int cout; };
-enum AttRoute { ROUTE_NONE, ROUTE_F32, ROUTE_BF16, ROUTE_ONLINE, ROUTE_F32_HEADS, ROUTE_ONLINE_HEADS };   // the entries an attention block runs on (att_route)
+enum AttRoute { ROUTE_NONE, ROUTE_F32, ROUTE_BF16, ROUTE_ONLINE, ROUTE_F32_HEADS, ROUTE_ONLINE_HEADS, ROUTE_F32_ONLINE };   // the entries an attention block runs on (att_route)
 struct Att {
 	int c, h, w;
 	AttRoute route;   // decided by att_route at create and at every bla_unet_set_attention
 	size_t wq, wk, wv, wo, bias;
 	bla_attention_ws fwd;
+	size_t raw_floats, weights_floats;   // what fwd.scores_raw and fwd.weights hold (bla_unet_set_attention: a route needs its buffers)
 	float* out;
 };
 struct Conv {
@@ -143,6 +144,8 @@ struct bla_unet {
 	float *dtb = nullptr, *partials = nullptr;   // batched blocks: per-image time-bias sums [B][Cout], per-image attention weight gradients [B][C*d]
 	bla_resnet_scratch sc = {};
 	bla_attention_ws agrad = {};
+	size_t agrad_raw = 0, agrad_weights = 0;   // floats of agrad.scores_raw and agrad.weights
+	size_t bytes = 0;                          // the sum of what dalloc handed out (bla_unet_device_bytes)
 	const float* last_x = nullptr; const float* last_temb = nullptr;   // the last forward pass's (the backward pass reads them)
 	std::vector<void*> owned;
 };
@@ -153,6 +156,7 @@ template <typename T> bla_status dalloc(bla_unet* m, T** p, size_t n) {
 	void* q = nullptr;
 	BLA_HIP(hipMalloc(&q, (n ? n : 1) * sizeof(T)));
 	m->owned.push_back(q);
+	m->bytes += (n ? n : 1) * sizeof(T);
 	*p = (T*)q;
 	return BLA_OK;
 }
@@ -455,13 +459,30 @@ bla_status conv_backward_bf16(bla_unet* m, void* stream, const Conv& k, const fl
 //   one head:      the mode's bf16 entries where they apply to the shape, else fp32, which takes any shape (never ROUTE_NONE);
 //   several heads: where both the fp32 heads entries (S <= 64) and the online ones apply, the mode chooses; else the one that applies, under EVERY mode -- a long
 //                  block is bf16-online under both modes.  ROUTE_NONE: neither applies, so no mode can run the block (BLA_UNET_ATTENTION_BF16 has no heads).
+//   BLA_UNET_ATTENTION_F32_ONLINE: a block with S > 64 runs the online fp32 entries, whatever the heads; every other block as under _F32.
 AttRoute att_route(int mode, int heads, int c, int s, int d) {
+	if (mode == BLA_UNET_ATTENTION_F32_ONLINE) {
+		if (s > 64 && bla_attention_online_f32_applies(c, s, heads, d)) return ROUTE_F32_ONLINE;
+		mode = BLA_UNET_ATTENTION_F32;
+	}
 	const bool online_mode = mode == BLA_UNET_ATTENTION_BF16_ONLINE;
 	if (heads == 1)
 		return online_mode && bla_attention_online_bf16_applies(c, s, d) ? ROUTE_ONLINE : mode == BLA_UNET_ATTENTION_BF16 && bla_attention_bf16_applies(c, s, d) ? ROUTE_BF16 : ROUTE_F32;
 	const bool f32 = bla_attention_f32_heads_applies(c, s, heads, d), online = bla_attention_online_bf16_heads_applies(c, s, heads, d);
 	if (f32 && online) return online_mode ? ROUTE_ONLINE_HEADS : ROUTE_F32_HEADS;
 	return f32 ? ROUTE_F32_HEADS : online ? ROUTE_ONLINE_HEADS : ROUTE_NONE;
+}
+// floats of scores_raw and of weights that a route reads or writes, in the block's own workspace and in the shared gradient workspace (what create allocates
+// for it and what bla_unet_set_attention asks a model to own): the materialising routes S x S, the online ones a float a row, the fp32 heads route P alone
+struct AttNeeds { size_t raw, weights, grad_raw, grad_weights; };
+AttNeeds att_needs(AttRoute r, size_t B, size_t heads, size_t s) {
+	switch (r) {
+	case ROUTE_F32: case ROUTE_BF16: return {B * s * s, B * s * s, B * s * s, B * s * s};
+	case ROUTE_ONLINE: case ROUTE_ONLINE_HEADS: case ROUTE_F32_ONLINE: return {B * heads * s, 0, B * heads * s, 0};
+	case ROUTE_F32_HEADS: return {0, B * heads * s * s, 0, 0};
+	case ROUTE_NONE: break;
+	}
+	return {0, 0, 0, 0};
 }
 bla_status att_forward(bla_unet* m, void* stream, Att& a, const float* in) {
 	const float* P = m->params;
@@ -473,6 +494,8 @@ bla_status att_forward(bla_unet* m, void* stream, Att& a, const float* in) {
 	case ROUTE_F32_HEADS: case ROUTE_ONLINE_HEADS:
 		return (a.route == ROUTE_F32_HEADS ? bla_attention_forward_batched_f32_heads : bla_attention_forward_batched_online_bf16_heads)(
 			stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, s, m->heads, d);
+	case ROUTE_F32_ONLINE:
+		return bla_attention_forward_batched_online_f32(stream, m->batch, in, P + a.wq, P + a.wk, P + a.wv, P + a.wo, P + a.bias, &a.fwd, a.out, a.c, s, m->heads, d);
 	case ROUTE_NONE: break;   // (create refuses such a model)
 	}
 	set_error("attention block without a route");
@@ -491,6 +514,9 @@ bla_status att_backward(bla_unet* m, void* stream, Att& a, const float* g, const
 	case ROUTE_F32_HEADS: case ROUTE_ONLINE_HEADS:
 		return (a.route == ROUTE_F32_HEADS ? bla_attention_backward_batched_f32_heads : bla_attention_backward_batched_online_bf16_heads)(
 			stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk, G + a.wv, G + a.wo, out, a.c, s, m->heads, d);
+	case ROUTE_F32_ONLINE:
+		return bla_attention_backward_batched_online_f32(stream, m->batch, g, x, P + a.wq, P + a.wk, P + a.wv, P + a.wo, &a.fwd, &m->agrad, m->partials, G + a.wq, G + a.wk,
+		                                                 G + a.wv, G + a.wo, out, a.c, s, m->heads, d);
 	case ROUTE_NONE: break;
 	}
 	set_error("attention block without a route");
@@ -613,19 +639,60 @@ int bla_unet_attention(const bla_unet* m) { return m ? m->attention : BLA_UNET_A
 int bla_unet_heads(const bla_unet* m) { return m ? m->heads : 1; }
 
 bla_status bla_unet_set_attention(bla_unet* m, int mode) {
-	BLA_REQUIRE(mode == BLA_UNET_ATTENTION_F32 || mode == BLA_UNET_ATTENTION_BF16 || mode == BLA_UNET_ATTENTION_BF16_ONLINE, BLA_ERR_INVALID,
-	            "bla_unet_set_attention: mode %d (BLA_UNET_ATTENTION_F32, _BF16 or _BF16_ONLINE)", mode);
+	BLA_REQUIRE(mode == BLA_UNET_ATTENTION_F32 || mode == BLA_UNET_ATTENTION_BF16 || mode == BLA_UNET_ATTENTION_BF16_ONLINE || mode == BLA_UNET_ATTENTION_F32_ONLINE,
+	            BLA_ERR_INVALID, "bla_unet_set_attention: mode %d (BLA_UNET_ATTENTION_F32, _BF16, _BF16_ONLINE or _F32_ONLINE)", mode);
 	BLA_REQUIRE(m, BLA_ERR_INVALID, "null argument");
 	BLA_REQUIRE(m->heads == 1 || mode != BLA_UNET_ATTENTION_BF16, BLA_ERR_INVALID,
 	            "bla_unet_set_attention: BLA_UNET_ATTENTION_BF16 on a model with %d heads (the materialising bf16 block has none)", m->heads);
-	m->attention = mode;   // (no route is ROUTE_NONE: create has made sure that some path takes every block under every mode accepted here)
-	for (Att& a : m->att) a.route = att_route(mode, m->heads, a.c, a.h * a.w, m->cfg.key_dim);
+	// every block needs a route under the new mode, and the buffers of that route: a model of the older create entries owns them under every mode accepted
+	// above; one created in BLA_UNET_ATTENTION_F32_ONLINE (bla_unet_create_attention) may have neither
+	AttRoute routes[5];
+	for (int i = 0; i < 5; i++) {
+		const Att& a = m->att[i];
+		const size_t s = (size_t)a.h * a.w;
+		routes[i] = att_route(mode, m->heads, a.c, (int)s, m->cfg.key_dim);
+		const AttNeeds n = att_needs(routes[i], (size_t)m->batch, (size_t)m->heads, s);
+		BLA_REQUIRE(routes[i] != ROUTE_NONE, BLA_ERR_INVALID, "bla_unet_set_attention: mode %d has no path for the block C=%d S=%zu heads=%d d=%d", mode, a.c, s, m->heads,
+		            m->cfg.key_dim);
+		BLA_REQUIRE(n.raw <= a.raw_floats && n.weights <= a.weights_floats && n.grad_raw <= m->agrad_raw && n.grad_weights <= m->agrad_weights, BLA_ERR_INVALID,
+		            "bla_unet_set_attention: mode %d needs S x S buffers for the block C=%d S=%zu that this model was created without", mode, a.c, s);
+	}
+	m->attention = mode;
+	for (int i = 0; i < 5; i++) m->att[i].route = routes[i];
 	return BLA_OK;
 }
 
 bla_status bla_unet_create_mixed(bla_unet** out, const bla_unet_config* cfg, int batch, int products) { return bla_unet_create_heads(out, cfg, batch, products, 1); }
 
+namespace {
+bla_status create_model(bla_unet** out, const bla_unet_config* cfg, int batch, int products, int heads, int attention);
+}
 bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int batch, int products, int heads) {
+	return create_model(out, cfg, batch, products, heads, BLA_UNET_ATTENTION_F32);
+}
+
+bla_status bla_unet_create_attention(bla_unet** out, const bla_unet_config* cfg, int batch, int products, int heads, int attention) {
+	BLA_REQUIRE(attention == BLA_UNET_ATTENTION_F32 || attention == BLA_UNET_ATTENTION_BF16 || attention == BLA_UNET_ATTENTION_BF16_ONLINE ||
+	            attention == BLA_UNET_ATTENTION_F32_ONLINE, BLA_ERR_INVALID, "bla_unet_create_attention: mode %d (BLA_UNET_ATTENTION_F32, _BF16, _BF16_ONLINE or _F32_ONLINE)",
+	            attention);
+	if (attention == BLA_UNET_ATTENTION_F32_ONLINE) return create_model(out, cfg, batch, products, heads, attention);
+	bla_unet* m = nullptr;   // the other modes: bla_unet_create_heads, then the switch -- the same refusals, bits and bytes
+	bla_status st = create_model(&m, cfg, batch, products, heads, BLA_UNET_ATTENTION_F32);
+	if (st) return st;
+	if ((st = bla_unet_set_attention(m, attention))) { (void)bla_unet_destroy(m); return st; }
+	*out = m;
+	return BLA_OK;
+}
+
+size_t bla_unet_device_bytes(const bla_unet* m) { return m ? m->bytes : 0; }
+
+}  // extern "C"
+
+namespace {
+// attention == BLA_UNET_ATTENTION_F32: a model that every mode can run (bla_unet_create_heads: a block no multi-head path takes is refused, one head keeps its
+// S x S buffers).  BLA_UNET_ATTENTION_F32_ONLINE: the model in that mode, every block's buffers those of its route.
+bla_status create_model(bla_unet** out, const bla_unet_config* cfg, int batch, int products, int heads, int attention) {
+	const bool in_mode = attention == BLA_UNET_ATTENTION_F32_ONLINE;
 	BLA_REQUIRE(products == BLA_UNET_PRODUCTS_F32 || products == BLA_UNET_PRODUCTS_BF16, BLA_ERR_INVALID, "bla_unet_create_mixed: products %d (BLA_UNET_PRODUCTS_F32 or _BF16)", products);
 	const bool bf16 = products == BLA_UNET_PRODUCTS_BF16;
 	bla_status st = require_ready();
@@ -641,6 +708,7 @@ bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int
 	m->cfg = *cfg;
 	m->batch = batch;
 	m->heads = heads;
+	m->attention = attention;
 	m->products = products;
 	m->stack = bf16 ? &kStackBf16 : &kStackF32;
 	const size_t B = (size_t)batch;
@@ -696,8 +764,11 @@ bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int
 			Att& a = m->att[s.index];
 			const size_t sp = (size_t)a.h * a.w;
 			// (under the default mode ROUTE_F32_HEADS is exactly "the fp32 heads entries apply": those blocks own P, whatever the mode turns to)
-			if ((st = alloc_att_ws(m, a.fwd, sp, B * heads * sp * (one_head ? sp : 1), one_head || a.route == ROUTE_F32_HEADS ? B * heads * sp * sp : 0)) ||
-			    (st = dalloc(m, &a.out, B * a.c * sp)))
+			const AttNeeds need = att_needs(a.route, B, heads, sp);
+			a.raw_floats = in_mode ? need.raw : B * heads * sp * (one_head ? sp : 1);
+			a.weights_floats = in_mode ? need.weights : one_head || a.route == ROUTE_F32_HEADS ? B * heads * sp * sp : 0;
+			m->agrad_raw = std::max(m->agrad_raw, need.grad_raw); m->agrad_weights = std::max(m->agrad_weights, need.grad_weights);   // (in_mode: the largest block that still materialises)
+			if ((st = alloc_att_ws(m, a.fwd, sp, a.raw_floats, a.weights_floats)) || (st = dalloc(m, &a.out, B * a.c * sp)))
 				return fail(st);
 			max_s = std::max(max_s, sp); max_cd = std::max(max_cd, (size_t)a.c * cfg->key_dim * heads);
 			s.out = a.out;
@@ -737,9 +808,10 @@ bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int
 		for (size_t i = 0; i < kGradPool; i++) { float* q; if ((st = dalloc(m, &q, max_act))) return fail(st); m->gpool.push_back(q); }
 		for (Res& r : m->res) if ((st = dalloc(m, &r.pads.g_out_b, (size_t)r.cout * r.h * r.w * B))) return fail(st);
 	}
+	if (!in_mode) { m->agrad_raw = B * heads * max_s * (one_head ? max_s : 1); m->agrad_weights = one_head ? B * max_s * max_s : 0; }
 	if ((st = dalloc(m, &m->ring[0], max_act)) || (st = dalloc(m, &m->ring[1], max_act)) || (st = dalloc(m, &m->ring[2], max_act)) || (st = dalloc(m, &m->sc.g_out_a, max_cout_hw)) ||
 	    (st = dalloc(m, &m->sc.g_out_b, max_cout_hw)) || (st = dalloc(m, &m->sc.g_in, max_cin_hw)) || (st = dalloc(m, &m->sc.flip, max_flip)) ||
-	    (st = alloc_att_ws(m, m->agrad, max_s, B * heads * max_s * (one_head ? max_s : 1), one_head ? B * max_s * max_s : 0)) || (st = dalloc(m, &m->dtb, B * m->max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
+	    (st = alloc_att_ws(m, m->agrad, max_s, m->agrad_raw, m->agrad_weights)) || (st = dalloc(m, &m->dtb, B * m->max_cout)) || (st = dalloc(m, &m->partials, B * 4 * max_cd)))   // (4 C d an image: the bf16 attention entries keep all four weight-gradient partials)
 		return fail(st);
 	if ((st = dalloc_zeroed(m, &m->zero_drop, B * m->drop_count))) return fail(st);
 	{   // the 18 time-embedding projections (and, for a batch, their gradients) as one launch each way (eight embedding rows in LDS), and the embedding gradient's
@@ -763,6 +835,9 @@ bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int
 	*out = m;
 	return BLA_OK;
 }
+}  // namespace
+
+extern "C" {
 
 bla_status bla_unet_destroy(bla_unet* m) {
 	if (!m) return BLA_OK;

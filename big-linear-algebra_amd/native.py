@@ -165,7 +165,11 @@ SIGNATURES = {
     "bla_attention_f32_heads_applies": (_I, [_I] * 4),
     "bla_attention_forward_batched_f32_heads": (_I, [_VP, _I] + [_VP] * 8 + [_I] * 4),
     "bla_attention_backward_batched_f32_heads": (_I, [_VP, _I] + [_VP] * 14 + [_I] * 4),
+    "bla_attention_online_f32_applies": (_I, [_I] * 4),
+    "bla_attention_forward_batched_online_f32": (_I, [_VP, _I] + [_VP] * 8 + [_I] * 4),
+    "bla_attention_backward_batched_online_f32": (_I, [_VP, _I] + [_VP] * 14 + [_I] * 4),
     "bla_unet_create_heads": (_I, [C.POINTER(_VP), _VP, _I, _I, _I]), "bla_unet_heads": (_I, [_VP]),
+    "bla_unet_create_attention": (_I, [C.POINTER(_VP), _VP, _I, _I, _I, _I]), "bla_unet_device_bytes": (C.c_size_t, [_VP]),
     "bla_unet_set_attention": (_I, [_VP, _I]), "bla_unet_attention": (_I, [_VP]),
     "bla_resnet_forward_batched_f32": (_I, [_VP, _I] + [_VP] * 6 + [_I] * 7), "bla_resnet_backward_batched_f32": (_I, [_VP, _I] + [_VP] * 9 + [_I] * 7),
     "bla_group_norm_relu_bf16_map": (_I, [_VP, _I, _VP] + [_I] * 4 + [_VP] * 4 + [C.POINTER(ConvBf16Map)]),
@@ -710,6 +714,39 @@ def unet_create_heads(cfg, batch=1, products=UNET_PRODUCTS_F32, heads=1):
 
 def unet_heads(model):
     return lib().bla_unet_heads(model)
+
+
+UNET_ATTENTION_F32_ONLINE = 4   # the online softmax in fp32 for every block with S > 64; the other blocks as under UNET_ATTENTION_F32
+
+
+def attention_online_f32_applies(c, s, heads, d):
+    """bla_attention_online_f32_applies: host only, no device needed; d is the width of one head."""
+    return bool(lib().bla_attention_online_f32_applies(c, s, heads, d))
+
+
+def attention_forward_batched_online_f32(batch, x, wq, wk, wv, w, bias, ws, out, c, s, heads, d, stream=None):
+    """bla_attention_forward_batched_online_f32: ws needs q, k, v, attention ([batch][s][heads d]) and scores_raw ([batch][heads][s], the lse)."""
+    check(lib().bla_attention_forward_batched_online_f32(stream, batch, _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(w), _ptr(bias), C.byref(ws), _ptr(out), c, s, heads, d))
+    return out
+
+
+def attention_backward_batched_online_f32(batch, del_y, x, wq, wk, wv, w, fwd, grad, partials, del_wq, del_wk, del_wv, del_w, del_x, c, s, heads, d, stream=None):
+    """bla_attention_backward_batched_online_f32: grad needs q, k, v, attention (del_P) and scores_raw ([batch][heads][s], the row dots); partials [batch][c heads d]."""
+    check(lib().bla_attention_backward_batched_online_f32(stream, batch, _ptr(del_y), _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(w), C.byref(fwd), C.byref(grad),
+                                                          _ptr(partials), _ptr(del_wq), _ptr(del_wk), _ptr(del_wv), _ptr(del_w), _ptr(del_x), c, s, heads, d))
+
+
+def unet_create_attention(cfg, batch=1, products=UNET_PRODUCTS_F32, heads=1, attention=UNET_ATTENTION_F32):
+    """bla_unet_create_attention: the U-Net created in its attention mode; under UNET_ATTENTION_F32_ONLINE every shape has a route and a block on the
+    online fp32 entries owns no S x S buffer."""
+    h = C.c_void_p()
+    check(lib().bla_unet_create_attention(C.byref(h), C.byref(cfg), batch, products, heads, attention))
+    return h
+
+
+def unet_device_bytes(model):
+    """bla_unet_device_bytes: the sum of what the model allocated on the device."""
+    return lib().bla_unet_device_bytes(model)
 
 
 def conv2d_gathered_bf16(a, rows, p, batch, hp, wp, cp, k, stride, ho, wo, out, ep_bias=None, ep_bias_stride=0, stream=None):

@@ -190,7 +190,8 @@ static void heads_from_env(int attention) {
 	const int level[2] = {2, 4};   /* the resolutions with attention blocks */
 	for (int i = 0; i < 2; i++) {
 		const int c = kDims[level[i] - 1], s = side_of(level[i]) * side_of(level[i]);
-		if (!bla_attention_f32_heads_applies(c, s, g_heads, KEY_DIM) && !bla_attention_online_bf16_heads_applies(c, s, g_heads, KEY_DIM)) {
+		if (!bla_attention_f32_heads_applies(c, s, g_heads, KEY_DIM) && !bla_attention_online_bf16_heads_applies(c, s, g_heads, KEY_DIM) &&
+		    !(attention == BLA_UNET_ATTENTION_F32_ONLINE && s > 64 && bla_attention_online_f32_applies(c, s, g_heads, KEY_DIM))) {
 			fprintf(stderr, "BLA_UNET_HEADS=%s: the model refuses %d heads of width %d (C = %d, S = %d; heads x %d <= 256)\n", v, g_heads, KEY_DIM, c, s, KEY_DIM);
 			exit(1);
 		}
@@ -436,22 +437,27 @@ static void products_from_env(void) {
 	else if (strcmp(v, "bf16") == 0) g_products = BLA_UNET_PRODUCTS_BF16;
 	else { fprintf(stderr, "BLA_UNET_PRODUCTS=%s: expected f32 or bf16\n", v); exit(1); }
 }
-/* BLA_UNET_ATTENTION=f32|bf16|online (default f32): where the model's attention blocks multiply (bla_unet_set_attention; online = bf16
- * products with the online softmax, any block up to S = 4096); orthogonal to the above. */
+/* BLA_UNET_ATTENTION=f32|bf16|online|online-f32 (default f32): where the model's attention blocks multiply (bla_unet_set_attention; online =
+ * bf16 products with the online softmax, any block up to S = 4096; online-f32 = the online softmax in fp32 for every block with S > 64, the model created in
+ * that mode by bla_unet_create_attention); orthogonal to the above. */
 static int g_attention = BLA_UNET_ATTENTION_F32;
 static void attention_from_env(void) {
 	const char* v = env_or("BLA_UNET_ATTENTION", "f32");
 	if (strcmp(v, "f32") == 0) g_attention = BLA_UNET_ATTENTION_F32;
 	else if (strcmp(v, "bf16") == 0) g_attention = BLA_UNET_ATTENTION_BF16;
 	else if (strcmp(v, "online") == 0) g_attention = BLA_UNET_ATTENTION_BF16_ONLINE;
-	else { fprintf(stderr, "BLA_UNET_ATTENTION=%s: expected f32, bf16 or online\n", v); exit(1); }
+	else if (strcmp(v, "online-f32") == 0) g_attention = BLA_UNET_ATTENTION_F32_ONLINE;
+	else { fprintf(stderr, "BLA_UNET_ATTENTION=%s: expected f32, bf16, online or online-f32\n", v); exit(1); }
 }
 static Device device_open(int batch, size_t drop_per_image) {
 	Device dv; memset(&dv, 0, sizeof dv); dv.batch = batch;
 	CHECK(bla_init(atoi(env_or("BLA_DEVICE", "0"))));
 	bla_unet_config cfg = {IMAGE_SIDE, IMAGE_SIDE, IMAGE_CHANNELS, {kDims[0], kDims[1], kDims[2], kDims[3]}, TIME_EMBED_DIM, KERNEL_SIZE, GROUP_SIZE, KEY_DIM};
-	CHECK(bla_unet_create_heads(&dv.net, &cfg, batch, g_products, g_heads));
-	CHECK(bla_unet_set_attention(dv.net, g_attention));
+	if (g_attention == BLA_UNET_ATTENTION_F32_ONLINE) CHECK(bla_unet_create_attention(&dv.net, &cfg, batch, g_products, g_heads, g_attention));
+	else {
+		CHECK(bla_unet_create_heads(&dv.net, &cfg, batch, g_products, g_heads));
+		CHECK(bla_unet_set_attention(dv.net, g_attention));
+	}
 	if (bla_unet_dropout_count(dv.net) != drop_per_image * batch) { fprintf(stderr, "dropout layout: device %zu, host %zu\n", bla_unet_dropout_count(dv.net), drop_per_image * batch); exit(1); }
 	CHECK(bla_malloc((void**)&dv.x, (size_t)batch * IMAGE_FLOATS * sizeof(float)));
 	CHECK(bla_malloc((void**)&dv.noise, (size_t)batch * IMAGE_FLOATS * sizeof(float)));

@@ -765,6 +765,36 @@ BLA_API bla_status bla_attention_backward_batched_f32_heads(void* stream, int ba
                                                             const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
                                                             float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w, float* d_del_x,
                                                             int c, int s, int heads, int d);
+/* Online-softmax attention in fp32: the recurrence of the online bf16 entries with NOTHING ROUNDED TO bf16, for any S up to 4096, any head width
+ * up to 64 and any C -- the fp32 path for the long blocks of a multi-head model, for sequence lengths no other multi-head path takes (S % 32 != 0 past 64), and
+ * an fp32 block without S x S tensors.  Layouts are the online heads entries': Wq, Wk, Wv [C][D], D = heads d, head h in columns h d .. h d + d - 1;  W [D][C];
+ * bias [C];  ws->q, k, v, attention and grad->q, k, v, attention (= del_P) [B][S][D];  ws->scores_raw [B][heads][S], the row log-sum-exp of each head;
+ * grad->scores_raw [B][heads][S], the row dots of each head;  `weights` is neither read nor written and may be NULL in both;  d_partials [batch][C D].  Float
+ * alignment only; S, d and C need not be multiples of anything.  heads = 1 is the single-head block.
+ * Per image, Z = X^T, inv = (float)(1 / sqrt((double)d)) -- THE HEAD'S WIDTH, NOT D -- key blocks j of BLA_ATTENTION_ONLINE_KEYS keys in ascending order:
+ *   forward:  Q = Z Wq, K = Z Wk, V = Z Wv at width D (the fp32 batched block's products).  Per head and query row:  m = -inf, l = 0, Acc = 0;  per key block j:
+ *               T_j = (Q K_j^T) inv, the scaling a rounding of its own (__fmul_rn: the backward pass sees the same bits);  m' = max(m, rowmax T_j);
+ *               a = exp(m - m');  p = exp(T_j - m');  l = l a + rowsum(p);  Acc = Acc a + p V_j;  m = m'
+ *             A = Acc / l;  lse = m + log(l);  out = (A W + bias)^T, the contraction over all D columns.
+ *   backward: del_W = sum_b A^T del_Y';  del_P = del_Y' W^T;  dot_i = sum over the head's d columns of del_P[i][dd] A[i][dd] (dd ascending);  per key block j:
+ *               P_j = exp(T_j - lse);  del_S_j = del_P V_j^T;  del_I_j = (P_j o (del_S_j - dot)) inv;  del_V_j = P_j^T del_P;  del_K_j = del_I_j^T Q;
+ *               del_Q += del_I_j K_j
+ *             then del_Wq/k/v = sum_b Z^T del_Q/K/V and del_X = Wq del_Q^T + Wk del_K^T + Wv del_V^T at width D.
+ * The last key block may be ragged: a key at or beyond S counts as T = -inf, p = 0, and its K and V rows are read as zeros; every block holds at least one real
+ * key, so no row is ever all -inf.  A query row at or beyond S is neither stored nor fed into a sum.  Every product of the per-head core runs on the fp32 MFMA
+ * (v_mfma_f32_32x32x2_f32); every sum has a fixed order: no atomics, the same bits on every run, and in the core image b of a batch equals a batch-1 run of it
+ * (the width-D products keep bla_gemm_batched_f32's plan, as in the fp32 heads entries).  Forward: 5 launches; backward: 4 beside the shared stages'.
+ * bla_attention_online_f32_applies (host only) is 1 exactly when 1 <= s <= 4096, 1 <= d <= 64, heads >= 1, heads d <= 256 and c > 0; outside that set, or with
+ * batch outside 1 .. 65535 or a NULL operand or workspace field that is read or written, both entries return BLA_ERR_INVALID before any launch, outputs
+ * untouched. */
+BLA_API int bla_attention_online_f32_applies(int c, int s, int heads, int d);
+BLA_API bla_status bla_attention_forward_batched_online_f32(void* stream, int batch, const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv,
+                                                            const float* d_w, const float* d_bias, const bla_attention_ws* ws, float* d_out, int c, int s, int heads,
+                                                            int d);
+BLA_API bla_status bla_attention_backward_batched_online_f32(void* stream, int batch, const float* d_del_y, const float* d_x, const float* d_wq, const float* d_wk,
+                                                             const float* d_wv, const float* d_w, const bla_attention_ws* fwd, const bla_attention_ws* grad,
+                                                             float* d_partials, float* d_del_wq, float* d_del_wk, float* d_del_wv, float* d_del_w, float* d_del_x,
+                                                             int c, int s, int heads, int d);
 BLA_API bla_status bla_resnet_forward_batched_f32(void* stream, int batch, const float* d_x, const float* d_temb, const bla_resnet_params* p,
                                                   const unsigned char* d_drop, const bla_resnet_ws* ws, float* d_result, int h, int w, int cin, int cout, int k,
                                                   int tdim, int group_size);
@@ -863,8 +893,13 @@ BLA_API int bla_unet_products(const bla_unet* m);               /* the mode the 
  * bla_attention_{forward,backward}_batched_online_bf16, bit for bit those entries; every other block keeps the fp32 entries.  The row log-sum-exp lives in
  * the first B S floats of the block's scores_raw, the row dots in the gradient workspace's; nothing more is allocated.
  * The mode is a bit set: bit 0 = bf16 products, bit 1 = the online softmax.  2 (an online softmax on fp32 products) does not exist; it and any other
- * value: BLA_ERR_INVALID, the model unchanged. */
-enum { BLA_UNET_ATTENTION_F32 = 0, BLA_UNET_ATTENTION_BF16 = 1, BLA_UNET_ATTENTION_BF16_ONLINE = 3 };
+ * value: BLA_ERR_INVALID, the model unchanged.
+ * BLA_UNET_ATTENTION_F32_ONLINE = 4 (outside the bit set): a block with S > 64 runs bla_attention_{forward,backward}_batched_online_f32, bit for bit
+ * those entries, for any number of heads; every other block keeps the route it has under BLA_UNET_ATTENTION_F32.  The row log-sum-exp and the row dots live
+ * where mode 3 and the online heads route keep them (the first B heads S floats of scores_raw).  A model switched to mode 4 and back behaves as before.
+ * On a model that bla_unet_create_attention created in mode 4 the setter returns BLA_ERR_INVALID, mode and routes unchanged, where the new mode would leave a
+ * block without a route or give a block a route whose buffers the model does not own. */
+enum { BLA_UNET_ATTENTION_F32 = 0, BLA_UNET_ATTENTION_BF16 = 1, BLA_UNET_ATTENTION_BF16_ONLINE = 3, BLA_UNET_ATTENTION_F32_ONLINE = 4 };
 BLA_API bla_status bla_unet_set_attention(bla_unet* m, int mode);
 BLA_API int bla_unet_attention(const bla_unet* m);
 /* The same network with multi-head self-attention: every attention block has `heads` heads of width cfg->key_dim -- bla_unet_config is unchanged,
@@ -875,13 +910,20 @@ BLA_API int bla_unet_attention(const bla_unet* m);
  *     otherwise bla_attention_{forward,backward}_batched_online_bf16_heads;
  *   BLA_UNET_ATTENTION_BF16_ONLINE: the online heads entries where bla_attention_online_bf16_heads_applies accepts the block, otherwise the fp32 heads entries;
  *   BLA_UNET_ATTENTION_BF16: bla_unet_set_attention returns BLA_ERR_INVALID, the model unchanged (the materialising bf16 block has no heads).
- * SO A heads > 1 MODEL'S LONG BLOCKS (S > 64) MULTIPLY IN bf16 ON THE ONLINE SOFTMAX IN BOTH MODES, BLA_UNET_ATTENTION_F32 INCLUDED: there is no fp32 multi-head
- * path for S > 64.  At the reference's constants that is the four 16 x 16 blocks (S = 256); the 4 x 4 mid block (S = 16) is fp32 in mode 0.
+ * SO A heads > 1 MODEL'S LONG BLOCKS (S > 64) MULTIPLY IN bf16 ON THE ONLINE SOFTMAX IN BOTH OF THESE MODES, BLA_UNET_ATTENTION_F32 INCLUDED; the fp32 path
+ * for them is BLA_UNET_ATTENTION_F32_ONLINE (above; bla_unet_create_attention below).  At the reference's constants that is the four 16 x 16 blocks (S = 256); the 4 x 4 mid block (S = 16) is fp32 in mode 0.
  * A block that neither predicate accepts (e.g. 36 x 36 images: S = 324 at level 1), heads < 1 or heads key_dim > 256: BLA_ERR_INVALID, nothing allocated
  * is left behind, *out untouched.  A heads > 1 model allocates P ([B][heads][S][S]) only for the blocks the fp32 heads predicate accepts; its other per-block
  * buffers beside q, k, v, attention are B heads S floats (the row log-sum-exp / the row dots): no S x S buffer exists for the long blocks. */
 BLA_API bla_status bla_unet_create_heads(bla_unet** out, const bla_unet_config* cfg, int batch, int products, int heads);
 BLA_API int bla_unet_heads(const bla_unet* m);                  /* the number of heads the model was created with (1 for every other create entry) */
+/* The same network created IN its attention mode.  attention = BLA_UNET_ATTENTION_F32, _BF16 or _BF16_ONLINE: bla_unet_create_heads followed by
+ * bla_unet_set_attention -- the same refusals, bits and bytes.  BLA_UNET_ATTENTION_F32_ONLINE: every block has a route (a 36 x 36 or 40 x 40 multi-head model is
+ * created), a block routed to the online fp32 entries owns B heads S floats beside q, k, v, attention and NO S x S buffer, and the shared gradient workspace is
+ * sized for the largest block that still materialises.  Such a model refuses bla_unet_set_attention to a mode it lacks a route or the buffers for (see there).
+ * Any other `attention`: BLA_ERR_INVALID, *out untouched.  bla_unet_device_bytes: the sum of the device allocations the model owns, in bytes. */
+BLA_API bla_status bla_unet_create_attention(bla_unet** out, const bla_unet_config* cfg, int batch, int products, int heads, int attention);
+BLA_API size_t bla_unet_device_bytes(const bla_unet* m);
 BLA_API int bla_unet_batch(const bla_unet* m);
 BLA_API bla_status bla_unet_destroy(bla_unet* m);
 BLA_API size_t bla_unet_param_count(const bla_unet* m);         /* floats in each bucket (every tensor starts 16-byte aligned) */
